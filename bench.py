@@ -2,7 +2,13 @@
 """RBVAE hot-path benchmark: frames/s of the fused training step (encode + binarise + decode,
 forward + backward + losses + Adam) on synthetic LDM-latent frames.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (frames/s, ms per step).  --full adds the legs
+beyond it: per-step median, per-kernel roofline event legs, end-to-end roof fractions, the other BASELINE configurations
+and the CPU baseline (--no-roofline / --no-others / --no-cpu drop single legs of a --full run).  --dump-outputs DIR
+writes what the last timed step computed (losses, parameters after Adam, gradients; float32 .npy) for output-by-output
+comparison of two builds: the inputs depend on the arguments only.
 
 N > 1 works both ways: launched by torch.distributed.run (RANK / WORLD_SIZE in the environment), or typed as is --
 then this process spawns N fresh rank processes BEFORE anything touches the GPU, waits for them and relays rank 0's
@@ -374,6 +380,16 @@ def other_configs(dev):
     return out
 
 
+def dump_outputs(out_dir, trainer):
+    """What the timed path's last step hands its caller, as float32 .npy (21.7 MB in all at the headline config):
+    losses [total, recon, kl, pair], the flat parameters after the Adam update, the flat gradients it applied."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": trainer.losses, "params": trainer.model._flat, "grads": trainer.gflat}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def load_profile_json(name):
     try:
         with open(os.path.join(ROOT, "profiles", name)) as f:
@@ -388,9 +404,13 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel event legs")
-    ap.add_argument("--no-others", action="store_true", help="skip the other BASELINE configurations (rank 0, 1 GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: per-step median, roofline, other configurations, CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel event legs")
+    ap.add_argument("--no-others", action="store_true",
+                    help="with --full: skip the other BASELINE configurations (rank 0, 1 GPU only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     args = ap.parse_args()
 
@@ -449,17 +469,21 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
-    # per-step times of a second, untimed-by-the-contract run of up to 200 steps: one event behind every step, no host
-    # synchronisation in between (SURVEY.md 8d quotes the median; `value` stays the mean over exactly --steps steps)
-    nmed = min(args.steps, 200)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nmed + 1)]
-    evs[0].record()
-    for i in range(nmed):
-        tr.step(None, TAU)
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nmed))
-    ms_median = per_step[len(per_step) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr)
+    ms_median = None
+    if args.full:
+        # per-step times of a second, untimed-by-the-contract run of up to 200 steps: one event behind every step, no
+        # host synchronisation in between (SURVEY.md 8d quotes the median; `value` stays the mean over exactly --steps)
+        nmed = min(args.steps, 200)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nmed + 1)]
+        evs[0].record()
+        for i in range(nmed):
+            tr.step(None, TAU)
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nmed))
+        ms_median = round(per_step[len(per_step) // 2], 4)
     losses = [float(v) for v in tr.losses.tolist()]
     graphs_captured = sum(len([g for g in gs if g is not None]) for gs in tr._graphs.values())
     if world == 1:
@@ -479,11 +503,12 @@ def main():
     cpu = None
     tname = "unsigned short" if args.dtype == "bf16" else "float"
     nleg = min(args.steps, 20)
-    if not args.no_roofline:
+    roofline_on = args.full and not args.no_roofline
+    if roofline_on:
         # every rank runs the instrumented legs (their steps contain the gradient all-reduce: a collective)
         legs = roofline_leg(tr, nleg, tname, overlap=True)
         legs_iso = roofline_leg(tr, nleg, tname, overlap=False)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline_on:
         peak = MFMA_BF16_PEAK_TFLOPS if args.dtype == "bf16" else 157.3
         traffic = load_profile_json("pmc_traffic.json")
         mfma_busy = load_profile_json("pmc_mfma_busy.json")
@@ -514,41 +539,42 @@ def main():
                 "profiles_ref": {"meta": prof_meta or None, "traffic": traffic.get(dom), "pmc": mfma_busy.get(dom),
                                  "files": ["profiles/pmc_traffic.json", "profiles/pmc_mfma_busy.json", "profiles/pmc_meta.json"]}}
     others = None
-    if rank == 0 and world == 1 and not args.no_others:
+    if args.full and rank == 0 and world == 1 and not args.no_others:
         del tr, ds, plan, table                  # release the headline's buffers before the larger configurations
         torch.cuda.empty_cache()
         others = other_configs(dev)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline()
     if world > 1:
         torch.distributed.barrier()
     if rank == 0:
         value = frames_per_step * world * args.steps / dt
-        hbm_roof, mfma_roof = (ROOF_HBM_FPS, ROOF_MFMA_FPS) if args.dtype == "bf16" else ROOF_F32
-        per_gpu = value / world
-        e2e = {"frames_per_s_per_gpu": round(per_gpu, 1), "hbm_roof_frames_per_s": round(hbm_roof, 0),
-               "frac_hbm": round(per_gpu / hbm_roof, 4), "mfma_roof_frames_per_s": round(mfma_roof, 0),
-               "frac_mfma": round(per_gpu / mfma_roof, 4),
-               "basis": "SURVEY.md 8d: 596.3 MFLOP and 1.805 MB (bf16; 3.611 MB f32) per frame fwd+bwd; 8.0 TB/s, "
-                        "2.5 PFLOP/s bf16 (157.3 TFLOP/s f32)"}
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import ceiling as ceiling_mod
-            c = ceiling_mod.ceiling()
-            step_us = dt / args.steps * 1e6
-            c["achieved_over_critical_path"] = round(c["critical_path_us"] / step_us, 4)
-            c["achieved_over_resource_sum"] = round(c["resource_sum_us"] / step_us, 4)
-            e2e["ceiling"] = c
-        except Exception as e:      # noqa: BLE001 -- the model is documentation, never fatal
-            e2e["ceiling"] = {"error": str(e)[:200]}
-        if roof is not None:
-            roof["e2e"] = e2e
-        else:
-            roof = {"e2e": e2e}
+        if args.full:
+            hbm_roof, mfma_roof = (ROOF_HBM_FPS, ROOF_MFMA_FPS) if args.dtype == "bf16" else ROOF_F32
+            per_gpu = value / world
+            e2e = {"frames_per_s_per_gpu": round(per_gpu, 1), "hbm_roof_frames_per_s": round(hbm_roof, 0),
+                   "frac_hbm": round(per_gpu / hbm_roof, 4), "mfma_roof_frames_per_s": round(mfma_roof, 0),
+                   "frac_mfma": round(per_gpu / mfma_roof, 4),
+                   "basis": "SURVEY.md 8d: 596.3 MFLOP and 1.805 MB (bf16; 3.611 MB f32) per frame fwd+bwd; 8.0 TB/s, "
+                            "2.5 PFLOP/s bf16 (157.3 TFLOP/s f32)"}
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                import ceiling as ceiling_mod
+                c = ceiling_mod.ceiling()
+                step_us = dt / args.steps * 1e6
+                c["achieved_over_critical_path"] = round(c["critical_path_us"] / step_us, 4)
+                c["achieved_over_resource_sum"] = round(c["resource_sum_us"] / step_us, 4)
+                e2e["ceiling"] = c
+            except Exception as e:      # noqa: BLE001 -- the model is documentation, never fatal
+                e2e["ceiling"] = {"error": str(e)[:200]}
+            if roof is not None:
+                roof["e2e"] = e2e
+            else:
+                roof = {"e2e": e2e}
         line = {"metric": "frames/sec (enc+binarise+dec fwd+bwd), batch 256x256, 1/2/4/8 MI355X",
                 "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-                "ms_per_step_median": round(ms_median, 4), "higher_is_better": True,
+                "ms_per_step_median": ms_median, "higher_is_better": True,
                 "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                 "config": {"workload": "percep_RBVAE fused train step (batch gather from the HBM-resident latent table "
                                        "+ fwd+bwd+losses+Adam), item [16,2,8,4,32,32] per GPU = 256 frames/step/GPU "

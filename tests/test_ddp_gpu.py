@@ -129,7 +129,7 @@ def test_bench_gpus2_self_launches():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu", "--no-roofline"], env=env, capture_output=True, text=True, timeout=540)
+                        "--full", "--no-cpu", "--no-roofline"], env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["global_frames_per_step"] == 512 and line["value"] > 0

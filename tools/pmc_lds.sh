@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/pmc_lds; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O -o l -- python3 $R/bench.py --no-cpu --no-roofline --steps 30 > $O/run.log 2>&1 || exit 1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O -o l -- python3 $R/bench.py --full --no-cpu --no-roofline --steps 30 > $O/run.log 2>&1 || exit 1
 cd $R && python3 - <<'PY'
 import csv, glob, collections, os
 f = glob.glob("gpurun_out/pmc_lds/**/*counter_collection.csv", recursive=True)[0]

@@ -5,10 +5,10 @@
 # -> files under gpurun_out/refresh/ ; copy the summaries into profiles/ (named per round).
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/refresh; mkdir -p $O
-cd $R && python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+cd $R && python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 tail -1 $O/bench_default.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --no-cpu --no-others > $O/bench_under_rocprof.json 2> $O/stats.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --full --no-cpu --no-others > $O/bench_under_rocprof.json 2> $O/stats.err || exit 1
 echo stats done
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o f -- python3 $R/bench.py --no-cpu --no-roofline --no-others --steps 40 > $O/fetch.log 2>&1 || exit 1
 echo fetch done
