@@ -1,0 +1,168 @@
+"""Element-wise error bounds and guarded buffers for the conv / GEMM kernel tests.
+
+ref_and_scale computes an operation in float64 from the operands as the kernel sees them (already rounded to their
+storage type) together with its condition scale S = the same operation on |operands|, i.e. S = sum |a * b| per output
+element.  check then asserts, element by element,
+
+    |got - ref| <= (1 + u_out) * |scale| * c_acc(K) * S + u_out * |ref| (+ u_out * |pre|) + tiny
+
+where c_acc bounds the f32 accumulation (an exact k-ordered f32 fma chain: 0.75-1.5e-7 * S for K <= 1024 and
+3.5e-7 * S at K = 4096, taken as 4e-7 * max(1, K / 1024); bf16 products are exact in f32, so the same term applies),
+and u_out is the rounding of the stored value: 2^-8 for bf16 (half an ulp, relative: 8 significant bits), whose
+(1 + u_out) factor carries the accumulation error through that rounding; 2^-23 for f32 (two f32 roundings: the bias
+add and the scale).  The f32 roundings before a bf16 store (<= 2^-23 |ref|) fit inside |scale| * c_acc * S, because
+S >= |acc + bias| = |ref / scale| before ReLU.  `pre` is the value before a second
+rounding in storage precision (the residual addend is added to the already-rounded result).  ReLU, the gate and an
+explicit keep-mask are 1-Lipschitz or exact, so the same bound covers them.
+
+guarded() hands out outputs inside a buffer of NaN sentinels (a guard band of at least one 128-row tile before and
+after the interior, and the columns ncols..ld of every interior row); assert_guards() then asserts that no byte outside
+the interior changed and that every interior element was written.  The same buffers, filled with data, serve as
+poisoned inputs: a read the ABI does not allow reaches an output as NaN."""
+import torch
+import torch.nn.functional as F
+
+U_OUT = {torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -23}
+TINY = 1e-30
+# NaN bit patterns that no kernel produces by arithmetic (the default quiet NaN of both types has a zero payload)
+SENTINEL = {torch.bfloat16: (torch.int16, 0xFFC1 - 0x10000), torch.float32: (torch.int32, 0x7FC0DEAD)}
+GUARD_ROWS = 128
+
+
+def c_acc(K, dtype=torch.float32):
+    """Accumulation error per unit of S for a K-long f32 accumulation (f32 products: an exact fma chain; bf16 products
+    are exact in f32 and accumulate the same way)."""
+    return 4e-7 * max(1.0, K / 1024.0)
+
+
+# ---- float64 references -------------------------------------------------------------------------------------------
+
+def _conv2d(x, w, stride=1, padding=1):
+    return F.conv2d(x, w, None, stride=stride, padding=padding)
+
+
+def _conv_transpose2d(x, w, stride=2, padding=1, output_padding=1):
+    return F.conv_transpose2d(x, w, None, stride=stride, padding=padding, output_padding=output_padding)
+
+
+def _linear(a, w):
+    return a @ w.t()
+
+
+def _wgrad_conv2d(dy, x, wshape, stride=1, padding=1):
+    """dW[co][ci][kh][kw] of conv2d(x, W) for the output gradient dy."""
+    return torch.nn.grad.conv2d_weight(x, wshape, dy, stride=stride, padding=padding)
+
+
+def _wgrad_conv_transpose2d(dy, x, wshape, stride=2, padding=1):
+    """dW[ci][co][kh][kw] of conv_transpose2d(x, W) (x: [N][ci][H][W]): the transposed conv is conv2d's input
+    gradient, so its weight gradient is conv2d's with the roles of input and output gradient exchanged."""
+    return torch.nn.grad.conv2d_weight(dy, wshape, x, stride=stride, padding=padding)
+
+
+def _wgrad_linear(dy, x):
+    return dy.t() @ x
+
+
+OPS = {"conv2d": _conv2d, "conv_transpose2d": _conv_transpose2d, "linear": _linear,
+       "wgrad_conv2d": _wgrad_conv2d, "wgrad_conv_transpose2d": _wgrad_conv_transpose2d, "wgrad_linear": _wgrad_linear}
+
+
+def ref_and_scale(op, a, b, **kw):
+    """(ref, S) of OPS[op](a, b, **kw) in float64 on the CPU: a and b as the kernel sees them (storage-rounded)."""
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    f = OPS[op]
+    return f(a, b, **kw), f(a.abs(), b.abs(), **kw)
+
+
+def rows(t):
+    """[N][C][H][W] -> NHWC rows [N*H*W][C]."""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+# ---- the element-wise check ---------------------------------------------------------------------------------------
+
+def bound(ref, S, *, out_dtype, K, scale=1.0, pre=None):
+    u = U_OUT[out_dtype]
+    b = (1 + u) * abs(scale) * c_acc(K) * S + u * ref.abs() + TINY
+    if pre is not None:
+        b = b + u * pre.abs()
+    return b
+
+
+def check(got, ref, S, *, out_dtype, K, scale=1.0, pre=None, nhw=None, what=""):
+    """Assert |got - ref| <= bound element-wise; got, ref and S are [rows][C] (NHWC rows when nhw = (N, H, W) is given,
+    which maps the worst row back to (image, y, x)).  Returns the worst |err| / bound."""
+    got = got.detach().cpu().double()
+    ref, S = ref.double().reshape(got.shape), S.double().reshape(got.shape)
+    if pre is not None:
+        pre = pre.double().reshape(got.shape)
+    bnd = bound(ref, S, out_dtype=out_dtype, K=K, scale=scale, pre=pre)
+    err = (got - ref).abs()
+    ratio = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err / bnd)
+    bad = ~(err <= bnd)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    if bool(bad.any()):
+        flat = int(torch.argmax(ratio.reshape(-1)))
+        r, c = divmod(flat, got.shape[-1]) if got.dim() > 1 else (flat, 0)
+        where = f"(row {r}, channel {c})"
+        if nhw is not None:
+            n, rem = divmod(r, nhw[1] * nhw[2])
+            where += f" = (image {n}, y {rem // nhw[2]}, x {rem % nhw[2]}, c {c})"
+        g, f = got.reshape(-1)[flat].item(), ref.reshape(-1)[flat].item()
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bound; worst "
+                             f"|err|/bound = {worst:.3g} at {where}: got {g!r}, ref {f!r}, bound {bnd.reshape(-1)[flat]:.3g}")
+    return worst
+
+
+def colsum_bound(vals):
+    """Bound of an f32 sum of the rows of vals (any order): (n - 1) * 2^-24 * sum |v| (recursive summation)."""
+    return max(vals.shape[0] - 1, 1) * 2.0 ** -24 * vals.abs().sum(0) + TINY
+
+
+# ---- guarded buffers ----------------------------------------------------------------------------------------------
+
+class Guarded:
+    """A [guard + rows + guard][ld] buffer of sentinels; .view is the [rows][ld] interior handed to a kernel, .out its
+    [rows][ncols] part (the declared elements)."""
+
+    def __init__(self, rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda"):
+        ib, pat = SENTINEL[dtype]
+        es = torch.empty((), dtype=dtype).element_size()
+        assert (ld * es) % 16 == 0, "rows of a guarded buffer keep 16-byte alignment"
+        assert ncols <= ld
+        self.rows, self.ld, self.ncols, self.dtype, self.g = rows, ld, ncols, dtype, max(guard_rows, GUARD_ROWS)
+        self.buf = torch.full((self.g + rows + self.g, ld), pat, dtype=ib, device=device).view(dtype)
+        self.view = self.buf[self.g:self.g + rows]
+        self.out = self.view[:, :ncols]
+        assert self.view.data_ptr() % 16 == 0
+
+    def fill(self, t):
+        """Store t ([rows][ncols], converted to the buffer's type) into the interior; the rest stays sentinel."""
+        self.out.copy_(t.reshape(self.rows, self.ncols).to(self.dtype))
+        return self
+
+
+def guarded(rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda"):
+    return Guarded(rows, ld, ncols, dtype, guard_rows, device)
+
+
+def poisoned(t, ld, dtype, guard_rows=GUARD_ROWS, device="cuda"):
+    """Input operand t ([rows][ncols]) inside NaN guard rows and NaN padding columns ncols..ld."""
+    t = t.reshape(t.shape[0], -1)
+    return Guarded(t.shape[0], ld, t.shape[1], dtype, guard_rows, device).fill(t.to(device))
+
+
+def assert_guards(g, what=""):
+    """Every element outside g's interior still holds the sentinel; no interior element does (all were written)."""
+    ib, pat = SENTINEL[g.dtype]
+    bits = g.buf.view(ib).cpu()
+    sent = bits == pat
+    inner = torch.zeros_like(sent)
+    inner[g.g:g.g + g.rows, :g.ncols] = True
+    stray = (~sent & ~inner).nonzero()
+    assert stray.shape[0] == 0, (f"{what}: {stray.shape[0]} elements outside the output were written; first at buffer "
+                                 f"(row {int(stray[0, 0]) - g.g}, col {int(stray[0, 1])}) relative to the interior")
+    unwritten = (sent & inner).nonzero()
+    assert unwritten.shape[0] == 0, (f"{what}: {unwritten.shape[0]} output elements were never written; first at "
+                                     f"(row {int(unwritten[0, 0]) - g.g}, col {int(unwritten[0, 1])})")
