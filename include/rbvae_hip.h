@@ -556,6 +556,32 @@ int rbvae_deconv3x3s2_halo(int dtype, const void* A, const void* W, void* Out, c
                            int ldo, int relu, int drop_mode, float drop_p, float scale, unsigned long long seed,
                            const unsigned long long* seed_dev, float* colsum_ws, void* stream);
 
+/* ---- raw frames in (csrc/frames.hip) ---------------------------------------------------------------
+ * Frames are u8 RGB, NHWC (3 channels, contiguous), a batch of N (<= 65535) images.
+ * rbvae_resample_u8: one separable pass of Pillow's 8-bit resampler (Image.resize as called by
+ * src/stable-diffusion/get_percep_embeddings.py:59-66, LANCZOS, and by T.Resize in
+ * models/contrastive_RBVAE/contrastive_RBVAE_train.py:110-114, BILINEAR; Pillow's Resample.c).  bounds [out][2] =
+ * (first source index, taps) and kk [out][ksize] int32 coefficients with 22 fractional bits come from the host
+ * (frames.py resample_coeffs); acc = (1 << 21) + sum_t src[first + t] * kk[o][t] in int32, result clamp(acc >> 22, 0, 255).
+ *   vertical = 0: in [N][in_h][in_w][3] -> out [N][out_h][out_w][3], output row r = source row row0 + r resampled
+ *                 along the width (row0 + out_h <= in_h: Pillow's horizontal pass covers only the rows the vertical pass
+ *                 reads, ybox_first .. ybox_last);
+ *   vertical = 1: in [N][in_h][W][3] -> out [N][out_h][W][3] (in_w == out_w == W), output row yy reads source rows
+ *                 bounds[yy][0] - row0 + t (Pillow's shift of the vertical bounds by ybox_first).
+ * Taps outside the source are skipped.  RBVAE_E_UNSUPPORTED when a horizontal pass's two rows exceed 64 KB of LDS. */
+int rbvae_resample_u8(const unsigned char* in, unsigned char* out, int N, int in_h, int in_w, int out_h, int out_w,
+                      int vertical, int row0, const int* bounds, const int* kk, int ksize, void* stream);
+/* ToTensor -> add_gaussian_noise (kind 1) / add_occlusion (kind 2) -> ToPILImage
+ * (scripts/evaluation/state_consistency_eval/embedding_matching.py:141-193 as called at :241-248), u8 in, u8 out, f32
+ * operations in the reference's order: x = u8 / 255; kind 1: x = clamp(x + (noise * std + mean), 0, 1) with noise f32
+ * [N][3][H][W] (randn_like of each frame's [1,3,H,W] tensor); kind 2: x = 0.5 inside the square boxes[n] = (x, y, size),
+ * int32 [N][3]; then trunc(x * 255) (.mul(255).byte()). */
+int rbvae_perturb_u8(const unsigned char* in, unsigned char* out, int N, int H, int W, int kind, const float* noise,
+                     float std_, float mean_, const int* boxes, void* stream);
+/* u8 [N][H][W][3] -> f32 [N][3][H][W]: mode 0 = T.ToTensor (x / 255, contrastive_RBVAE_train.py:110-114); mode 1 =
+ * load_img's np.float32(x) / 255 then 2x - 1 (get_percep_embeddings.py:68-71, embedding_matching.py:335-338). */
+int rbvae_u8_to_input(const unsigned char* in, float* out, int N, int H, int W, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

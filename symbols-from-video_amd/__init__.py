@@ -16,3 +16,7 @@ from .ldm import LDMEncoder  # noqa: F401
 from .model import Seq2SeqBinaryVAE, binary_concrete_logits  # noqa: F401
 from .trainer import FusedTrainer, noise_key  # noqa: F401
 from .compose import OnTheFlyLatentTrainer  # noqa: F401
+from .frames import (contrastive_input, extract_embeddings, load_frames, perturb_u8, resample_coeffs,  # noqa: F401
+                     resize_u8, sd_input, to_reference_dict, u8_to_input)
+from .robustness import (adjacent_hamming, most_common_codes, reference_draws, state_codes_under,  # noqa: F401
+                         state_consistency_under)
