@@ -82,22 +82,27 @@ def rows(t):
 
 # ---- the element-wise check ---------------------------------------------------------------------------------------
 
-def bound(ref, S, *, out_dtype, K, scale=1.0, pre=None):
+def bound(ref, S, *, out_dtype, K, scale=1.0, pre=None, S_in=None, u_in=0.0):
     u = U_OUT[out_dtype]
     b = (1 + u) * abs(scale) * c_acc(K) * S + u * ref.abs() + TINY
     if pre is not None:
         b = b + u * pre.abs()
+    if S_in is not None:
+        b = b + (1 + u) * abs(scale) * u_in * S_in
     return b
 
 
-def check(got, ref, S, *, out_dtype, K, scale=1.0, pre=None, nhw=None, what=""):
+def check(got, ref, S, *, out_dtype, K, scale=1.0, pre=None, nhw=None, what="", S_in=None, u_in=0.0):
     """Assert |got - ref| <= bound element-wise; got, ref and S are [rows][C] (NHWC rows when nhw = (N, H, W) is given,
-    which maps the worst row back to (image, y, x)).  Returns the worst |err| / bound."""
+    which maps the worst row back to (image, y, x)).  S_in / u_in: the staged-operand term (staged_u_in).  Returns the
+    worst |err| / bound."""
     got = got.detach().cpu().double()
     ref, S = ref.double().reshape(got.shape), S.double().reshape(got.shape)
     if pre is not None:
         pre = pre.double().reshape(got.shape)
-    bnd = bound(ref, S, out_dtype=out_dtype, K=K, scale=scale, pre=pre)
+    if S_in is not None:
+        S_in = S_in.double().reshape(got.shape)
+    bnd = bound(ref, S, out_dtype=out_dtype, K=K, scale=scale, pre=pre, S_in=S_in, u_in=u_in)
     err = (got - ref).abs()
     ratio = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err / bnd)
     bad = ~(err <= bnd)
@@ -118,6 +123,56 @@ def check(got, ref, S, *, out_dtype, K, scale=1.0, pre=None, nhw=None, what=""):
 def colsum_bound(vals):
     """Bound of an f32 sum of the rows of vals (any order): (n - 1) * 2^-24 * sum |v| (recursive summation)."""
     return max(vals.shape[0] - 1, 1) * 2.0 ** -24 * vals.abs().sum(0) + TINY
+
+
+U32 = 2.0 ** -24              # unit roundoff of f32
+
+
+# ---- an operand computed in the kernel: GroupNorm (+ swish) applied while the input is staged -----------------------
+
+def staged_operand(x, scale, shift, swish):
+    """float64 a = swish?(x * scale + shift) of an [N][C][H][W] input (scale / shift [N][C]), NOT rounded to the storage
+    type: the reference operand of a kernel that computes a in f32 and rounds it before the MFMA.  Also returns
+    max |x * scale + shift| (for staged_u_in)."""
+    t = x.double() * scale.double()[:, :, None, None] + shift.double()[:, :, None, None]
+    a = t * torch.sigmoid(t) if swish else t
+    return a, float(t.abs().max()) if t.numel() else 0.0
+
+
+def staged_u_in(dtype, swish, tmax):
+    """Relative error of the staged operand a against staged_operand's float64 value: u_in = 2^-8 (round to nearest
+    bf16) + c_eval for bf16, c_eval for f32 (the f32 value is the MFMA operand).  c_eval, in units u = 2^-24:
+      t = fmaf(x, scale, shift): one rounding, |dt| <= u |t|; through swish (|t swish'(t) / swish(t)| <= 1 + |t|):
+      (1 + |t|) u.  bf16 swish, t * rcp(1 + exp2(-1.44269504 t)): the constant's and the product's rounding put an
+      absolute error of 2 u |1.4427 t| into exp2's argument, i.e. a relative 2 |t| u into e = exp2(..); v_exp_f32 and
+      v_rcp_f32 are 1 ulp (2 u) each; 1 + e and the final product one rounding each; a relative error of e moves the
+      sigmoid by at most as much: (1 + |t|) + 2 |t| + 2 + 1 + 2 + 1 = 7 + 3 |t|.  f32 swish, t / (1 + expf(-t)):
+      expf 1 ulp, 1 + e, the division and the product one rounding each: 6 + |t|.  Without swish: 1.
+    c_eval = (8 + 3 tmax) u covers both swish forms, tmax = max |t| of the case."""
+    c_eval = (8 + 3 * tmax) * U32 if swish else U32
+    return (2.0 ** -8 if dtype == torch.bfloat16 else 0.0) + c_eval
+
+
+# ---- GroupNorm statistics out of an epilogue ---------------------------------------------------------------------
+
+def stats_height(cg):
+    """Additions any one stored value goes through on its way into conv_halo_k's (mean, M2) of a tile and group of cg
+    channels (csrc/conv_halo.hip): <= 16 rows per thread, two lane merges, eight waves, cg channels, two divisions;
+    the recursive-summation bound of a tree is (height) u sum |terms|."""
+    return cg + 28
+
+
+def tile_stats_bounds(n, cg, sum_abs, amax, m2):
+    """Bounds of the kernel's f32 (mean, M2) of one tile and group: n values (pixels x cg), sum |x|, max |x| and the
+    float64 M2 of the stored values.  mean: h u sum|x| / n.  M2: every partial mean is off by at most E = h u max|x|;
+    the squared deviations of a partial from its OWN mean cancel that to first order, the merge terms
+    n_a n_b / n (mean_a - mean_b)^2 do not: at most 2 E sqrt(W M2) per merge level (Cauchy-Schwarz, W <= n) over <= 4
+    levels, plus n E^2 per level and for the threads; the sums of the nonnegative terms (2 h + 4) u M2."""
+    h = stats_height(cg)
+    E = h * U32 * amax
+    bm = h * U32 * sum_abs / n + TINY
+    bM2 = (2 * h + 4) * U32 * m2 + 8 * E * (n * m2) ** 0.5 + 5 * n * E * E + TINY
+    return bm, bM2, E
 
 
 # ---- guarded buffers ----------------------------------------------------------------------------------------------
@@ -141,6 +196,18 @@ class Guarded:
         """Store t ([rows][ncols], converted to the buffer's type) into the interior; the rest stays sentinel."""
         self.out.copy_(t.reshape(self.rows, self.ncols).to(self.dtype))
         return self
+
+
+class GuardedFlat(Guarded):
+    """n contiguous elements inside `guard` sentinels on each side (packed outputs such as float2 statistics)."""
+
+    def __init__(self, n, dtype, guard=1024, device="cuda"):
+        ib, pat = SENTINEL[dtype]
+        self.rows, self.ld, self.ncols, self.dtype, self.g = n, 1, 1, dtype, guard
+        self.buf = torch.full((guard + n + guard, 1), pat, dtype=ib, device=device).view(dtype)
+        self.view = self.buf[guard:guard + n].view(-1)
+        self.out = self.view
+        assert self.view.data_ptr() % 16 == 0
 
 
 def guarded(rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda"):

@@ -81,7 +81,9 @@ def _worker(rank, world, port, q):
     dist.all_gather(both, g_h)
     assert all(torch.equal(both[0], b_) for b_ in both)
     if rank == 0:
-        q.put((flat.clone(), gflat.clone()))
+        # by value (numpy arrays): a torch tensor crosses the queue as a file descriptor that the parent fetches from
+        # this process's resource sharer, which is gone once this rank has exited -- a race the parent could lose
+        q.put((flat.numpy().copy(), gflat.numpy().copy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -98,7 +100,7 @@ def test_two_rank_gradient_equals_global_batch_gradient():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p_ in procs:
         p_.start()
-    flat, gflat = q.get(timeout=240)
+    flat, gflat = (torch.from_numpy(a) for a in q.get(timeout=240))
     for p_ in procs:
         p_.join(timeout=60)
         assert p_.exitcode == 0
