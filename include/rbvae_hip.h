@@ -368,8 +368,14 @@ int rbvae_lstm_bwd(const float* wblk, const float* wT, const float* acts, const 
  * (T + layers - 1 dependent steps); 32 < L <= 128 (the reference's latent_dim 50 / 75 / 100, best_models.txt) -- layer by
  * layer, a gate row shared by two lanes (eight lanes per hidden unit in the backward pass), the input half W_ih x_t of
  * every time step computed in one batch off the dependent chain. */
-/* Extended forms that take over the small kernels around the stacks (wavefront kernel only: L <= 32,
- * layers * roundup64(4L) <= 1024, else RBVAE_E_INVALID):
+/* rbvae_lstm_fwd_wave_ok / rbvae_lstm_bwd_wave_ok: 1 when the wavefront kernel serves the shape -- L <= 32,
+ * layers * roundup64(4L) <= 1024, and the sequence's state within 64 KB of LDS: (layers+1)*T*L + layers*4L floats forward,
+ * T*L + layers*(5*T*L + 12L) backward (at L = 32 with 4 layers: T <= 99 forward, T <= 22 backward).  The dispatchers ask
+ * these functions themselves; longer sequences run layer by layer (plain rbvae_lstm_fwd / _bwd only). */
+int rbvae_lstm_fwd_wave_ok(int T, int L, int layers);
+int rbvae_lstm_bwd_wave_ok(int T, int L, int layers);
+/* Extended forms that take over the small kernels around the stacks (wavefront kernel only: rbvae_lstm_fwd_wave_ok /
+ * rbvae_lstm_bwd_wave_ok, else RBVAE_E_INVALID):
  *  - in_parts / g_top_parts: the stack input (forward) / top-layer gradient (backward) as `nparts` K-split slabs of
  *    the fc product that feeds them (rbvae_skinny_linear_parts; slab q at + q*part_stride floats), summed in slab
  *    order in the kernel's prologue; the forward also writes the sum to slot 0 of hs_all.  in_parts NULL /

@@ -1663,6 +1663,23 @@ using namespace rbvae;
 
 extern "C" {
 
+// The wavefront kernels' own range: one thread group per layer and the whole sequence's state in LDS.  The dispatchers
+// below and the callers that want the slab / cast / binarise epilogues (which only these kernels have) ask the same
+// two functions.
+int rbvae_lstm_fwd_wave_ok(int T, int L, int layers) {
+    if (T <= 0 || L <= 0 || layers <= 0 || L > 32) return 0;
+    const int threads = ((4 * L + 63) / 64) * 64;
+    const size_t wlds = ((size_t)(layers + 1) * T * L + (size_t)layers * 4 * L) * sizeof(float);
+    return (long)layers * threads <= 1024 && wlds <= 64 * 1024;
+}
+
+int rbvae_lstm_bwd_wave_ok(int T, int L, int layers) {
+    if (T <= 0 || L <= 0 || layers <= 0 || L > 32) return 0;
+    const int threads = ((4 * L + 63) / 64) * 64;
+    const size_t wlds = ((size_t)T * L + (size_t)layers * T * 5 * L + (size_t)layers * 12 * L) * sizeof(float);
+    return (long)layers * threads <= 1024 && wlds <= 64 * 1024;
+}
+
 static int lstm_fwd_impl(const float* wblk, const float* wT, float* hs_all, float* hprev, float* acts, float* cs, int S,
                          int T, int L, int layers, const float* in_parts, int nparts, long part_stride, void* cast_out,
                          int cast_dtype, int cast_ld, void* stream) {
@@ -1679,7 +1696,7 @@ static int lstm_fwd_impl(const float* wblk, const float* wT, float* hs_all, floa
     hipStream_t st = (hipStream_t)stream;
     // wavefront kernel: one thread group per layer (weights in registers, L <= 32)
     const size_t wlds = (size_t)((layers + 1) * T * L + layers * 4 * L) * sizeof(float);
-    if (L <= 32 && layers * threads <= 1024 && wlds <= 64 * 1024) {
+    if (rbvae_lstm_fwd_wave_ok(T, L, layers)) {
         if (L == 32)
             hipLaunchKernelGGL((lstm_fwd_wave_k<32, true, true>), dim3(S), dim3(layers * threads), wlds, st, wblk, wT,
                                hs_all, hprev, acts, cs, S, T, L, layers, threads, in_parts, nparts, part_stride, cast_out,
@@ -1695,7 +1712,7 @@ static int lstm_fwd_impl(const float* wblk, const float* wT, float* hs_all, floa
         RBVAE_CHECK_LAUNCH("lstm_fwd_wave");
         return RBVAE_OK;
     }
-    RBVAE_CHECK_ARG(!in_parts && !cast_out, "lstm_fwd_ex: only the wavefront kernel (L <= 32, layers * roundup64(4L) <= 1024) sums input slabs / writes a cast copy");
+    RBVAE_CHECK_ARG(!in_parts && !cast_out, "lstm_fwd_ex: only the wavefront kernel (rbvae_lstm_fwd_wave_ok) sums input slabs / writes a cast copy");
     if (L > 32) {
         // two lanes per gate row, the input half batched over time (lstm_fwd_big_k)
         const int RP = ((4 * L + 63) / 64) * 64;
@@ -1799,7 +1816,7 @@ static int lstm_bwd_impl(const float* wblk, const float* wT, const float* acts, 
     RBVAE_CHECK_ARG(lds <= 64 * 1024, "lstm_bwd: T*L=%d too large", T * L);
     hipStream_t st = (hipStream_t)stream;
     const size_t wlds = (size_t)(T * L + layers * T * 5 * L + layers * 12 * L) * sizeof(float);
-    if (L <= 32 && layers * threads <= 1024 && wlds <= 64 * 1024) {
+    if (rbvae_lstm_bwd_wave_ok(T, L, layers)) {
         if (L == 32)
             hipLaunchKernelGGL((lstm_bwd_wave_k<32, true>), dim3(S), dim3(layers * threads), wlds, st, wblk, acts, cs,
                                g_top, dG, dx, S, T, L, layers, threads, nparts, part_stride, cast_out, cast_bf16, cast_ld,
@@ -1811,7 +1828,7 @@ static int lstm_bwd_impl(const float* wblk, const float* wT, const float* acts, 
         RBVAE_CHECK_LAUNCH("lstm_bwd_wave");
         return RBVAE_OK;
     }
-    RBVAE_CHECK_ARG(nparts == 1 && !cast_out && !dx_colsum && !bb.on, "lstm_bwd_ex: only the wavefront kernel (L <= 32, layers * roundup64(4L) <= 1024) sums gradient slabs / writes a cast copy");
+    RBVAE_CHECK_ARG(nparts == 1 && !cast_out && !dx_colsum && !bb.on, "lstm_bwd_ex: only the wavefront kernel (rbvae_lstm_bwd_wave_ok) sums gradient slabs / writes a cast copy / binarises");
     if (L > 32) {
         const int KP = ((L + 15) / 16) * 16;
         const size_t blds = (size_t)((2 * T + 1) * BIG_VS + T * 4 * BIG_SEG) * sizeof(float);

@@ -769,7 +769,10 @@ class Engine:
         sv.hs_dec = self._E(nl + 1, S, T, Ld, dtype=torch.float32)
         sv.e = self._E(N, Ld, dtype=torch.float32) if v.simple_order else sv.hs_enc[0].view(N, Ld)
         e_parts = None
-        if self.fc_split > 1:
+        # the slab input / cast output exist in the wavefront kernel only, whose LDS need grows with T: asked per call of
+        # the query the C dispatcher uses itself (long sequences take the plain kernels, the unsplit fc and rbvae_cast_pad)
+        fwd_wave = self.lstm_cast and bool(L.query("rbvae_lstm_fwd_wave_ok", T, Ld, nl))
+        if self.fc_split > 1 and fwd_wave:
             e_parts = self._buf((N, "e_parts"), self.fc_split * N * Ld)
             L.call("rbvae_skinny_linear_parts", self.dt, sv.a3, self.Wfc, P("encoder_cnn.fc.bias"), e_parts, N, Ld,
                    self.F3, self.F3, self.F3, Ld, self.fc_split)
@@ -832,7 +835,7 @@ class Engine:
                        float(kl_p if kl_p is not None else 0.5), 1e-8, 1, int(seed) * 8 + 5, self.seed_dev)
             if encode_only:
                 return {"z": sv.z.view(S, T, Ld), "hs": hs, "saved": sv}
-            if self.lstm_cast:
+            if fwd_wave:
                 sv.ds_pad = self._E(N, self.Lp)
                 L.call("rbvae_lstm_fwd_ex", wdec, self.wT_dec, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec, S, T, Ld, nl,
                        None, 1, 0, sv.ds_pad, self.dt, self.Lp)
@@ -848,7 +851,7 @@ class Engine:
             L.call("rbvae_lstm_fwd", wdec, self.wT_dec, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec, S, T, Ld, nl)
         ds = sv.hs_dec[nl]
         # decoder CNN
-        if not ((self.lstm_cast or fused_pair) and not v.simple_order):
+        if not ((fwd_wave or fused_pair) and not v.simple_order):
             sv.ds_pad = self._E(N, self.Lp)
             L.call("rbvae_cast_pad", self.dt, ds, sv.ds_pad, N, Ld, self.Lp)
         sv.f = self._E(N * h3 * w3, c3)
@@ -1063,7 +1066,11 @@ class Engine:
         defer_side = self.overlap
         if not defer_side:
             issue_decoder_side()
-        if self.fc_split > 1:
+        # as in forward(): slab sums, the cast copy, the column sums and the fused binarise backward are the wavefront
+        # kernel's, which long sequences do not fit
+        bwd_wave = self.lstm_cast and bool(L.query("rbvae_lstm_bwd_wave_ok", T, Ld, nl))
+        split = self.fc_split if bwd_wave else 1
+        if split > 1:
             dds = tmp("dds", self.fc_split, N, Ld, dtype=f32)
             L.call("rbvae_skinny_linear_parts", self.dt, df, self.WdfcT, None, dds, N, Ld, self.F3, self.F3, self.F3,
                    Ld, self.fc_split)
@@ -1076,19 +1083,19 @@ class Engine:
         dGe = tmp("dG_enc", nl, S, T, 4 * Ld, dtype=f32)
         d_in_dec = tmp("d_in_dec", N, Ld, dtype=f32)
         de = tmp("de", N, Ld, dtype=f32)
-        pair_bwd = (self.lstm_pair_bwd and not v.simple_order and self.lstm_cast and self.bin_bwd_fused
+        pair_bwd = (self.lstm_pair_bwd and not v.simple_order and bwd_wave and self.bin_bwd_fused
                     and L.query("rbvae_lstm_pair_bwd_ok", T, Ld, nl))
         if pair_bwd:
             # decoder stack -> binarise backward (+ fused KL) -> encoder stack: one wavefront launch
             de_pad = tmp("de_pad", N, self.Lp)
             de_sums = self._buf((N, "de_sums"), S * Ld)
-            nparts = self.fc_split if self.fc_split > 1 else 1
+            nparts = split
             L.call("rbvae_lstm_pair_bwd", wenc, wdec, sv.acts_enc, sv.cs_enc, sv.acts_dec, sv.cs_dec, dds, nparts, N * Ld,
                    None if g_z is None else g_z.reshape(N, Ld).contiguous(), sv.y, sv.z,
                    None if g_hs is None else g_hs.reshape(N, Ld).contiguous(), float(sv.tau), sv.tau_dev, float(kl_weight),
                    float(kl_p), 1e-8, 1, dGe, dG, de, d_in_dec if self.keep_dz else None, de_pad, self.dt, self.Lp, de_sums,
                    S, T, Ld, nl)
-        elif self.fc_split > 1:
+        elif split > 1:
             L.call("rbvae_lstm_bwd_ex", wdec, sv.acts_dec, sv.cs_dec, dds, self.fc_split, N * Ld, dG, d_in_dec, None, 0, 0,
                    None, S, T, Ld, nl)
         else:
@@ -1102,7 +1109,7 @@ class Engine:
                 gz = gz + g_z.reshape(N, Ld)
             de_pad = None
             de_sums = None
-            if self.lstm_cast and self.bin_bwd_fused:
+            if bwd_wave and self.bin_bwd_fused:
                 # binarise backward (+ fused KL) in the prologue of the encoder stack's BPTT launch
                 de_pad = tmp("de_pad", N, self.Lp)
                 de_sums = self._buf((N, "de_sums"), S * Ld)
@@ -1120,7 +1127,7 @@ class Engine:
                            float(kl_p), 1e-8, 1)
                     if g_hs is not None:
                         dh = dh + g_hs.reshape(N, Ld)
-                if self.lstm_cast:
+                if bwd_wave:
                     de_pad = tmp("de_pad", N, self.Lp)
                     de_sums = self._buf((N, "de_sums"), S * Ld)        # per-sequence column sums of de: fc bias gradient
                     L.call("rbvae_lstm_bwd_ex", wenc, sv.acts_enc, sv.cs_enc, dh, 1, 0, dGe, de, de_pad, self.dt, self.Lp,

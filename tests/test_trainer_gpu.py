@@ -133,6 +133,31 @@ def test_fused_step_parameter_ranges(variant, in_ch, B, T, Ld, hw):
         assert float((gr - rf).norm()) <= 2e-3 * max(float(rf.norm()), 1e-7), k
 
 
+def _long_sequence_cases():
+    """Latent 32 with the percep variant's 4 LSTM layers: T = the first sequence length the backward wavefront kernel
+    refuses (the encoder's fused binarise backward, the cast copy and the slab sums have to fall back), and a T where
+    only the two-stack backward launch is refused -- both from the restated dispatch of tests/_lstm_cases.py.  16 x 16
+    frames are the smallest the model takes; 16 x 32 is the smallest whose fc layers run K-split (F3 = 2048)."""
+    import _lstm_cases as C
+    T_wave, T_pair = C.T_BWD_32x4, C.T_PAIR_BWD_32x4
+    assert C.bwd_dispatch(T_wave, 32, 4) == "lstm_bwd_k<32>" and C.bwd_dispatch(T_wave - 1, 32, 4).startswith("lstm_bwd_wave_k")
+    assert not C.pair_bwd_ok(T_pair, 32, 4) and C.bwd_wave_ok(T_pair, 32, 4) and C.pair_bwd_ok(T_pair - 1, 32, 4)
+    T_fwd = C.T_FWD_32x4                       # ... and the first T the forward wavefront kernel refuses
+    assert C.fwd_dispatch(T_fwd, 32, 4) == "lstm_fwd_k<32>" and C.fwd_dispatch(T_fwd - 1, 32, 4).startswith("lstm_fwd_wave_k")
+    return [(T_wave, (16, 16)), (T_pair, (16, 16)), (T_wave, (16, 32)), (T_fwd, (16, 32))]
+
+
+@pytest.mark.parametrize("T,hw", _long_sequence_cases())
+def test_fused_step_long_sequences(T, hw):
+    """The engine chooses the LSTM launches per call from the queries the C dispatchers use themselves
+    (rbvae_lstm_*_wave_ok, rbvae_lstm_pair_*_ok): a sequence too long for the wavefront kernels runs on the plain kernels
+    + rbvae_binarize_kl_bwd + rbvae_cast_pad + the unsplit fc instead of raising.  Same tolerances as
+    test_fused_step_parameter_ranges."""
+    test_fused_step_parameter_ranges("percep", 4, 1, T, 32, hw)
+    import sfv_amd as sfv
+    assert not sfv._lib.query("rbvae_lstm_pair_bwd_ok", T, 32, 4)
+
+
 @pytest.mark.parametrize("Ld,T,hw", [(50, 5, (32, 32)), (100, 8, (32, 32)), (25, 4, (16, 16))])
 def test_bf16_step_tracks_f32_step_at_other_latents(Ld, T, hw):
     """bf16 storage at the reference's other latent sizes (layer-by-layer LSTM kernels above 32, the K = 64 / 128 fc
