@@ -588,6 +588,45 @@ int rbvae_perturb_u8(const unsigned char* in, unsigned char* out, int N, int H, 
  * load_img's np.float32(x) / 255 then 2x - 1 (get_percep_embeddings.py:68-71, embedding_matching.py:335-338). */
 int rbvae_u8_to_input(const unsigned char* in, float* out, int N, int H, int W, int mode, void* stream);
 
+/* ---- linear probe evaluation (csrc/probe.hip) -----------------------------------------------------------
+ * scripts/evaluation/linear_projection_eval/linear_regression_eval.py:123-144: LinearRegression().fit on the train rows,
+ * predict on the test rows, r2_score / explained_variance_score (uniform average), mean_squared_error and
+ * mean_absolute_error, for an embedding of L <= 128 values and P targets per row, all in f64.
+ * Targets Y are resident on the device as u8 (RBVAE_PROBE_U8: [N][P] bytes, e.g. frames [N][H][W][3]; a value is
+ * ToTensor's (float)v / 255.0f widened to f64) or f32 (RBVAE_PROBE_F32: [N][P]).  Rows are addressed through int32 lists
+ * on the device, in any order; an index outside [0, N) contributes nothing.  row0 (in [0, N)) is the row every target is
+ * shifted by, which makes a target that is constant over the rows come out exactly.
+ *
+ * rbvae_probe_xty (:126, fit): C [M][P] = B^T (Y[rows] - Y[row0]) on the f64 matrix cores, B [n_rows][M] f64 the host's
+ * fit factor (2 <= M <= 129; for the fit M = L + 1: the minimum-norm least-squares operator's transpose and a column
+ * 1 / n_rows, so rows 0..L-1 of C are the coefficients and row L the shifted target mean).  Long row lists are split
+ * over rbvae_probe_xty_slabs K slabs, written to ws (rbvae_probe_xty_ws_bytes bytes, may be NULL when that is 0) and
+ * summed in slab order: two runs agree bit for bit. */
+#define RBVAE_PROBE_U8 0
+#define RBVAE_PROBE_F32 1
+int rbvae_probe_xty_slabs(int n_rows, int M, long P);
+size_t rbvae_probe_xty_ws_bytes(int n_rows, int M, long P);
+int rbvae_probe_xty(int y_dtype, const void* Y, long N, long P, const int* rows, int n_rows, int row0,
+                    const double* B, int M, double* C, double* ws, void* stream);
+/* linear_regression_eval.py:126 (model.intercept_): intercept [P] = (C[L] - sum_l mean_x[l] C[l]) + Y[row0], l ascending;
+ * C [L + 1][P] from rbvae_probe_xty, mean_x [L] the train mean of the embedding. */
+int rbvae_probe_intercept(int y_dtype, const void* Y, long N, long P, int row0, const double* C, const double* mean_x,
+                          int L, double* intercept, void* stream);
+/* linear_regression_eval.py:129-144 (predict and the sums behind the four metrics) over the rows of the list: with
+ * e = y - (intercept + sum_l Xr[r][l] C[l]) and d = y - Y[row0], sums [5][P] = sum e, sum e^2, sum |e|, sum d, sum d^2.
+ * Xr [n_rows][L] f64 holds the embedding of row rows[r] in row r. */
+int rbvae_probe_residual_sums(int y_dtype, const void* Y, long N, long P, const int* rows, int n_rows, int row0,
+                              const double* Xr, const double* C, const double* intercept, int L, double* sums,
+                              void* stream);
+/* linear_regression_eval.py:135-144: per target r2 [P] = 1 - sum e^2 / SStot, SStot = sum d^2 - (sum d)^2 / m, and
+ * evs [P] = 1 - (sum e^2 / m - (sum e / m)^2) / (SStot / m), a zero denominator scoring 1 with a zero numerator and 0
+ * otherwise (scikit-learn's force_finite); metrics [4] = (mean r2, mse, mae, mean evs), n_constant [1] = targets with
+ * SStot == 0.  m = the number of test rows behind sums; part: workspace of rbvae_probe_finish_parts(P) * 5 doubles.
+ * The reductions run in a fixed order (no atomics). */
+int rbvae_probe_finish_parts(long P);
+int rbvae_probe_finish(const double* sums, long P, int m, double* r2, double* evs, double* part, double* metrics,
+                       int* n_constant, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,3 +20,5 @@ from .frames import (contrastive_input, extract_embeddings, load_frames, perturb
                      resize_u8, sd_input, to_reference_dict, u8_to_input)
 from .robustness import (adjacent_hamming, most_common_codes, reference_draws, state_codes_under,  # noqa: F401
                          state_consistency_under)
+from . import probe  # noqa: F401  (probe.split_indices is the probe's train/test split; data.split_indices the trainer's)
+from .probe import ProbeResult, fit_factor, frame_embeddings, frame_probe, linear_probe  # noqa: F401
