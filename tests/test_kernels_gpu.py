@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import rbvae_oracle as O
+from _ends_cases import keyed_keep_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -181,21 +182,7 @@ def test_keyed_dropout_mask_is_its_definition(sfv):
     gemm(sfv, DT["bf16"][0], A.cuda(), Wt.cuda(), out, None, None, None, (M, 1, 1, 1, 1, 1, 1, 1, 1), K, Nout, 1,
          [1, 0, 0, 0, 0, 0], 1, drop_mode=1, drop_p=pdrop, scale=1.25, seed=seed)
     got_keep = (out.float().cpu() != 0).numpy()
-    u64, u32 = np.uint64, np.uint32
-    with np.errstate(over="ignore"):
-        x = u64(seed) * u64(0x9E3779B97F4A7C15) + u64(0xD6E8FEB86659FD93)
-        x ^= x >> u64(32); x *= u64(0xD6E8FEB86659FD93); x ^= x >> u64(32)
-        k0, k1 = u32(x & u64(0xFFFFFFFF)), u32(x >> u64(32))
-        thresh16 = u32(int(pdrop * 4294967296.0) >> 16)
-        rows, chunks = np.arange(M, dtype=np.uint64)[:, None], np.arange(0, Nout, 8, dtype=np.uint64)[None, :]
-        idx = rows * u64(Nout) + chunks                                # first element of every 8-element chunk
-        s = (idx & u64(0xFFFFFFFF)).astype(u32) + k0 + (idx >> u64(32)).astype(u32) * k1
-        s ^= s >> u32(16); s *= u32(0x7feb352d); s ^= s >> u32(15); s *= u32(0x846ca68b); s ^= s >> u32(16)
-        want_keep = np.empty((M, Nout), dtype=bool)
-        for e in range(0, 8, 2):
-            want_keep[:, e::8] = (s & u32(0xffff)) >= thresh16
-            want_keep[:, e + 1::8] = (s >> u32(16)) >= thresh16
-            s ^= s << u32(13); s ^= s >> u32(17); s ^= s << u32(5)
+    want_keep = keyed_keep_mask(M, Nout, seed, pdrop)                  # the host restatement (tests/_ends_cases.py)
     assert np.array_equal(got_keep, want_keep)
     assert 0.17 < 1.0 - want_keep.mean() < 0.23
 
