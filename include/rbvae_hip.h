@@ -71,7 +71,8 @@ int rbvae_binarize_kl_fwd_parts(const float* h, const float* U, float* y_soft, f
                                 float kl_p, float kl_eps, int kl_clamp, unsigned long long seed,
                                 const unsigned long long* seed_dev, void* stream);
 /* dh (+)= (g_z + kl_weight * gscale * dKL/dz) * y_soft*(1-y_soft)/tau (straight-through when hard).
- * g_z may be NULL; gscale_dev (device scalar, may be NULL = 1) multiplies kl_weight.
+ * g_z may be NULL; gscale_dev (device scalar, may be NULL = 1) multiplies kl_weight.  kl_p outside (0,1) is refused
+ * unless kl_weight == 0 (the KL term, and with it kl_p, is then not evaluated).
  * tau_dev (here and in every entry point that has it): when not NULL the kernel reads the temperature from that
  * device float instead of `tau`, so a captured HIP graph follows the reference's annealing schedule
  * (percep_RBVAE_train.py:424-437) without being re-captured. */
@@ -80,7 +81,7 @@ int rbvae_binarize_kl_bwd(const float* g_z, const float* y_soft, const float* z,
                           float kl_p, float kl_eps, int kl_clamp, void* stream);
 
 /* kl_binary_concrete as a free function (percep_RBVAE_train.py:52-76; simple
- * variant simple_RBVAE_train.py:45-68 = clamp 0, eps 1e-10). */
+ * variant simple_RBVAE_train.py:45-68 = clamp 0, eps 1e-10).  Both refuse p outside (0,1). */
 int rbvae_kl_fwd(const float* q_logits, float* out_mean, int rows, int L, float p, float eps, int clamp,
                  void* stream);
 int rbvae_kl_bwd(const float* q_logits, float* dq, int rows, int L, float p, float eps, int clamp,
@@ -114,7 +115,8 @@ int rbvae_contrast_term_bwd(const float* h0, const float* h1, int B, int T, int 
 int rbvae_contrast_term_nparts(int B, int T);
 int rbvae_contrast_term_fused(const float* h0, const float* h1, int B, int T, int L, float scale,
                               const float* gscale_dev, float* parts, float* dh0, float* dh1, void* stream);
-/* F.triplet_margin_loss(p=2, eps, swap) (triplet_RBVAE_train.py:82-96) on strided rows. */
+/* F.triplet_margin_loss(p=2, eps, swap) (triplet_RBVAE_train.py:82-96) on strided rows.  Backward: the negative
+ * pair's gradient goes to the smaller of d(a,n), d(p,n) and is split evenly when they are equal (torch.minimum). */
 int rbvae_triplet_fwd(const float* a, const float* p, const float* n, long sa, long sp, long sn, int rows, int L,
                       float margin, float eps, int swap, float* out_mean, void* stream);
 int rbvae_triplet_bwd(const float* a, const float* p, const float* n, long sa, long sp, long sn, int rows, int L,

@@ -369,10 +369,11 @@ __device__ __forceinline__ void triplet_row_bwd(const float* a, const float* p, 
     const float dap = sqrtf(row_sqdist(a, p, L, eps, lane));
     const float dan = sqrtf(row_sqdist(a, n, L, eps, lane));
     float dpn = 0.f;
-    bool use_pn = false;
+    bool use_pn = false, tie = false;
     if (swap) {
         dpn = sqrtf(row_sqdist(p, n, L, eps, lane));
         use_pn = dpn < dan;            // torch.minimum sends the gradient to the smaller one
+        tie = dpn == dan;              // ... and half to each at a tie (exact whenever a and p are bitwise equal views)
     }
     const float dneg = use_pn ? dpn : dan;
     const bool active = (margin + dap - dneg) > 0.f;
@@ -381,8 +382,12 @@ __device__ __forceinline__ void triplet_row_bwd(const float* a, const float* p, 
     for (int k = lane; k < L; k += 64) {
         const float gap = cap * (a[k] - p[k] + eps);           // d dap: +a, -p
         float ga = gap, gp = -gap, gn = 0.f;
-        if (use_pn) { const float g = cng * (p[k] - n[k] + eps); gp += g; gn -= g; }
-        else        { const float g = cng * (a[k] - n[k] + eps); ga += g; gn -= g; }
+        if (tie) {
+            const float g1 = 0.5f * (cng * (a[k] - n[k] + eps)), g2 = 0.5f * (cng * (p[k] - n[k] + eps));
+            ga += g1; gp += g2; gn = -g1 - g2;
+        }
+        else if (use_pn) { const float g = cng * (p[k] - n[k] + eps); gp += g; gn -= g; }
+        else             { const float g = cng * (a[k] - n[k] + eps); ga += g; gn -= g; }
         if (da) acc_store(da + k, ga, accumulate);
         if (dp) acc_store(dp + k, gp, accumulate);
         if (dn) acc_store(dn + k, gn, accumulate);
@@ -532,6 +537,8 @@ int rbvae_binarize_kl_bwd(const float* g_z, const float* y_soft, const float* z,
                           float kl_p, float kl_eps, int kl_clamp, void* stream) {
     RBVAE_CHECK_ARG(y_soft && z && dh, "binarize_kl_bwd: null pointer");
     RBVAE_CHECK_ARG(rows > 0 && L > 0 && (tau_dev || tau > 0.f), "binarize_kl_bwd: rows=%d L=%d tau=%g", rows, L, tau);
+    // log(1 - p) of p = 1 would put an infinite gradient into dh silently; weight 0 skips the KL term (and its p)
+    RBVAE_CHECK_ARG(kl_weight == 0.f || (kl_p > 0.f && kl_p < 1.f), "binarize_kl_bwd: p=%g outside (0,1)", kl_p);
     const int n = rows * L;
     hipLaunchKernelGGL(binarize_kl_bwd_k, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, g_z, y_soft, z,
                        dh, accumulate, n, rows, tau, tau_dev, kl_weight, gscale_dev, logf(kl_p), logf(1.0f - kl_p),
@@ -552,6 +559,7 @@ int rbvae_kl_fwd(const float* q, float* out, int rows, int L, float p, float eps
 int rbvae_kl_bwd(const float* q, float* dq, int rows, int L, float p, float eps, int clamp, float scale,
                  const float* gscale_dev, void* stream) {
     RBVAE_CHECK_ARG(q && dq && rows > 0 && L > 0, "kl_bwd: bad arguments");
+    RBVAE_CHECK_ARG(p > 0.f && p < 1.f, "kl_bwd: p=%g outside (0,1)", p);
     const int n = rows * L;
     hipLaunchKernelGGL(kl_bwd_k, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, q, dq, n, rows, logf(p),
                        logf(1.0f - p), eps, clamp, scale, gscale_dev);
