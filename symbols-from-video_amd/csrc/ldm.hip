@@ -294,6 +294,11 @@ static bool gn_tiled_ok(int dtype, int C, int ldx, int ldy, int groups) {
     const int tpr = C / V;
     return tpr <= 256 && 256 % tpr == 0 && ldx % V == 0 && ldy % V == 0;
 }
+// gn_apply_vec_k walks an unsigned index in steps of gridDim.x * 256 <= 16384 * 256 = 2^22: the last step from below
+// `rows * (C / V)` must not wrap, or the loop never ends.  Larger launches take gn_apply_k (64-bit index).
+static bool gn_vec_index_ok(int dtype, long rows, int C) {
+    return rows * (C / (dtype == RBVAE_F32 ? 4 : 8)) <= (1l << 32) - (1l << 22);
+}
 static int gn_rows_per_block(int dtype, int C) { return (256 / (C / (dtype == RBVAE_F32 ? 4 : 8))) * GN_PASSES; }
 
 size_t rbvae_groupnorm_ws_floats(int dtype, int N, int HW, int C, int groups) {
@@ -320,7 +325,7 @@ int rbvae_groupnorm_swish_ws(int dtype, const void* x, void* y, const float* gam
     float* rstd = stats_ws + (size_t)N * groups;
     const long rows = (long)N * HW;
     const bool tiled = gn_tiled_ok(dtype, C, ldx, ldy, groups) && ws_floats >= rbvae_groupnorm_ws_floats(dtype, N, HW, C, groups) &&
-                       rows * (C / (dtype == RBVAE_F32 ? 4 : 8)) < (1l << 32) &&
+                       gn_vec_index_ok(dtype, rows, C) &&
                        ((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0;
     if (tiled) {
         const int rb = gn_rows_per_block(dtype, C), nb = cdiv(HW, rb);
@@ -399,7 +404,7 @@ int rbvae_groupnorm_apply(int dtype, const void* x, void* y, const float* mean, 
     RBVAE_CHECK_ARG(groups > 0 && C % groups == 0 && ldx >= C && ldy >= C, "groupnorm_apply: C=%d groups=%d", C, groups);
     hipStream_t st = (hipStream_t)stream;
     const long rows = (long)N * HW;
-    const bool vec = gn_tiled_ok(dtype, C, ldx, ldy, groups) && rows * (C / (dtype == RBVAE_F32 ? 4 : 8)) < (1l << 32) &&
+    const bool vec = gn_tiled_ok(dtype, C, ldx, ldy, groups) && gn_vec_index_ok(dtype, rows, C) &&
                      ((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0;
     if (vec) {
         DISPATCH_T(dtype,

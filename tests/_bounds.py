@@ -162,13 +162,15 @@ def stats_height(cg):
     return cg + 28
 
 
-def tile_stats_bounds(n, cg, sum_abs, amax, m2):
+def tile_stats_bounds(n, cg, sum_abs, amax, m2, h=None):
     """Bounds of the kernel's f32 (mean, M2) of one tile and group: n values (pixels x cg), sum |x|, max |x| and the
     float64 M2 of the stored values.  mean: h u sum|x| / n.  M2: every partial mean is off by at most E = h u max|x|;
     the squared deviations of a partial from its OWN mean cancel that to first order, the merge terms
     n_a n_b / n (mean_a - mean_b)^2 do not: at most 2 E sqrt(W M2) per merge level (Cauchy-Schwarz, W <= n) over <= 4
-    levels, plus n E^2 per level and for the threads; the sums of the nonnegative terms (2 h + 4) u M2."""
-    h = stats_height(cg)
+    levels, plus n E^2 per level and for the threads; the sums of the nonnegative terms (2 h + 4) u M2.
+    h: the summation height of another kernel's statistics (default: conv_halo_k's stats_height(cg)); the arguments
+    may be tensors of one shape."""
+    h = stats_height(cg) if h is None else h
     E = h * U32 * amax
     bm = h * U32 * sum_abs / n + TINY
     bM2 = (2 * h + 4) * U32 * m2 + 8 * E * (n * m2) ** 0.5 + 5 * n * E * E + TINY
@@ -181,10 +183,10 @@ class Guarded:
     """A [guard + rows + guard][ld] buffer of sentinels; .view is the [rows][ld] interior handed to a kernel, .out its
     [rows][ncols] part (the declared elements)."""
 
-    def __init__(self, rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda"):
+    def __init__(self, rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda", row_align=16):
         ib, pat = SENTINEL[dtype]
         es = torch.empty((), dtype=dtype).element_size()
-        assert (ld * es) % 16 == 0, "rows of a guarded buffer keep 16-byte alignment"
+        assert (ld * es) % row_align == 0, "rows of a guarded buffer keep 16-byte alignment (row_align: a test of a misaligned ld)"
         assert ncols <= ld
         self.rows, self.ld, self.ncols, self.dtype, self.g = rows, ld, ncols, dtype, max(guard_rows, GUARD_ROWS)
         self.buf = torch.full((self.g + rows + self.g, ld), pat, dtype=ib, device=device).view(dtype)
@@ -210,14 +212,14 @@ class GuardedFlat(Guarded):
         assert self.view.data_ptr() % 16 == 0
 
 
-def guarded(rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda"):
-    return Guarded(rows, ld, ncols, dtype, guard_rows, device)
+def guarded(rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda", row_align=16):
+    return Guarded(rows, ld, ncols, dtype, guard_rows, device, row_align)
 
 
-def poisoned(t, ld, dtype, guard_rows=GUARD_ROWS, device="cuda"):
+def poisoned(t, ld, dtype, guard_rows=GUARD_ROWS, device="cuda", row_align=16):
     """Input operand t ([rows][ncols]) inside NaN guard rows and NaN padding columns ncols..ld."""
     t = t.reshape(t.shape[0], -1)
-    return Guarded(t.shape[0], ld, t.shape[1], dtype, guard_rows, device).fill(t.to(device))
+    return Guarded(t.shape[0], ld, t.shape[1], dtype, guard_rows, device, row_align).fill(t.to(device))
 
 
 def assert_guards(g, what=""):
