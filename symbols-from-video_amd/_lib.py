@@ -93,6 +93,7 @@ def query(name, *args):
 
 # ---- diagnostic probes (include/rbvae_dbg.h, librbvae_dbg.so): not part of the product ABI ----------------
 DBG_HEADER = os.path.join(os.path.dirname(HERE), "include", "rbvae_dbg.h")
+DBG_VARIANTS_HEADER = os.path.join(os.path.dirname(HERE), "include", "rbvae_dbg_variants.h")   # kernel-form selectors added later
 DBG_LIB_PATH = os.path.join(HERE, "librbvae_dbg.so")
 _dbg = None
 
@@ -103,7 +104,7 @@ def dbg_lib():
     if _dbg is None:
         lib()                                   # the probes resolve rbvae::fail (and the hooks their switches) from the main library
         l = ctypes.CDLL(DBG_LIB_PATH)
-        for n, (restype, a) in parse_header(DBG_HEADER).items():
+        for n, (restype, a) in {**parse_header(DBG_HEADER), **parse_header(DBG_VARIANTS_HEADER)}.items():
             fn = getattr(l, n, None)            # the stamp hooks exist in stamped builds of the main library only
             if fn is not None:
                 fn.restype = restype

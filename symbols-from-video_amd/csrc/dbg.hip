@@ -92,3 +92,12 @@ extern "C" int rbvae_dbg_lstm_unit_threads(int v) {
     rbvae::lstm_unit_threads = v;
     return old;
 }
+
+// which form of wgrad_gemm_k rbvae_wgrad_gemm (librbvae_hip) launches for its one-workgroup-per-CU bf16 problems: see
+// include/rbvae_dbg_variants.h; returns the previous value
+namespace rbvae { extern int wgrad_gemm_variant; }
+extern "C" int rbvae_dbg_wgrad_gemm_variant(int v) {
+    const int old = rbvae::wgrad_gemm_variant;
+    rbvae::wgrad_gemm_variant = v;
+    return old;
+}

@@ -337,11 +337,15 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     // wait until at most YOUNGER LDS reads are outstanding (in-order return): the guarded fragments landed
     auto landed = [&](auto younger_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
         constexpr int YOUNGER = decltype(younger_tag)::value;
-        static_assert((MT == 4 && (NTW == 1 || NTW == 2 || NTW == 4)) || (MT == 2 && NTW == 2) || (MT == 8 && NTW == 2), "operand list below");
+        static_assert((MT == 4 && (NTW == 1 || NTW == 2 || NTW == 4)) || (MT == 2 && (NTW == 1 || NTW == 2)) || (MT == 8 && NTW == 2), "operand list below");
         if constexpr (MT == 8)
             asm volatile("s_waitcnt lgkmcnt(%10)"
                          : "+v"(fa[0]), "+v"(fa[1 % MT]), "+v"(fa[2 % MT]), "+v"(fa[3 % MT]), "+v"(fa[4 % MT]), "+v"(fa[5 % MT]),
                            "+v"(fa[6 % MT]), "+v"(fa[7 % MT]), "+v"(fb[0]), "+v"(fb[1 % NTW])
+                         : "n"(YOUNGER));
+        else if constexpr (MT == 2 && NTW == 1)
+            asm volatile("s_waitcnt lgkmcnt(%3)"
+                         : "+v"(fa[0]), "+v"(fa[MT - 1]), "+v"(fb[0])
                          : "n"(YOUNGER));
         else if constexpr (MT == 2)
             asm volatile("s_waitcnt lgkmcnt(%4)"
@@ -603,6 +607,16 @@ static int launch_gg(const GgArgs& a, hipStream_t st) {
     return RBVAE_OK;
 }
 
+// The 64-row tile (one 4-wave workgroup per CU, 16 KB per K slice): ring depth and waves.  With three stages at most 32 KB
+// per CU is in flight, short of what keeps a CU's intake from L2 busy; GG_RING64 stages keep (GG_RING64 - 1) * 16 KB in
+// flight.  Build-time switches for same-GPU A/B runs (tools/ab_variants.sh); the measurements are in DESIGN.md section 5.
+#ifndef GG_RING64
+#define GG_RING64 6
+#endif
+#ifndef GG_WAVES64
+#define GG_WAVES64 4       // 8: two waves per SIMD, half the LDS-DMA pieces per wave
+#endif
+
 template <typename T>
 static int dispatch_gg(const GgArgs& a, hipStream_t st, int max_steps) {
     const long blocks = (long)cdiv(a.Nimg * a.TH * a.TW, GG_BM) * cdiv(a.Nout, a.Nout > 64 ? 128 : 64) * a.nclass;
@@ -616,7 +630,7 @@ static int dispatch_gg(const GgArgs& a, hipStream_t st, int max_steps) {
     // a deep-K product with few rows and <= 64 columns (the LDM encoder's conv_out: 16 384 rows, K = 4608, 8 columns): 64-row
     // tiles put a workgroup on every CU instead of on half of them (55 -> 30 us)
     if (a.Nout <= 64 && blocks <= 128 && max_steps >= 16 && sizeof(T) == 2 && !a.colsum_ws && !a.xcd_order)
-        return launch_gg<T, 2, 4, 3, 1, 64>(a, st);
+        return launch_gg<T, 2, GG_WAVES64, GG_RING64, 1, 64>(a, st);
     if (a.Nout <= 64) return ns == 1 ? launch_gg<T, 2, 4, 1>(a, st) : launch_gg<T, 2, 4, 2>(a, st);
     // deep-K problems with too few 128x128 tiles for the 256 CUs: narrower tiles (more workgroups, shorter steps)
     constexpr int small = 2;
@@ -626,7 +640,7 @@ static int dispatch_gg(const GgArgs& a, hipStream_t st, int max_steps) {
         // the 128-row tiles (their partial-sum rows are counted in 128-row tiles by the callers); xcd_order too.
         constexpr int sq = 1;
         if (sq && small >= 2 && blocks <= 64 && !a.colsum_ws && !a.xcd_order && sizeof(T) == 2)
-            return launch_gg<T, 2, 4, 3, 1, 64>(a, st);
+            return launch_gg<T, 2, GG_WAVES64, GG_RING64, 1, 64>(a, st);
         if (small >= 2 && blocks <= 64) return launch_gg<T, 1, 4, 3>(a, st);
         if (blocks <= 128) return launch_gg<T, 2, 4, 3>(a, st);
     }

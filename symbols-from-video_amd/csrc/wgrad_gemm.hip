@@ -10,7 +10,8 @@
 //
 // Tile: 128 x (64*NT) (co x ci) per 512-thread workgroup (8 waves, two per SIMD), 32 pixels per K
 // step, a 3-deep LDS-DMA ring with counted vmcnt waits; the K-slice's gather indices are read into
-// LDS once so no register load sits between the LDS-DMA issues.  grid = (co tiles, ci tiles, taps * ksplit); each
+// LDS once so no register load sits between the LDS-DMA issues.  Deep K loops in bf16 run a 12-wave form of the same kernel
+// (ROLES: waves 8-11 issue the LDS-DMA, waves 0-7 only multiply; see the kernel).  grid = (co tiles, ci tiles, taps * ksplit); each
 // K-slice writes its own f32 slab (summed later in a fixed order by
 // rbvae_permute_reduce, so gradients are bitwise reproducible -- no float atomics).
 #include "common.h"
@@ -83,9 +84,20 @@ template <int N> __device__ __forceinline__ void wg_wait_barrier() {
 // own L2 instead of from the Infinity Cache; otherwise the K-slice index is the fastest digit of the workgroup id.
 // BM = co per workgroup: 128, or 64 (f32 only) for layers of <= 64 output channels -- with the 128-row tile half of the
 // waves multiplied zero rows, and the exact-f32 kernel is bound by its matrix-core time (cfg 3, 64 channels: 45 % of the f32 step)
-template <typename T, int NT, int WG_NS, int BM = WG_BM>
-__global__ __launch_bounds__(512, WG_NS == 2 ? 2 : 1) void wgrad_gemm_k(const WgArgs p) {
+//
+// ROLES (bf16, one workgroup per CU): 12 waves.  Waves 0-7 are the 2 x 4 MFMA waves of the 8-wave form -- the same fragment
+// offsets, the same read_half / landed / mma_half sequence, the same slab stores, so every sum is formed in the same order and
+// the slabs are equal bit for bit -- but they issue no LDS-DMA and carry no vmcnt wait: one s_barrier per K step hands
+// them a landed stage and hands the stage they have in registers back.  Waves 8-11 (one per SIMD) issue every LDS-DMA piece
+// of a stage (piece i = producer + 4 j: i < 16 the Dy rows, then the gathered In rows) and wait for their own pieces with
+// counted vmcnt in front of that barrier.  In the 8-wave form a piece holds its issuing wave in the vector-memory issue while
+// an in-order wave feeds no MFMA: fill alone 0.41 us per K step, reads + MFMAs alone 0.48, both 0.74 (DESIGN.md section 5;
+// csrc/wgrad_row.hip has the same split).
+template <typename T, int NT, int WG_NS, int BM = WG_BM, bool ROLES = false>
+__global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_gemm_k(const WgArgs p) {
     constexpr int ES = sizeof(T);
+    constexpr int THREADS = ROLES ? 768 : 512;
+    static_assert(!ROLES || (ES == 2 && BM == WG_BM && WG_NS >= 3), "wave roles: the bf16 one-workgroup-per-CU ring only");
     constexpr int WG_BK = (ES == 2) ? 64 : 32;            // pixels per K step (one or two 32-pixel MFMA steps)
     constexpr int MT = BM / 32;
     static_assert(BM == 128 || (BM == 64 && ES == 4), "64-row tiles: the f32 path only (the bf16 fragment guards list MT = 4 operands)");
@@ -135,7 +147,7 @@ __global__ __launch_bounds__(512, WG_NS == 2 ? 2 : 1) void wgrad_gemm_k(const Wg
         const int padded = nsteps * WG_BK;
         // an index outside [0, in_rows) reads the zero row: a table that is stale, half-built or built for another shape
         // gives wrong sums (the parity tests see those), never an out-of-bounds access
-        for (int i = tid; i < padded; i += 512) {
+        for (int i = tid; i < padded; i += THREADS) {
             int r = i < npix ? (idx ? idx[i] : pbeg + i) : -1;
             if ((unsigned)r >= (unsigned)p.in_rows) r = -1;
             s_idx[i] = r;
@@ -147,6 +159,72 @@ __global__ __launch_bounds__(512, WG_NS == 2 ? 2 : 1) void wgrad_gemm_k(const Wg
     // staging roles.  One instruction = 1 KiB = (1024/RB) image rows.
     constexpr int A_LPR = RBA / 16, B_LPR = RBB / 16;     // lanes (chunks) per row
     constexpr int A_RPI = 64 / A_LPR, B_RPI = 64 / B_LPR; // rows per instruction
+    if constexpr (ROLES) {
+        if (w >= 8) {
+            // ================= producer waves: pw = w - 8 issues pieces pw + 4 j of every stage =================
+            constexpr int PA = A_TOT / 4, PB = B_TOT / 4, PP = PA + PB;      // pieces per producer wave and stage
+            static_assert(A_TOT % 4 == 0 && B_TOT % 4 == 0 && (WG_NS - 2) * PP <= 63, "piece split / vmcnt is a 6-bit counter");
+            const int pw = w - 8;
+            if (nsteps == 0) return;                       // no barrier follows for anyone (uniform)
+            int a_row[PA];
+            bool a_cval[PA];
+            const unsigned char* acur[PA];
+#pragma unroll
+            for (int j = 0; j < PA; ++j) {
+                const int r = (pw + 4 * j) * A_RPI + lane / A_LPR;
+                const int c = (lane % A_LPR) ^ tr_swz<RBA>(r);
+                a_row[j] = r;
+                a_cval[j] = co0 + c * (16 / ES) < p.Co;
+                acur[j] = p.Dy + ((size_t)(pbeg + r) * p.ldy + co0) * ES + c * 16;
+            }
+            int b_row[PB];
+            bool b_cval[PB];
+            const unsigned char* bbase[PB];
+#pragma unroll
+            for (int j = 0; j < PB; ++j) {
+                const int r = (pw + 4 * j) * B_RPI + lane / B_LPR;
+                const int c = (lane % B_LPR) ^ tr_swz<RBB>(r);
+                b_row[j] = r;
+                b_cval[j] = ci0 + c * (16 / ES) < p.Ci;
+                bbase[j] = p.In + (size_t)ci0 * ES + c * 16;
+            }
+            const size_t a_stride = (size_t)WG_BK * p.ldy * ES, ldi_b = (size_t)p.ldi * ES;
+            int pstep = 0, pbuf = 0;
+            auto stage = [&]() {
+                unsigned char* la = smem + pbuf * STAGE + pw * 1024;
+                const int base = pstep * WG_BK;
+#pragma unroll
+                for (int j = 0; j < PA; ++j) {
+                    const bool v = a_cval[j] && base + a_row[j] < npix;
+                    glds16w(v ? acur[j] : p.zero, la + j * 4096);
+                    acur[j] += a_stride;
+                }
+                unsigned char* lb = la + A_BYTES;
+                int src[PB];                               // all of a stage's indices first: no LDS wait between the pieces
+#pragma unroll
+                for (int j = 0; j < PB; ++j) src[j] = s_idx[base + b_row[j]];
+#pragma unroll
+                for (int j = 0; j < PB; ++j) {
+                    const bool v = b_cval[j] && src[j] >= 0;
+                    glds16w(v ? bbase[j] + (size_t)src[j] * ldi_b : p.zero, lb + j * 4096);
+                }
+                ++pstep;
+                pbuf = (pbuf + 1 == WG_NS) ? 0 : pbuf + 1;
+            };
+            // the 8-wave form's schedule: stage s + 1 landed (WG_NS - 2 younger ones may stay in flight) -> barrier -> the
+            // MFMA waves hold stage s in registers, its ring slot takes stage s + WG_NS
+#pragma unroll
+            for (int i = 0; i < WG_NS - 1; ++i)
+                if (i < nsteps) stage();
+            if (nsteps >= WG_NS - 1) wg_wait_barrier<(WG_NS - 2) * PP>(); else wg_wait_barrier<0>();
+            if (WG_NS - 1 < nsteps) stage();
+            for (int s = 0; s + 1 < nsteps; ++s) {
+                if (nsteps - s - 2 >= WG_NS - 2) wg_wait_barrier<(WG_NS - 2) * PP>(); else wg_wait_barrier<0>();
+                if (s + WG_NS < nsteps) stage();
+            }
+            return;
+        }
+    }
     int a_row[A_INSTR], a_coff[A_INSTR];
     bool a_cval[A_INSTR];
 #pragma unroll
@@ -305,11 +383,15 @@ __global__ __launch_bounds__(512, WG_NS == 2 ? 2 : 1) void wgrad_gemm_k(const Wg
         using Younger = std::integral_constant<int, RPH>;
         using None = std::integral_constant<int, 0>;
         if (nsteps > 0) {
+            if constexpr (ROLES) {
+                asm volatile("s_barrier" ::: "memory");        // stage 0 landed (the producer waves waited for it)
+            } else {
 #pragma unroll
-            for (int i = 0; i < WG_NS - 1; ++i)
-                if (i < nsteps) stage_next();
-            wait_stage(nsteps >= WG_NS - 1);
-            if (WG_NS - 1 < nsteps) stage_next();
+                for (int i = 0; i < WG_NS - 1; ++i)
+                    if (i < nsteps) stage_next();
+                wait_stage(nsteps >= WG_NS - 1);
+                if (WG_NS - 1 < nsteps) stage_next();
+            }
             int cbuf = 0;
             read_half(lds0, 0, a0l, a0h, b0l, b0h);
             for (int s = 0; s < nsteps; ++s) {
@@ -323,8 +405,13 @@ __global__ __launch_bounds__(512, WG_NS == 2 ? 2 : 1) void wgrad_gemm_k(const Wg
                 // would read a fragment before its wait.
                 landed(None{}, a1l, a1h, b1l, b1h, fa, fb);
                 if (s + 1 < nsteps) {
-                    wait_stage(nsteps - s - 2 >= WG_NS - 2);
-                    if (s + WG_NS < nsteps) stage_next();
+                    if constexpr (ROLES) {
+                        // no LDS read of this wave is in flight (landed(None) above): stage s is in registers
+                        asm volatile("s_barrier" ::: "memory");
+                    } else {
+                        wait_stage(nsteps - s - 2 >= WG_NS - 2);
+                        if (s + WG_NS < nsteps) stage_next();
+                    }
                     read_half(lds0 + cbuf * STAGE, 0, a0l, a0h, b0l, b0h);
                 }
                 mma_half(fa, fb);
@@ -393,7 +480,7 @@ __global__ void conv_gather_index_k(int* __restrict__ idx, int Nimg, int IH, int
     idx[i] = (ih >= 0 && ih < IH && iw >= 0 && iw < IW) ? (n * IH + ih) * IW + iw : -1;
 }
 
-template <typename T, int NT, int NS, int BM = WG_BM>
+template <typename T, int NT, int NS, int BM = WG_BM, bool ROLES = false>
 static int launch_wg_ns(const WgArgs& a, hipStream_t st) {
     constexpr int ES = sizeof(T);
     constexpr int BK = (ES == 2) ? 64 : 32;
@@ -401,16 +488,25 @@ static int launch_wg_ns(const WgArgs& a, hipStream_t st) {
     const size_t lds = ring + (size_t)a.Pper * sizeof(int);            // + this launch's index table
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_gemm_k<T, NT, NS, BM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)wgrad_gemm_k<T, NT, NS, BM, ROLES>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(ring + WG_MAXP * sizeof(int)));
         attr_set = true;
     }
     long blocks = (long)cdiv(a.Co, BM) * cdiv(a.Ci, 64 * NT) * a.taps * a.ksplit;
     if (a.xcd_order) blocks = 8 * ((blocks + 7) / 8);
-    hipLaunchKernelGGL((wgrad_gemm_k<T, NT, NS, BM>), dim3((unsigned)blocks), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((wgrad_gemm_k<T, NT, NS, BM, ROLES>), dim3((unsigned)blocks), dim3(ROLES ? 768 : 512), lds, st, a);
     RBVAE_CHECK_LAUNCH("wgrad_gemm");
     return RBVAE_OK;
 }
+
+// Which form the one-workgroup-per-CU bf16 launches take.  Written only by librbvae_dbg's rbvae_dbg_wgrad_gemm_variant
+// (bit-identity tests, A/B timing): 0 the product dispatch, 1 the 8-wave form, 2 the 12-wave form with wave roles, 3 the
+// 12-wave form with a ring of four stages where the index table leaves room.
+int wgrad_gemm_variant = 0;
+// Product dispatch: wave roles for K loops of at least this many steps (the 4096-pixel layers at the bench shape: 22 steps,
+// 24.0 / 31.0 -> 21.0 / 24.8 us per launch in the step); the 8-9-step launches (conv1 / last deconv weight gradients, NT = 1)
+// and the 32-workgroup fc launch ran no faster or slower with them.
+constexpr int WG_ROLES_MIN_STEPS = 16;
 
 template <typename T, int NT, int BM = WG_BM>
 static int launch_wg(const WgArgs& a, hipStream_t st) {
@@ -423,6 +519,11 @@ static int launch_wg(const WgArgs& a, hipStream_t st) {
     const bool two = force ? force == 2 : (blocks > 256 && 2 * lds2 <= 160 * 1024);
     if constexpr (ES == 2) {
         if (force == 4 && a.Pper <= 2560) return launch_wg_ns<T, NT, 4>(a, st);
+        const int v = wgrad_gemm_variant;
+        if (!two && (v == 0 ? a.Pper >= WG_ROLES_MIN_STEPS * BK : v >= 2)) {
+            if (v == 3 && a.Pper <= 2560) return launch_wg_ns<T, NT, 4, BM, true>(a, st);
+            return launch_wg_ns<T, NT, 3, BM, true>(a, st);
+        }
     }
     return two ? launch_wg_ns<T, NT, 2, BM>(a, st) : launch_wg_ns<T, NT, 3, BM>(a, st);
 }
