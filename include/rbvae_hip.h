@@ -564,6 +564,46 @@ int rbvae_deconv3x3s2_halo(int dtype, const void* A, const void* W, void* Out, c
                            int ldo, int relu, int drop_mode, float drop_p, float scale, unsigned long long seed,
                            const unsigned long long* seed_dev, float* colsum_ws, void* stream);
 
+/* ---- LDM / Stable-Diffusion VAE decoder: latents -> frames (csrc/upconv.hip) --------------------------------
+ * The decoder (ldm/modules/diffusionmodules/model.py:462-568 behind AutoencoderKL.decode, ldm/models/autoencoder.py:330-333,
+ * and decode_first_stage, ldm/models/diffusion/ddpm.py:706-713) is built from the encoder's blocks and runs on the entry
+ * points above; these are the pieces it adds.
+ *
+ * Upsample (model.py:42-57: F.interpolate(x, scale_factor=2.0, mode="nearest") then Conv2d(c, c, 3, 1, 1)) as four 2x2
+ * convolutions of the LOW-resolution input, one per output parity class cls = 2p + q (p, q = output row, column & 1), tap =
+ * 2th + tw:
+ *   Out[n][2r+p][2c+q][co] = bias[co] + addend + sum_{th,tw,ci} A[n][r-1+p+th][c-1+q+tw][ci] * Wf[co][4 cls + tap][ci]
+ *   Wf[co][4 cls + tap][ci] = sum_{kh in R(p,th)} sum_{kw in R(q,tw)} w[co][ci][kh][kw],
+ *   R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2};   A is zero outside the IH x IW map.
+ * rbvae_upconv_fold: w f32 [Co][Ci][3][3] (the torch layout) -> Wf [Co][16][Kc] of the storage type: each entry the f32
+ * sum over kh ascending and, inside it, kw ascending, starting from +0, rounded once; channels Ci..Kc zero.
+ * rbvae_upconv3x3_halo: A [Nimg*IH*IW][lda], Out / addend [Nimg*2IH*2IW][ldo] NHWC rows of the storage type, zero_page >= 128
+ * zero bytes (what padding lanes read), every pointer 16-byte aligned; a workgroup
+ * owns a 16 x 16 block of low-resolution pixels x 128 output channels x one class, stages the block's 18 x 18 patch in LDS
+ * once per 128-byte channel slice and takes the four folded tap tiles through a four-slot LDS-DMA ring.  The same sums
+ * come from rbvae_gather_gemm with the four-class descriptor (sa = 1, so = 2, class (p, q): oh0 = p, ow0 = q, taps
+ * (4 cls + tap, p - 1 + th, q - 1 + tw)).  rbvae_upconv3x3_halo_ok: 1 when the shape is covered (IH >= 5, IW >= 5,
+ * Kc % 64 (bf16) / 32 (f32) == 0, Nout % 128 == 0, fewer than 2^30 output rows); a shape it refuses makes
+ * rbvae_upconv3x3_halo return RBVAE_E_UNSUPPORTED without a launch.
+ * rbvae_nearest2x_rows: the upsampled rows themselves, out[(n, 2r+p, 2c+q)][0..C) = in[(n, r, c)][0..C) (model.py:52; the
+ * as-written baseline in front of a 3x3 convolution), C * sizeof(T) a multiple of 16. */
+int rbvae_upconv_fold(int dtype, const float* w, void* out, int Co, int Ci, int Kc, void* stream);
+int rbvae_upconv3x3_halo_ok(int dtype, int Nimg, int IH, int IW, int Kc, int Nout);
+int rbvae_upconv3x3_halo(int dtype, const void* A, const void* Wf, void* Out, const float* bias, const void* addend,
+                         const void* zero_page, int Nimg, int IH, int IW, int Kc, int Nout, int lda, int ldo, void* stream);
+int rbvae_nearest2x_rows(int dtype, const void* in, void* out, int Nimg, int IH, int IW, int C, int ldi, int ldo,
+                         void* stream);
+/* decode_first_stage's z = 1. / scale_factor * z (ddpm.py:713) into the NHWC rows post_quant_conv (autoencoder.py:303,331)
+ * reads as a one-tap rbvae_gather_gemm: z f32 [N][Z][HW] -> rows [N*HW][Kpad] of the storage type,
+ * z * (float)(1.0 / scale_factor) in f32 (the double quotient rounded to f32 as torch rounds the scalar, then one f32
+ * product), then the storage type; columns Z..Kpad zero. */
+int rbvae_latent_rows(int dtype, const float* z, void* rows, int N, int Z, int HW, int Kpad, double scale_factor,
+                      void* stream);
+/* conv_out's rows [N*HW][ld] (3 used columns; model.py:565) -> img f32 [N][3][HW] (the decoder's output, may be NULL) and /
+ * or u8 [N][HW][3] (may be NULL): trunc(255 * clamp((x + 1) / 2, 0, 1)) in f32, operation by operation as
+ * scripts/pretrained_model_experiments/ldm_embedding_interpol.py:179-182 -- the u8 NHWC frames of csrc/frames.hip. */
+int rbvae_decoded_to_image(int dtype, const void* rows, int ld, float* img, unsigned char* u8, int N, int HW, void* stream);
+
 /* ---- raw frames in (csrc/frames.hip) ---------------------------------------------------------------
  * Frames are u8 RGB, NHWC (3 channels, contiguous), a batch of N (<= 65535) images.
  * rbvae_resample_u8: one separable pass of Pillow's 8-bit resampler (Image.resize as called by

@@ -12,7 +12,7 @@ from .losses import (contrast_loss, contrast_term, kl_binary_concrete, kl_binary
                      l1_loss, recon_loss, triplet_loss, triplet_term)
 from .data import (DeviceStatePairDataset, assign_label, build_pairs, consistency_from_codes,  # noqa: F401
                    split_indices, state_consistency)
-from .ldm import LDMEncoder  # noqa: F401
+from .ldm import LDMDecoder, LDMEncoder, interpolate_embeddings  # noqa: F401
 from .model import Seq2SeqBinaryVAE, binary_concrete_logits  # noqa: F401
 from .trainer import FusedTrainer, noise_key  # noqa: F401
 from .compose import OnTheFlyLatentTrainer  # noqa: F401

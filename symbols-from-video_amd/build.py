@@ -58,13 +58,14 @@ ISA_CHECKED = {
     "wgrad_halo.hip": ("_ZN5rbvae12wgrad_halo_k", ("ds_read_b64_tr_b16",)),
     "wgrad_row.hip": ("_ZN5rbvae11wgrad_row_k", ("ds_read_b64_tr_b16",)),
     "conv_s2.hip": ("_ZN5rbvae9conv_s2_k", ("ds_read_b128",)),
+    "upconv.hip": ("_ZN5rbvae13upconv_halo_k", ("ds_read_b128",)),
     "conv_first.hip": (("_ZN5rbvae13wgrad_first_k", "_ZN5rbvae18wgrad_first_wide_k"), ("ds_read_b64_tr_b16",)),
 }
 
 
 # kernels with register-destination loads issued as inline asm (counted vmcnt waits): the load opcode
 ASM_VMEM_LOADS = {"conv_halo.hip": "global_load_dwordx4", "deconv_halo.hip": "global_load_dwordx4",
-                  "conv_halo_ws.hip": "buffer_load_dwordx4"}
+                  "conv_halo_ws.hip": "buffer_load_dwordx4", "upconv.hip": "global_load_dwordx4"}
 
 
 def _check_asm_reads(src):
