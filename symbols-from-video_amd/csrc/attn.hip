@@ -22,15 +22,10 @@
 //   * the output accumulators are only rescaled when a row maximum moved (wave-uniform test).
 // ~72 KB of LDS per workgroup at C = 512.  Measured (MI355X, bf16): 4 x 4096 tokens (512x512 frames) 387 us = 355 TFLOP/s,
 // the three-launch form 393 us; 8 x 1024 tokens (256x256) 104 us against 329 us.
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 constexpr int AT_BK = 32, AT_PAD = 8;
 
@@ -74,10 +69,8 @@ __global__ __launch_bounds__(4 * AT_BQ, AT_BQ == 64 ? 2 : 1) void attn_flash_k(c
             // all of a wave's 8 rows are in flight together.  (Through registers the loop became a load-wait-store
             // chain of four dependent L2 round trips per tile: 4.3 us per 32-key tile at 4096 tokens.)
             for (int r = w; r < AT_BK; r += AT_WAVES) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(K + (img + k0 + r) * ldk + 8 * l),
-                                                 (__attribute__((address_space(3))) void*)(sK + r * LD), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(V + (img + k0 + r) * ldv + 8 * l),
-                                                 (__attribute__((address_space(3))) void*)(sV + r * LD), 16, 0, 0);
+                glds16(K + (img + k0 + r) * ldk + 8 * l, sK + r * LD);
+                glds16(V + (img + k0 + r) * ldv + 8 * l, sV + r * LD);
             }
             // every wave's own transfers have landed before it arrives at the barrier (the compiler only guards a
             // wave's OWN later LDS reads)
@@ -172,10 +165,6 @@ __global__ __launch_bounds__(4 * AT_BQ, AT_BQ == 64 ? 2 : 1) void attn_flash_k(c
 // (454 TFLOP/s), 8 x 1024 tokens 103 -> 79 us.  What is left is the single MFMA wave per SIMD (248 registers: Q fragments +
 // output accumulators): it exposes its own LDS latency -- a 128-query tile on eight MFMA waves that also issue the LDS-DMA
 // needs every fragment read as inline asm (the compiler drains the LDS-DMA in front of its own LDS reads).
-template <int N> __device__ __forceinline__ void at_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void at_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __global__ __launch_bounds__(384, 1) void attn_flash_db_k(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, bf16_t* __restrict__ O, int hw, int ldq,
@@ -202,8 +191,7 @@ __global__ __launch_bounds__(384, 1) void attn_flash_db_k(const bf16_t* __restri
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int r = pw + 2 * i;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + r * ld),
-                                                 (__attribute__((address_space(3))) void*)(dst + r * LD), 16, 0, 0);
+                glds16(src + r * ld, dst + r * LD);
             }
         };
         issue(0);
@@ -211,9 +199,9 @@ __global__ __launch_bounds__(384, 1) void attn_flash_db_k(const bf16_t* __restri
         if (nh > 2) issue(2);
         for (int h = 0; h < nh; ++h) {
             // own pieces of half-step h landed (h + 1, h + 2 may be in flight) -> barrier -> refill the buffer of half-step h - 1
-            if (h + 2 < nh) at_wait_barrier<32>();
-            else if (h + 1 < nh) at_wait_barrier<16>();
-            else at_wait_barrier<0>();
+            if (h + 2 < nh) wait_vm_barrier<32>();
+            else if (h + 1 < nh) wait_vm_barrier<16>();
+            else wait_vm_barrier<0>();
             if (h + 3 < nh) issue(h + 3);
         }
         return;
@@ -239,7 +227,7 @@ __global__ __launch_bounds__(384, 1) void attn_flash_db_k(const bf16_t* __restri
     for (int t = 0; t < nt; ++t) {
         const bf16_t* cK = sK + (t & 1) * TILE;
         const bf16_t* cV = sV + (t & 1) * TILE;
-        at_lds_barrier();                                     // half-step 2t: K_t landed; everyone is past P V of tile t - 1
+        lds_barrier();                                     // half-step 2t: K_t landed; everyone is past P V of tile t - 1
         f32x4_t sc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int s = 0; s < D / 32; ++s) {
@@ -275,7 +263,7 @@ __global__ __launch_bounds__(384, 1) void attn_flash_db_k(const bf16_t* __restri
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[c][r] *= alpha[r];
         }
-        at_lds_barrier();                                     // half-step 2t + 1: V_t landed; everyone is past the scores of tile t
+        lds_barrier();                                     // half-step 2t + 1: V_t landed; everyone is past the scores of tile t
         const bf16x8_t pa = *(const bf16x8_t*)(myP + m * PLD + 8 * g);
         const int i4 = m >> 2, p4 = m & 3;
         const bf16_t* vlo = cV + (8 * g + i4) * LD + 4 * p4;

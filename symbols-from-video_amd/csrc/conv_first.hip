@@ -13,7 +13,7 @@
 //
 // They replace rbvae_im2col(_frames) + the single-slice rbvae_gather_gemm (same arithmetic per element: one 64-deep MFMA
 // chain; same dropout key and chunk indices; stored values are bit-identical).
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 
 #ifndef CF_DBG      // timing experiments only: 1 no output stores, 2 no col stores, 3 stop after the staging, 4 no patch loads, 5 no gate reads
@@ -22,21 +22,9 @@
 
 namespace rbvae {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-struct CfFrameMap { int d1, d2; long s0, s1, s2; };
-__device__ __forceinline__ long cf_frame_off(const CfFrameMap& f, unsigned n) {
-    if (f.d1 == 0) return (long)n * f.s2;
-    const unsigned a = n / (unsigned)f.d1, r = n - a * (unsigned)f.d1;
-    const unsigned b = r / (unsigned)f.d2, c = r - b * (unsigned)f.d2;
-    return (long)a * f.s0 + (long)b * f.s1 + (long)c * f.s2;
-}
-
 struct CfArgs {
-    const float* x;              // MODE 0: frames [Cin][IH][IW] f32 at cf_frame_off(fm, n); MODE 1: [N][IH][IW][Cin] f32
-    CfFrameMap fm;
+    const float* x;              // MODE 0: frames [Cin][IH][IW] f32 at frame_off_u32(fm, n); MODE 1: [N][IH][IW][Cin] f32
+    FrameMap fm;
     const unsigned char* W;      // [Nout][64] bf16 (im2col column order, zero padded)
     const float* bias;           // [Nout] or null (MODE 0)
     const unsigned char* zero;   // >= 16 zero bytes
@@ -67,23 +55,6 @@ template <int CIN, int MODE> struct CfOff {
     }
 };
 
-__device__ __forceinline__ void cf_glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-template <int CTRL> __device__ __forceinline__ float cf_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// sum over the 16 lanes of a DPP row (lane & 15), every lane gets the total
-__device__ __forceinline__ float cf_row_sum(float v) {
-    v += cf_dpp<0x128>(v);     // row_ror:8
-    v += cf_dpp<0x124>(v);     // row_ror:4
-    v += cf_dpp<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += cf_dpp<0xB1>(v);      // quad_perm [1,0,3,2]
-    return v;
-}
-__device__ __forceinline__ bool cf_bf16_pos(unsigned v16) { return (v16 - 1u) < 0x7f80u; }    // 0 < v <= +inf, NaN excluded
-
 // NQ = 64-channel quads of the tile: 4 (Nout <= 256: wave = 64 pixels x one quad) or 1 (Nout <= 64, the cfg 3 widths: wave =
 // 16 pixels x the one quad -- with the 256-wide tile three of four waves multiplied and staged zero weights and sat out the
 // epilogue; 8 KB of weights instead of 32 and 16 accumulators per lane let four workgroups share a CU)
@@ -110,7 +81,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
             const int ct = r >> 4, j = r & 15;
             const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
             const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + ((schunk ^ ((r >> 1) & 7)) * 16) : p.zero;
-            cf_glds16(src, s_b + (size_t)(r - srow) * 128);
+            glds16(src, s_b + (size_t)(r - srow) * 128);
         }
     }
     // bias and dropout key early: their latency hides behind the patch loads, and the epilogue's stores are never waited on
@@ -131,7 +102,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
     if constexpr (MODE == 0) {
         // s_patch row c*17 + r, column 0 = the halo column 2*ow0 - 1, columns 1 .. 32 = the 128-byte run from 2*ow0: one
         // instruction loads two rows (32 lanes each)
-        const float* xf = p.x + cf_frame_off(p.fm, n);
+        const float* xf = p.x + frame_off_u32(p.fm, n);
         constexpr int R = CIN * CF_PA, PAIRS = (R + 1) / 2, PIT = (PAIRS + 7) / 8;
         float pv[PIT], hv = 0.f;
 #pragma unroll
@@ -310,7 +281,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
             float* red = s_patch;                              // [pixel groups][64 NQ]; the patch is dead since the second barrier
             constexpr int RW = 64 * NQ, NGRP = NQ == 4 ? 2 : 8;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) csum[e] = cf_row_sum(csum[e]);
+            for (int e = 0; e < 16; ++e) csum[e] = row_sum(csum[e]);
             if (fi == 0) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) red[wm * RW + col + e] = csum[e];
@@ -326,7 +297,6 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
     }
 }
 
-
 // ---- weight gradient of the two 3/4-channel ends WITHOUT the im2col rows in HBM -------------------------------------------
 //   dW[ks][co][k] = sum_{p in K-slice ks} dY[p][co] * col(x)[p][k],   k = (kh*3+kw)*CIN + ci  (zero padded to 64)
 // MODE 0: the first Conv2d's weight (x = the input frames; dY = the gradient at its output); MODE 1: the last
@@ -337,15 +307,12 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
 // LDS (pixel-major 128-byte rows: the reduction index is the row), the [128 px][64 co] tile of dY arrives by LDS-DMA one
 // block ahead, fragments by ds_read_b64_tr_b16.  Tile 64 co x 64 k, 2 sub-tiles per wave; two workgroups per CU.
 struct WfArgs {
-    const float* x; CfFrameMap fm;
+    const float* x; FrameMap fm;
     const unsigned char* dY;     // [N*OH*OW][ldy] bf16
     const unsigned char* zero;
     float* dW;                   // [ksplit][Nout][64] f32
     int N, Cin, IH, IW, OH, OW, Nout, ldy, ksplit, per, nblk;
 };
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-__device__ __forceinline__ int wf_swz(int row) { return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1; }   // tr_swz<128> (wgrad_gemm.hip)
-__device__ __forceinline__ void wf_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_first_k(const WfArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char s_col[128 * 128];       // im2col rows [px][64 k], tr-swizzled
@@ -375,7 +342,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
         const int n = b / (unsigned)ta_n;
         const int ih0 = 2 * tai * CF_TA - 1, iw0 = 2 * tbi * CF_TB - 1;
         if constexpr (MODE == 0) {
-            const float* xf = p.x + cf_frame_off(p.fm, n);
+            const float* xf = p.x + frame_off_u32(p.fm, n);
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int row = 2 * (w + 8 * it) + (lane >> 5);
@@ -431,8 +398,8 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
             const int oh = tai * CF_TA + (r >> 4), ow = tbi * CF_TB + (r & 15);
             const bool v = oh < p.OH && ow < p.OW;
             const unsigned char* src = p.dY + ((size_t)(n * p.OH + oh) * p.OW + ow) * ((size_t)p.ldy * 2) + co0 * 2 +
-                                       (((lane & 7) ^ wf_swz(r)) * 16);
-            cf_glds16(v ? src : p.zero, s_dy[buf] + (2 * w + i2) * 1024);
+                                       (((lane & 7) ^ tr_swz<128>(r)) * 16);
+            glds16(v ? src : p.zero, s_dy[buf] + (2 * w + i2) * 1024);
         }
     };
 
@@ -441,9 +408,9 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
     const int q = fi >> 2, pp = fi & 3;
     const int mt = w & 3, nt0 = (w >> 2) * 2;
     const int row0 = 8 * fg + q;
-    const int offA = row0 * 128 + (((mt * 2 + (pp >> 1)) ^ wf_swz(row0)) * 16) + (pp & 1) * 8;
-    const int offB0 = row0 * 128 + (((nt0 * 2 + (pp >> 1)) ^ wf_swz(row0)) * 16) + (pp & 1) * 8;
-    const int offB1 = row0 * 128 + ((((nt0 + 1) * 2 + (pp >> 1)) ^ wf_swz(row0)) * 16) + (pp & 1) * 8;
+    const int offA = row0 * 128 + (((mt * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
+    const int offB0 = row0 * 128 + (((nt0 * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
+    const int offB1 = row0 * 128 + ((((nt0 + 1) * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
     f32x4_t acc0 = f32x4_t{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
     const unsigned l_col = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)s_col;
     const unsigned l_dy = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)s_dy[0];
@@ -460,7 +427,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
         asm volatile("" : "+v"(hv));
         store_patch();
         if (blk + 1 < blk1) load_patch(blk + 1);                         // lands under this block's work
-        wf_lds_barrier();
+        lds_barrier();
         // im2col rows: 128 rows x 8 chunks of 8 columns
 #pragma unroll
         for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
@@ -477,9 +444,9 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
             u32x4_t pk;
             pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
             pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
-            *(u32x4_t*)(s_col + r * 128 + ((c ^ wf_swz(r)) * 16)) = pk;
+            *(u32x4_t*)(s_col + r * 128 + ((c ^ tr_swz<128>(r)) * 16)) = pk;
         }
-        wf_lds_barrier();
+        lds_barrier();
         // the next block's dY tile: issued HERE, behind the last compiler-visible LDS access of the block (in front of one
         // the compiler drains every LDS-DMA); the fragment reads below are asm
         if (blk + 1 < blk1) stage_dy(blk + 1, buf ^ 1);
@@ -501,7 +468,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0, fa, acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1, fa, acc1, 0, 0, 0);
         }
-        wf_lds_barrier();                                                // everyone is done with s_patch / s_col / s_dy[buf]
+        lds_barrier();                                                // everyone is done with s_patch / s_col / s_dy[buf]
         buf ^= 1;
     }
     // D[row = k 4 fg + r][col = co fi]: a lane owns 4 consecutive k of one co
@@ -547,7 +514,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
         const int n = b / (unsigned)ta_n;
         const int ih0 = 2 * tai * CF_TA - 1, iw0 = 2 * tbi * CF_TB - 1;
         if constexpr (MODE == 0) {
-            const float* xf = p.x + cf_frame_off(p.fm, n);
+            const float* xf = p.x + frame_off_u32(p.fm, n);
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int row = 2 * (w + 8 * it) + (lane >> 5);
@@ -584,7 +551,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
             const int oh = tai * CF_TA + (r >> 4), ow = tbi * CF_TB + (r & 15);
             const bool v = oh < p.OH && ow < p.OW;
             const unsigned char* src = p.dY + ((size_t)(n * p.OH + oh) * p.OW + ow) * ((size_t)p.ldy * 2) + co0 * 2 +
-                                       (((lane & 7) ^ wf_swz(r)) * 16);
+                                       (((lane & 7) ^ tr_swz<128>(r)) * 16);
 #pragma unroll
             for (int q = 0; q < 4; ++q) st.dy[q * 2 + i2] = *(const u32x4_t*)(v ? src + q * 128 : p.zero);
         }
@@ -617,9 +584,9 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
     const int qq = fi >> 2, pp = fi & 3;
     const int mt = w & 3, nt0 = (w >> 2) * 2;
     const int row0 = 8 * fg + qq;
-    const int offA = row0 * 128 + (((mt * 2 + (pp >> 1)) ^ wf_swz(row0)) * 16) + (pp & 1) * 8;
-    const int offB0 = row0 * 128 + (((nt0 * 2 + (pp >> 1)) ^ wf_swz(row0)) * 16) + (pp & 1) * 8;
-    const int offB1 = row0 * 128 + ((((nt0 + 1) * 2 + (pp >> 1)) ^ wf_swz(row0)) * 16) + (pp & 1) * 8;
+    const int offA = row0 * 128 + (((mt * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
+    const int offB0 = row0 * 128 + (((nt0 * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
+    const int offB1 = row0 * 128 + ((((nt0 + 1) * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
     f32x4_t acc[4][2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { acc[q][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[q][1] = acc[q][0]; }
@@ -629,7 +596,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
     auto block = [&](int blk, Stage& st, int buf) {
         store_block(st, buf);
         load_block(blk + 2, st);
-        wf_lds_barrier();
+        lds_barrier();
         // im2col rows: 128 rows x 8 chunks of 8 columns
 #pragma unroll
         for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
@@ -646,9 +613,9 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
             u32x4_t pk;
             pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
             pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
-            *(u32x4_t*)(s_col + r * 128 + ((c ^ wf_swz(r)) * 16)) = pk;
+            *(u32x4_t*)(s_col + r * 128 + ((c ^ tr_swz<128>(r)) * 16)) = pk;
         }
-        wf_lds_barrier();
+        lds_barrier();
         const unsigned la = l_dy + buf * (4 * 16384);
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
@@ -678,7 +645,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
                 acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1, fa, acc[q][1], 0, 0, 0);
             }
         }
-        wf_lds_barrier();                                                // everyone is done with s_patch / s_col / this dY buffer
+        lds_barrier();                                                // everyone is done with s_patch / s_col / this dY buffer
     };
     if (blk0 < blk1) {
         Stage sa, sb;
@@ -770,7 +737,7 @@ extern "C" int rbvae_conv_first_fused(int dtype, const float* x, int fd1, int fd
     RBVAE_CHECK_ARG(((uintptr_t)W | (uintptr_t)zero_page | (uintptr_t)col | (uintptr_t)out) % 16 == 0 &&
                     (!bias || (uintptr_t)bias % 16 == 0), "conv_first_fused: pointers must be 16-byte aligned");
     CfArgs a;
-    a.x = x; a.fm = CfFrameMap{fd1, fd2, fs0, fs1, fs2}; a.W = (const unsigned char*)W; a.bias = bias;
+    a.x = x; a.fm = FrameMap{fd1, fd2, fs0, fs1, fs2}; a.W = (const unsigned char*)W; a.bias = bias;
     a.zero = (const unsigned char*)zero_page; a.col = (unsigned char*)col; a.out = (unsigned char*)out;
     a.gate = nullptr; a.colsum_ws = nullptr;
     a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = (IH + 2 - 3) / 2 + 1; a.OW = (IW + 2 - 3) / 2 + 1;
@@ -797,7 +764,7 @@ extern "C" int rbvae_deconv_last_dgrad_fused(int dtype, const float* dpre, const
     RBVAE_CHECK_ARG(((uintptr_t)W | (uintptr_t)zero_page | (uintptr_t)col | (uintptr_t)out | (uintptr_t)gate) % 16 == 0,
                     "deconv_last_dgrad_fused: pointers must be 16-byte aligned");
     CfArgs a;
-    a.x = dpre; a.fm = CfFrameMap{0, 0, 0, 0, 0}; a.W = (const unsigned char*)W; a.bias = nullptr;
+    a.x = dpre; a.fm = FrameMap{0, 0, 0, 0, 0}; a.W = (const unsigned char*)W; a.bias = nullptr;
     a.zero = (const unsigned char*)zero_page; a.col = (unsigned char*)col; a.out = (unsigned char*)out;
     a.gate = (const unsigned char*)gate; a.colsum_ws = colsum_ws;
     a.N = N; a.Cin = Cout; a.IH = OH; a.IW = OW; a.OH = (OH + 2 - 3) / 2 + 1; a.OW = (OW + 2 - 3) / 2 + 1;
@@ -824,7 +791,7 @@ extern "C" int rbvae_wgrad_first(int dtype, int mode, const float* x, int fd1, i
     RBVAE_CHECK_ARG(ldy >= Nout && ldy % 8 == 0, "wgrad_first: ldy=%d", ldy);
     RBVAE_CHECK_ARG(((uintptr_t)dY | (uintptr_t)dW_slabs | (uintptr_t)zero_page) % 16 == 0, "wgrad_first: pointers must be 16-byte aligned");
     WfArgs a;
-    a.x = x; a.fm = mode == 0 ? CfFrameMap{fd1, fd2, fs0, fs1, fs2} : CfFrameMap{0, 0, 0, 0, 0};
+    a.x = x; a.fm = mode == 0 ? FrameMap{fd1, fd2, fs0, fs1, fs2} : FrameMap{0, 0, 0, 0, 0};
     a.dY = (const unsigned char*)dY; a.zero = (const unsigned char*)zero_page; a.dW = dW_slabs;
     a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = (IH + 2 - 3) / 2 + 1; a.OW = (IW + 2 - 3) / 2 + 1;
     a.Nout = Nout; a.ldy = ldy;

@@ -48,7 +48,7 @@ template <int N> __device__ __forceinline__ void ch_wait_barrier() {
 #if CH_ABL & 2
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(N) : "memory");
 #else
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+    wait_vm_lgkm_barrier<N>();
 #endif
 }
 
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
         const unsigned char* src = wtile + ((size_t)j * p.Kc) * ES + (size_t)kc * 128;
         unsigned char* lb = smem + A_BYTES + (j % RING) * CH_BBYTES + (w * LOADS) * 1024;
 #pragma unroll
-        for (int i = 0; i < LOADS; ++i) ch_glds16(src + blane[i], lb + i * 1024);
+        for (int i = 0; i < LOADS; ++i) glds16(src + blane[i], lb + i * 1024);
 #endif
     };
 
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) ChMma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
+            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
     };
     // The same MFMA group with patch piece I of slice kcn riding in it: its GroupNorm + swish arithmetic fills the
     // vector-issue slots between the MFMAs (done as one block at the slice boundary it left the matrix pipe idle for
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     // (whose last reader finished a slice ago; the barrier of the next slice's first step publishes the last piece).
     auto slice = [&](int kc, auto more_tag) {
         constexpr bool more = decltype(more_tag)::value;       // another slice follows (the last slice is its own instance)
-        ch_static_for<0, 9>([&](auto j_tag) {
+        static_for<0, 9>([&](auto j_tag) {
             constexpr int j = decltype(j_tag)::value;
             constexpr int nj = (j + 1) % 9;                  // tap of the next step
             using NJ = std::integral_constant<int, nj>;
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             }
         }
     }
-    ch_lds_barrier();
+    lds_barrier();
 
     // ---- store phase: whole 16-B chunks of NHWC rows (+ residual).  The residual chunks of all eight passes are fetched
     // before the first is used and the stores go out back to back (a load -> add -> store chain per pass left one
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             }
             fcnt = ncnt;
         }
-        ch_lds_barrier();                                  // every thread has read its tile rows: the tile's LDS is scratch now
+        lds_barrier();                                  // every thread has read its tile rows: the tile's LDS is scratch now
         // ... then over the eight waves and over a group's channels through LDS
         float* r_sum = (float*)smem;                       // [8 waves][BN]
         float* r_m2 = r_sum + 8 * CH_BN;                   // [8][BN]
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             }
             if (lane == 0) r_cnt[w] = fcnt;
         }
-        ch_lds_barrier();
+        lds_barrier();
         const int cg = p.stats_cg, ng = CH_BN / cg;
         if (tid < CH_BN) {
             float S = 0.f, N = 0.f;
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             c_m2[tid] = M2;
             if (tid == 0) c_m2[CH_BN] = N;
         }
-        ch_lds_barrier();
+        lds_barrier();
         if (tid < ng) {
             const float N = c_m2[CH_BN];
             float gm = 0.f;

@@ -269,20 +269,20 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
         SliceD d0 = desc(0);
         set_patch(d0);
         load_coefs();
-        ch_static_for<0, CW_NP>([&](auto k_tag) { load_piece(areg[decltype(k_tag)::value], pixoff[decltype(k_tag)::value]); });
+        static_for<0, CW_NP>([&](auto k_tag) { load_piece(areg[decltype(k_tag)::value], pixoff[decltype(k_tag)::value]); });
         take_coefs(std::integral_constant<int, CW_NP>{});
-        ch_static_for<0, CW_NP>([&](auto k_tag) { piece_landed(I0{}, areg[decltype(k_tag)::value]); });
+        static_for<0, CW_NP>([&](auto k_tag) { piece_landed(I0{}, areg[decltype(k_tag)::value]); });
         mask_proc = mask_ld;
-        ch_static_for<0, CW_NP>([&](auto k_tag) { piece(k_tag, 0); });
+        static_for<0, CW_NP>([&](auto k_tag) { piece(k_tag, 0); });
         {
             SliceD d1 = desc(1);
             set_patch(d1);
-            ch_static_for<0, 9>([&](auto j_tag) {
+            static_for<0, 9>([&](auto j_tag) {
                 constexpr int j = decltype(j_tag)::value;
                 if constexpr (j < 6) dummy4();
                 else tile(d0.wsoff + (j - 6) * p.Kc * 2, j - 6);
                 if constexpr (j == 0) load_coefs();
-                ch_static_for<cw_pp_before(j), cw_pp_before(j) + cw_pp(j)>([&](auto k_tag) {
+                static_for<cw_pp_before(j), cw_pp_before(j) + cw_pp(j)>([&](auto k_tag) {
                     load_piece(areg[decltype(k_tag)::value], pixoff[decltype(k_tag)::value]);
                 });
             });
@@ -294,14 +294,14 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             const SliceD dc = desc(g), dn = desc(g + 1), dl = desc(g + 2);
             const int v1 = dn.valid;
             const int nbuf = (g + 1) & 1;
-            ch_static_for<0, 9>([&](auto j_tag) {
+            static_for<0, 9>([&](auto j_tag) {
                 constexpr int j = decltype(j_tag)::value;
                 // tile u landed, this wave's patch writes done
                 constexpr int NTOP = cw_ntop(j, NC);
 #if CW_ABL & 32
                 asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NTOP) : "memory");
 #else
-                asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(NTOP) : "memory");
+                wait_vm_lgkm_barrier<NTOP>();
 #endif
                 // T: tile u + 3 into the slot unit u - 1 has left
                 const int slot = (g + j + 3) & (CW_RING - 1);
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
                     load_coefs();                            // C
                 }
                 // this body's pieces: landed (a period ago) -> GroupNorm -> the other patch buffer -> re-load for slice g + 2
-                ch_static_for<cw_pp_before(j), cw_pp_before(j) + cw_pp(j)>([&](auto k_tag) {
+                static_for<cw_pp_before(j), cw_pp_before(j) + cw_pp(j)>([&](auto k_tag) {
                     constexpr int K = decltype(k_tag)::value;
                     piece_landed(PieceWait{}, areg[K]);
                     if (v1) piece(k_tag, nbuf);
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) ChMma<bf16_t>::run(acc[mt][nt], fb[nt], fa[mt]);
+            for (int nt = 0; nt < NTW; ++nt) Mma<bf16_t>::run(acc[mt][nt], fb[nt], fa[mt]);
     };
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
     auto slice = [&](int g) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) ta[mt] = abase[mt] + (unsigned)((g & 1) * CH_ABUF);
-        ch_static_for<0, 9>([&](auto j_tag) {
+        static_for<0, 9>([&](auto j_tag) {
             constexpr int j = decltype(j_tag)::value;
             const unsigned rs = (unsigned)(((g + j) & (CW_RING - 1)) * CH_BBYTES);
 #if !(CW_ABL & 32)
@@ -434,7 +434,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
         const int sch = te & 15, rl = te >> 4;                     // store phase: 16 chunks per row x 32 row lanes
         // ---- epilogue through the patch buffer of the tile's last slice, 128 rows at a time (conv_halo_k's arithmetic)
         unsigned char* tile = smem + ((g - 1) & 1) * CH_ABUF;
-        ch_lds_barrier();
+        lds_barrier();
         // + bias, to bf16: the accumulators are free again (lane: pixel fi, channels 4 fg .. + 3 of each 16 x 16 block)
         uint2 pk[MT][NTW];
 #pragma unroll
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
                     for (int mt = 0; mt < MT; ++mt)
                         *(uint2*)(tile + (((wr & 1) * MT + mt) * 16 + fi) * CW_PITCH + ((wc * NTW + nt) * 16 + 4 * fg) * 2) = pk[mt][nt];
             }
-            ch_lds_barrier();
+            lds_barrier();
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int it = round * 4 + i, row = i * 32 + rl;
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             }
             if (round == 0) {
                 if (p.addend) addend_rows(1);
-                ch_lds_barrier();
+                lds_barrier();
             }
         }
         if (p.stats) {
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
                 }
                 fcnt = ncnt;
             }
-            ch_lds_barrier();
+            lds_barrier();
             float* r_sum = (float*)tile;                       // [8 waves][BN]
             float* r_m2 = r_sum + 8 * CH_BN;                   // [8][BN]
             float* r_cnt = r_m2 + 8 * CH_BN;                   // [8]
@@ -551,7 +551,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
                 }
                 if (lane == 0) r_cnt[w] = fcnt;
             }
-            ch_lds_barrier();
+            lds_barrier();
             const int cg = p.stats_cg;
             if (tid < CH_BN) {
                 float S = 0.f, N = 0.f;

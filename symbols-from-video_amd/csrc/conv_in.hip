@@ -11,14 +11,10 @@
 // the accumulators, 32 bytes per lane and pixel.  Statistics: per workgroup tile and group of cg channels the mean and the
 // sum of squared deviations of the STORED (bf16) values, two passes over the registers, merged over lanes by DPP row sums
 // and over waves through LDS; rbvae_gn_finish_tiles (tile 8 x 16) merges the tiles.
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short ci_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float ci_f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned ci_u32x4_t;
 
 struct CiArgs {
     const float* x;              // [N][Cin][H][W] f32
@@ -43,22 +39,6 @@ template <int CIN> struct CiOff {
         }
     }
 };
-
-__device__ __forceinline__ void ci_glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-template <int CTRL> __device__ __forceinline__ float ci_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// sum over the 16 lanes of a DPP row (lane & 15), every lane gets the total
-__device__ __forceinline__ float ci_row_sum(float v) {
-    v += ci_dpp<0x128>(v);     // row_ror:8
-    v += ci_dpp<0x124>(v);     // row_ror:4
-    v += ci_dpp<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += ci_dpp<0xB1>(v);      // quad_perm [1,0,3,2]
-    return v;
-}
 
 // NQ = 64-channel quads of the tile (Nout <= 64 NQ); wave = quad w % NQ x pixel tiles NQ (w / NQ) .. + NQ - 1
 template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) void conv_in_k(const CiArgs p) {
@@ -85,18 +65,18 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
             const int ct = r >> 4, j = r & 15;
             const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
             const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + ((schunk ^ ((r >> 1) & 7)) * 16) : p.zero;
-            ci_glds16(src, s_b + (size_t)(r - srow) * 128);
+            glds16(src, s_b + (size_t)(r - srow) * 128);
         }
     }
     const int fi = lane & 15, fg = lane >> 4;
     const int wq = w % NQ, wm = w / NQ;
     const int col = 64 * wq + 16 * fg;
     const bool first = col < p.Nout, second = col + 8 < p.Nout;
-    ci_f32x4_t bz4[4];
+    f32x4_t bz4[4];
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
-        bz4[h] = ci_f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (p.bias && col + 4 * h < p.Nout) bz4[h] = *(const ci_f32x4_t*)(p.bias + col + 4 * h);
+        bz4[h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        if (p.bias && col + 4 * h < p.Nout) bz4[h] = *(const f32x4_t*)(p.bias + col + 4 * h);
     }
     static constexpr CiOff<CIN> otab{};
     int koff[8];
@@ -139,33 +119,33 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
             const float v = koff[k8] >= 0 ? s_patch[corner + max(koff[k8], 0)] : 0.f;
             e[k8] = f32_to_bf16(v);
         }
-        ci_u32x4_t pk;
+        u32x4_t pk;
         pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
         pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
-        *(ci_u32x4_t*)(s_a + r * 128 + ((c ^ ((r >> 1) & 7)) * 16)) = pk;
+        *(u32x4_t*)(s_a + r * 128 + ((c ^ ((r >> 1) & 7)) * 16)) = pk;
     }
     __syncthreads();
 
     // 128 x 64 NQ x 64 on the matrix cores
     const int fsw = (fi >> 1) & 7;
-    ci_f32x4_t acc[MT][4];
+    f32x4_t acc[MT][4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int h = 0; h < 4; ++h) acc[mt][h] = ci_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < 4; ++h) acc[mt][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         const int ch = ((4 * kk + fg) ^ fsw) * 16;
-        ci_u32x4_t wv[4], av[MT];
+        u32x4_t wv[4], av[MT];
 #pragma unroll
-        for (int h = 0; h < 4; ++h) wv[h] = *(const ci_u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);
+        for (int h = 0; h < 4; ++h) wv[h] = *(const u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) av[mt] = *(const ci_u32x4_t*)(s_a + ((MT * wm + mt) * 16 + fi) * 128 + ch);
+        for (int mt = 0; mt < MT; ++mt) av[mt] = *(const u32x4_t*)(s_a + ((MT * wm + mt) * 16 + fi) * 128 + ch);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int h = 0; h < 4; ++h)
-                acc[mt][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const ci_bf16x8_t*)&wv[h], *(const ci_bf16x8_t*)&av[mt],
+                acc[mt][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&wv[h], *(const bf16x8_t*)&av[mt],
                                                                      acc[mt][h], 0, 0, 0);
     }
     // epilogue from registers: lane = pixel fi of tile mt, channels 64*wq + 16*fg .. +15 (two 16-byte chunks); the stored
@@ -180,7 +160,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         const size_t orow = (size_t)(n * p.H + oh) * p.Wd + ow;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            ci_u32x4_t val;
+            u32x4_t val;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int i0 = 8 * half + 2 * e, i1 = i0 + 1;
@@ -190,7 +170,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
                 xs[mt][i0] = __uint_as_float(lo << 16);
                 xs[mt][i1] = __uint_as_float(hi << 16);
             }
-            if (live[mt] && (half == 0 || second)) *(ci_u32x4_t*)(p.out + (orow * p.ldo + col + 8 * half) * 2) = val;
+            if (live[mt] && (half == 0 || second)) *(u32x4_t*)(p.out + (orow * p.ldo + col + 8 * half) * 2) = val;
         }
     }
     if (!p.stats) return;
@@ -215,7 +195,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
     }
     combine(q4, gs);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) gs[g] = ci_row_sum(gs[g]);
+    for (int g = 0; g < 4; ++g) gs[g] = row_sum(gs[g]);
     if (fi == 0) {
 #pragma unroll
         for (int g = 0; g < 4; ++g)
@@ -249,7 +229,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
     }
     combine(q4, gs);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) gs[g] = ci_row_sum(gs[g]);
+    for (int g = 0; g < 4; ++g) gs[g] = row_sum(gs[g]);
     if (fi == 0) {
 #pragma unroll
         for (int g = 0; g < 4; ++g)

@@ -26,7 +26,7 @@
 // unit are split around the next unit's barrier and fragment reads (gather_gemm.hip's software pipeline).
 // Epilogue = rbvae_gather_gemm's, element for element: +bias, ReLU, *scale, keyed / explicit dropout (same element indices),
 // ReLU gate, 16-byte NHWC stores through an LDS tile, per-tile column sums (bias gradients).
-#include "common.h"
+#include "mma.h"
 #include <type_traits>
 
 #ifndef CS_ABL          // timing ablations (results wrong on purpose; -DRBVAE_ABLATION builds only): 1 no LDS-DMA, 2 no fragment reads / MFMAs
@@ -37,10 +37,6 @@
 #endif
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short cs_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float cs_f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned cs_u32x4_t;
 
 struct CsArgs {
     const unsigned char* A;        // [Nimg*IH*IW][lda] bf16
@@ -72,22 +68,6 @@ __host__ __device__ constexpr int cs_pitch(bool codd) { return codd ? 17 : 16; }
 // wait for the next slice's first weight tile (issued at unit 6) covers them
 __host__ __device__ constexpr int cs_pp(int j) { return j < 0 ? 0 : j < 4 ? 2 : j == 4 ? 1 : 0; }
 __host__ __device__ constexpr int cs_pp_before(int j) { int s = 0; for (int k = 0; k < j; ++k) s += cs_pp(k); return s; }
-
-template <bool GATE> __device__ __forceinline__ bool cs_pos(const unsigned char* p, int e) {
-    const bf16_t v = ((const bf16_t*)p)[e];
-    return (v & 0x8000u) == 0 && (v & 0x7fffu) != 0 && (v & 0x7fffu) <= 0x7f80u;
-}
-
-template <int I, int N, typename F> __device__ __forceinline__ void cs_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        cs_static_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ void cs_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int N> __device__ __forceinline__ void cs_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 template <int BN> constexpr int cs_lds_main() {
     constexpr int ring = 2 * CS_PATCH + CS_RING * BN * 64;
@@ -184,11 +164,11 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
         // pieces of the two units before this one.
         auto slice = [&](int sl, auto more_tag) {
             constexpr bool more = decltype(more_tag)::value;         // another slice follows
-            cs_static_for<0, 9>([&](auto j_tag) {
+            static_for<0, 9>([&](auto j_tag) {
                 constexpr int j = decltype(j_tag)::value;
                 constexpr int tiles_after = more ? 2 : (8 - j < 2 ? 8 - j : 2);
                 constexpr int young = tiles_after * NW + (more ? cs_pp(j - 2) + cs_pp(j - 1) : 0);
-                cs_wait_barrier<young>();
+                wait_vm_barrier<young>();
                 if constexpr (more) {
                     if constexpr (cs_pp(j) > 0) patch_piece(sl + 1, cs_pp_before(j), cs_pp_before(j) + cs_pp(j));
                 }
@@ -221,14 +201,14 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
     // weight fragment of channel sub-tile nt: row 64 wc + 16 nt + fi of the tap tile, chunk fg at its swizzled position
     const unsigned vB = lds0 + 2 * CS_PATCH + (wc * 64 + fi) * 64 + ((fg ^ (3 * ((fi >> 3) & 1))) * 16);
 
-    cs_f32x4_t acc[MT][NT];
+    f32x4_t acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = cs_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     // fragment reads (inline asm: invisible to the compiler's wait-count pass; isa_check proves the counted waits)
-    auto read_unit = [&](auto j_tag, unsigned pbuf, unsigned rslot, cs_u32x4_t (&fa)[MT], cs_u32x4_t (&fb)[NT]) {
+    auto read_unit = [&](auto j_tag, unsigned pbuf, unsigned rslot, u32x4_t (&fa)[MT], u32x4_t (&fb)[NT]) {
         constexpr int j = decltype(j_tag)::value, kh = j / 3, kw = j % 3;
         constexpr bool codd = kw != 1;
         constexpr int pitch = cs_pitch(codd);
@@ -242,7 +222,7 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
         for (int mt = 0; mt < MT; ++mt)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[mt]) : "v"(aa), "n"(aimm + mt * pitch * 16));
     };
-    auto landed = [&](cs_u32x4_t (&fa)[MT], cs_u32x4_t (&fb)[NT]) {
+    auto landed = [&](u32x4_t (&fa)[MT], u32x4_t (&fb)[NT]) {
         if constexpr (MT == 4)
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
@@ -251,23 +231,23 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
     };
     // the MFMAs of output rows m0 .. m0 + MT / 2 - 1 of a unit (weights as the row operand: a lane owns 4 consecutive output
     // channels of one pixel)
-    auto mma_half = [&](auto m0_tag, const cs_u32x4_t (&fa)[MT], const cs_u32x4_t (&fb)[NT]) {
+    auto mma_half = [&](auto m0_tag, const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NT]) {
         constexpr int M0 = decltype(m0_tag)::value;
 #pragma unroll
         for (int mt = M0; mt < M0 + MT / 2; ++mt)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const cs_bf16x8_t*)&fb[nt], *(const cs_bf16x8_t*)&fa[mt],
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&fb[nt], *(const bf16x8_t*)&fa[mt],
                                                                       acc[mt][nt], 0, 0, 0);
     };
     using MLO = std::integral_constant<int, 0>;
     using MHI = std::integral_constant<int, MT / 2>;
 
-    cs_u32x4_t xa[MT], xb[NT], ya[MT], yb[NT];
+    u32x4_t xa[MT], xb[NT], ya[MT], yb[NT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) { xa[i] = cs_u32x4_t{0, 0, 0, 0}; ya[i] = cs_u32x4_t{0, 0, 0, 0}; }
+    for (int i = 0; i < MT; ++i) { xa[i] = u32x4_t{0, 0, 0, 0}; ya[i] = u32x4_t{0, 0, 0, 0}; }
 #pragma unroll
-    for (int i = 0; i < NT; ++i) { xb[i] = cs_u32x4_t{0, 0, 0, 0}; yb[i] = cs_u32x4_t{0, 0, 0, 0}; }
+    for (int i = 0; i < NT; ++i) { xb[i] = u32x4_t{0, 0, 0, 0}; yb[i] = u32x4_t{0, 0, 0, 0}; }
     unsigned rslot = 0;                         // byte offset of the ring slot of the unit being read
     // Unit u: barrier (its weight tile -- and at a slice's first tap its patch -- landed: the producer waves waited in front of
     // it; every MFMA wave is past the reads of unit u - 1, whose ring slot tile u + 3 takes) -> this unit's fragment reads ->
@@ -276,7 +256,7 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
     auto slice = [&](int sl, auto par_tag) {
         constexpr int PAR = decltype(par_tag)::value;
         const unsigned pbuf = (sl & 1) * CS_PATCH;
-        cs_static_for<0, 9>([&](auto j_tag) {
+        static_for<0, 9>([&](auto j_tag) {
             constexpr int j = decltype(j_tag)::value;
             asm volatile("s_barrier" ::: "memory");
 #if CS_ABL != 2
@@ -317,7 +297,7 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
         mma_half(MHI{}, ya, yb);                // (tap 8 of an odd slice: set y)
 #endif
     }
-    cs_lds_barrier();                           // (the producer waves have left: the barrier counts the MFMA waves only)
+    lds_barrier();                           // (the producer waves have left: the barrier counts the MFMA waves only)
 
     // ---- epilogue: bias, ReLU, scale -> bf16 tile in LDS -> dropout / gate -> 16-byte NHWC stores, column sums
     constexpr int PITCH = BN * 2 + 16;
@@ -350,17 +330,17 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
             *(uint2*)(tl + row * PITCH + cb * 2) = pk;
         }
     }
-    cs_lds_barrier();
+    lds_barrier();
     const int sch = tid % CPR, rl = tid / CPR;
     const int scol = n0 + sch * 8;
     DropKey dkey{0u, 0u};
     if (p.drop_mode == 1) dkey = drop_key(p.seed + (p.seed_dev ? p.seed_dev[0] * 0x9E3779B97F4A7C15ull : 0ull));
     int orow_[ITERS];
-    cs_u32x4_t gv[ITERS];
+    u32x4_t gv[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         orow_[it] = s_orow[it * RL + rl];
-        if (p.gate) gv[it] = *(const cs_u32x4_t*)(p.gate + ((size_t)(orow_[it] < 0 ? 0 : orow_[it]) * p.ldo + scol) * 2);
+        if (p.gate) gv[it] = *(const u32x4_t*)(p.gate + ((size_t)(orow_[it] < 0 ? 0 : orow_[it]) * p.ldo + scol) * 2);
     }
     float csum[8];
 #pragma unroll
@@ -369,7 +349,7 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
     for (int it = 0; it < ITERS; ++it) {
         const int row = it * RL + rl, orow = orow_[it];
         if (orow >= 0) {
-            cs_u32x4_t val = *(const cs_u32x4_t*)(tl + row * PITCH + sch * 16);
+            u32x4_t val = *(const u32x4_t*)(tl + row * PITCH + sch * 16);
             bf16_t* ev = (bf16_t*)&val;
             if (p.drop_mode == 1) {
                 const unsigned run = drop_run(dkey, (unsigned long long)orow * p.Nout + scol);
@@ -383,9 +363,9 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
             if (p.gate) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
-                    if (!cs_pos<true>((const unsigned char*)&gv[it], e)) ev[e] = 0;
+                    if (!elem_pos<bf16_t>((const unsigned char*)&gv[it], e)) ev[e] = 0;
             }
-            *(cs_u32x4_t*)(p.Out + ((size_t)orow * p.ldo + scol) * 2) = val;
+            *(u32x4_t*)(p.Out + ((size_t)orow * p.ldo + scol) * 2) = val;
             if (p.colsum_ws) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) csum[e] += bf16_to_f32(ev[e]);
@@ -395,7 +375,7 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
     if (p.colsum_ws) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) red[rl * BN + sch * 8 + e] = csum[e];
-        cs_lds_barrier();
+        lds_barrier();
         if (tid < BN) {
             float t = 0.f;
 #pragma unroll 8

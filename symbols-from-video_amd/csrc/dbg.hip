@@ -1,12 +1,9 @@
 // Hardware-mapping probes (rbvae_dbg_*): tiny kernels that pin the MFMA operand /
 // accumulator lane maps, the LDS-DMA destination order and the transposed LDS read
 // that conv_gemm.hip relies on.  Exercised by tests/test_hw_maps.py on the GPU.
-#include "common.h"
+#include "mma.h"
 
 namespace rbvae {
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 // A: [16][32] bf16 row-major, B: [32][16] bf16 row-major, D: [16][16] f32
 __global__ void dbg_mfma_bf16_k(const bf16_t* A, const bf16_t* B, float* D) {
@@ -31,8 +28,7 @@ __global__ void dbg_mfma_f32_k(const float* A, const float* B, float* D) {
 __global__ void dbg_glds_k(const unsigned* src, const int* lane_src_chunk, unsigned* out) {
     __shared__ __attribute__((aligned(16))) unsigned lds[256];
     const int l = threadIdx.x;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 4 * lane_src_chunk[l]),
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+    glds16(src + 4 * lane_src_chunk[l], lds);
     __syncthreads();
     for (int i = l; i < 256; i += 64) out[i] = lds[i];
 }

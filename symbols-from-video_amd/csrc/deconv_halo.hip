@@ -22,15 +22,11 @@
 // wave behind one barrier.  8 waves as 4 (pixel rows) x 2 (channel halves).  Epilogue class by class through one LDS tile:
 // bias, ReLU, scale, keyed / explicit dropout, ReLU gate of the layer below, per-tile column sums (bias gradients) --
 // element for element the arithmetic of rbvae_gather_gemm's epilogue (same dropout element indices).
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 struct DhArgs {
     const unsigned char* A;        // [Nimg*TH*TW][lda] T
@@ -76,46 +72,7 @@ constexpr int DH_BN = 64;
 constexpr int DH_TAPB = DH_BN * 128;          // one tap's weight tile
 constexpr int DH_STAGE = 2 * DH_TAPB;         // a step's stage: two taps
 
-__device__ __forceinline__ void dh_glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
 __device__ __forceinline__ unsigned dh_plane_off(int chunk, int plane) { return (unsigned)(chunk * plane + (chunk >> 1) * 32); }
-
-template <typename T> struct DhMma;
-template <> struct DhMma<bf16_t> {
-    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& rowop, const u32x4_t& colop) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&rowop, *(const bf16x8_t*)&colop, acc, 0, 0, 0);
-    }
-};
-template <> struct DhMma<float> {
-    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& rowop, const u32x4_t& colop) {
-        const f32x4_t r = *(const f32x4_t*)&rowop, c = *(const f32x4_t*)&colop;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(r[q], c[q], acc, 0, 0, 0);
-    }
-};
-
-template <typename T> __device__ __forceinline__ bool dh_pos(const unsigned char* p, int e);
-template <> __device__ __forceinline__ bool dh_pos<float>(const unsigned char* p, int e) { return ((const float*)p)[e] > 0.f; }
-template <> __device__ __forceinline__ bool dh_pos<bf16_t>(const unsigned char* p, int e) {
-    const bf16_t v = ((const bf16_t*)p)[e];
-    return (v & 0x8000u) == 0 && (v & 0x7fffu) != 0 && (v & 0x7fffu) <= 0x7f80u;
-}
-
-template <int I, int N, typename F> __device__ __forceinline__ void dh_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        dh_static_for<I + 1, N>(f);
-    }
-}
-// workgroup barrier that orders LDS traffic only.  __syncthreads() also waits vmcnt(0): behind the epilogue's global stores
-// every barrier then costs a full store round trip (the epilogue ran at half the HBM write rate because of it).
-__device__ __forceinline__ void dh_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int N> __device__ __forceinline__ void dh_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 template <typename T, int SC, int WAVES> constexpr int dh_lds_main() {
     constexpr int ES = sizeof(T), BM = 32 * WAVES;
@@ -265,7 +222,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
         const unsigned char* src0 = wtile + ((size_t)DH_WIDX[t0] * p.Kc) * ES + (size_t)kc * 128;
         const unsigned char* src1 = wtile + ((size_t)DH_WIDX[t1] * p.Kc) * ES + (size_t)kc * 128;
 #pragma unroll
-        for (int i = 0; i < LOADS; ++i) dh_glds16((((w * LOADS + i) >> 3) ? src1 : src0) + blane[i], lb + i * 1024);
+        for (int i = 0; i < LOADS; ++i) glds16((((w * LOADS + i) >> 3) ? src1 : src0) + blane[i], lb + i * 1024);
         pslot = (pslot + 1 == RING) ? 0 : pslot + 1;
     };
 
@@ -329,7 +286,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) DhMma<T>::run(acc[cls][mt][nt], fb[nt], fa[mt]);
+            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[cls][mt][nt], fb[nt], fa[mt]);
     };
     using Younger = std::integral_constant<int, MT + NTW>;
     using None = std::integral_constant<int, 0>;
@@ -343,7 +300,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     a_load(0, B1{}, areg);
     a_landed(std::integral_constant<int, 0>{}, areg);
     a_write(0, B1{}, areg);
-    dh_wait_barrier<0>();
+    wait_vm_lgkm_barrier<0>();
     b_issue(0, std::integral_constant<int, AHEAD>{});
     u32x4_t fa0[MT], fb0[NTW], fa1[MT], fb1[NTW];
     set_slice(0);
@@ -356,7 +313,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     // (loads, wait and stores inside one unrolled slice body: conv_halo.hip).
     auto slice = [&](int kc, auto more_tag) {
         constexpr bool more = decltype(more_tag)::value;
-        dh_static_for<0, 18>([&](auto h_tag) {
+        static_for<0, 18>([&](auto h_tag) {
             constexpr int h = decltype(h_tag)::value, t = h >> 1;
             constexpr bool cur0 = (h & 1) == 0;
             constexpr bool last_of_slice = h == 17;
@@ -384,10 +341,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
                 // the opened step's stage has landed; younger: the stage behind it (none behind the very last step), and
                 // when steps 2 / 3 open the patch batch issued behind it
                 constexpr int young = (more || last_of_slice) ? AHEAD - 1 : (AHEAD - 1 < 4 - ns ? AHEAD - 1 : 4 - ns);
-                if (last_of_slice && !moren && AHEAD - 1 > 4) dh_wait_barrier<0>();      // (never: AHEAD <= 2)
-                else if constexpr (ns == 2 && more) dh_wait_barrier<young * LOADS + NB0>();
-                else if constexpr (ns == 3 && more) dh_wait_barrier<young * LOADS + NB1>();
-                else dh_wait_barrier<young * LOADS>();
+                if (last_of_slice && !moren && AHEAD - 1 > 4) wait_vm_lgkm_barrier<0>();      // (never: AHEAD <= 2)
+                else if constexpr (ns == 2 && more) wait_vm_lgkm_barrier<young * LOADS + NB0>();
+                else if constexpr (ns == 3 && more) wait_vm_lgkm_barrier<young * LOADS + NB1>();
+                else wait_vm_lgkm_barrier<young * LOADS>();
                 cslot = (cslot + 1 == RING) ? 0 : cslot + 1;
                 if constexpr (ns + AHEAD < 5) b_issue(kn, std::integral_constant<int, (ns + AHEAD) % 5>{});
                 else if (moren) b_issue(kn + 1, std::integral_constant<int, (ns + AHEAD) % 5>{});
@@ -449,10 +406,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     int obase[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) obase[it] = s_obase[it * RL + rl];
-    dh_static_for<0, 4 / CPRD>([&](auto r_tag) {
+    static_for<0, 4 / CPRD>([&](auto r_tag) {
         constexpr int rnd = decltype(r_tag)::value;
-        if (rnd) dh_lds_barrier();                 // the previous round's readers are done with the tiles
-        dh_static_for<0, CPRD>([&](auto c_tag) {
+        if (rnd) lds_barrier();                 // the previous round's readers are done with the tiles
+        static_for<0, CPRD>([&](auto c_tag) {
             constexpr int cls = rnd * CPRD + decltype(c_tag)::value;
             unsigned char* tl = tile + decltype(c_tag)::value * DH_BM * PITCH;
 #pragma unroll
@@ -485,7 +442,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
                 }
             }
         });
-        dh_lds_barrier();
+        lds_barrier();
         // the round's gate chunks, all in flight before the first is used
         u32x4_t gv[CPRD][ITERS];
         if (p.gate) {
@@ -525,7 +482,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
                     if (p.gate) {
 #pragma unroll
                         for (int e = 0; e < EC; ++e)
-                            if (!dh_pos<T>((const unsigned char*)&gv[c][it], e)) ev[e] = 0;
+                            if (!elem_pos<T>((const unsigned char*)&gv[c][it], e)) ev[e] = 0;
                     }
                     *(u32x4_t*)(p.Out + ((size_t)orow * p.ldo + scol) * ES) = val;
                     if (p.colsum_ws) {
@@ -538,10 +495,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
         if (p.colsum_ws) {
 #pragma unroll
             for (int c = 0; c < CPRD; ++c) {
-                if (c) dh_lds_barrier();
+                if (c) lds_barrier();
 #pragma unroll
                 for (int e = 0; e < EC; ++e) red[rl * DH_BN + sch * EC + e] = csum[c][e];
-                dh_lds_barrier();
+                lds_barrier();
                 if (tid < DH_BN) {
                     float t = 0.f;
 #pragma unroll 8

@@ -9,22 +9,10 @@
 //
 // It replaces the product GEMM (Y to HBM as bf16) + the col2im pass of the two-kernel path; same sums in the same
 // tap order, with Y in f32 instead of bf16.
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-struct DlFrameMap { int d1, d2; long s0, s1, s2; };
-__device__ __forceinline__ long dl_frame_off(const DlFrameMap& f, unsigned n) {
-    if (f.d1 == 0) return (long)n * f.s2;
-    const unsigned a = n / (unsigned)f.d1, r = n - a * (unsigned)f.d1;
-    const unsigned b = r / (unsigned)f.d2, c = r - b * (unsigned)f.d2;
-    return (long)a * f.s0 + (long)b * f.s1 + (long)c * f.s2;
-}
 
 struct DlArgs {
     const unsigned char* D2;     // [N*IH*IW][C1] bf16
@@ -33,7 +21,7 @@ struct DlArgs {
     const unsigned char* zero;   // >= 16 zero bytes
     float* xr;                   // [N][Cout][OH][OW]
     const float* target;         // frames through tfm (or null)
-    DlFrameMap tfm;
+    FrameMap tfm;
     float* ws;                   // [gridDim.x] squared-error sums, then [gridDim.x][4] column sums of dpre (or null)
     float* dpre;                 // [N][OH][OW][Cout] or null
     float gscale;
@@ -53,11 +41,6 @@ constexpr int DL_PIX = DL_HA * DL_HB;                // 153
 constexpr int DL_MROWS = 160;                        // padded to MFMA tiles
 constexpr int DL_WROWS = 48;
 constexpr int DL_YP = 37;                            // Y row pitch (floats)
-
-__device__ __forceinline__ void dl_glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
 
 template <bool ONE>
 __global__ __launch_bounds__(256, (DL_SL == 1 ? 5 : 3)) void deconv_last_fused_k(const DlArgs p) {
@@ -96,7 +79,7 @@ __global__ __launch_bounds__(256, (DL_SL == 1 ? 5 : 3)) void deconv_last_fused_k
         const int q = tid + 256 * it;
         const int oh = 2 * a0 + q / (2 * DL_TB), ow = 2 * b0 + q % (2 * DL_TB);
         const bool ok = p.target && oh < OH && ow < OW;
-        const float* tp = p.target + (ok ? dl_frame_off(p.tfm, n) + (long)oh * OW + ow : 0);
+        const float* tp = p.target + (ok ? frame_off_u32(p.tfm, n) + (long)oh * OW + ow : 0);
 #pragma unroll
         for (int c = 0; c < 4; ++c) tg[it][c] = (ok && c < p.Cout) ? tp[(long)c * OHW] : 0.f;
     }
@@ -157,7 +140,7 @@ __global__ __launch_bounds__(256, (DL_SL == 1 ? 5 : 3)) void deconv_last_fused_k
             }
             unsigned char* dst = (is_w ? s_wts + (size_t)buf * DL_WROWS * 128 : s_pix + (size_t)buf * DL_MROWS * 128) +
                                  (size_t)(r - srow) * 128;
-            dl_glds16(src, dst);
+            glds16(src, dst);
         }
     };
     auto stage = [&](int s, int buf) __attribute__((always_inline)) {
@@ -165,7 +148,7 @@ __global__ __launch_bounds__(256, (DL_SL == 1 ? 5 : 3)) void deconv_last_fused_k
         else {
 #pragma unroll
             for (int i = 0; i < NPIECE; ++i)
-                if (w + 4 * i < PIX_I + WTS_I) dl_glds16(psrc[i] + (size_t)(pinc[i] * (unsigned)s), smem + pdst[i] + pbuf[i] * (unsigned)buf);
+                if (w + 4 * i < PIX_I + WTS_I) glds16(psrc[i] + (size_t)(pinc[i] * (unsigned)s), smem + pdst[i] + pbuf[i] * (unsigned)buf);
         }
     };
     // this wave's LDS-DMA count per slice: q = w, w + 4, ... < 26
@@ -181,10 +164,10 @@ __global__ __launch_bounds__(256, (DL_SL == 1 ? 5 : 3)) void deconv_last_fused_k
         if (s + 1 < KS) {
             stage(s + 1, buf ^ 1);
             // slice s landed for this wave (its PER pieces of slice s+1 stay in flight), then the workgroup barrier
-            if (w < 2) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(PER0) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(PER1) : "memory");
+            if (w < 2) wait_vm_lgkm_barrier<PER0>();
+            else wait_vm_lgkm_barrier<PER1>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            wait_vm_lgkm_barrier<0>();
         }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -238,7 +221,7 @@ __global__ __launch_bounds__(256, (DL_SL == 1 ? 5 : 3)) void deconv_last_fused_k
             }
             unsigned char* dst = (is_w ? s_wts + (size_t)sl * DL_WROWS * 128 : s_pix + (size_t)sl * DL_MROWS * 128) +
                                  (size_t)(r - srow) * 128;
-            dl_glds16(src, dst);
+            glds16(src, dst);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -393,7 +376,7 @@ extern "C" int rbvae_deconv_last_fused(int dtype, const void* D2, const void* V,
                     "deconv_last_fused: pointers must be 16-byte aligned");
     DlArgs a;
     a.D2 = (const unsigned char*)D2; a.V = (const unsigned char*)V; a.bias = bias; a.zero = (const unsigned char*)zero_page;
-    a.xr = xr; a.target = target; a.tfm = DlFrameMap{fd1, fd2, fs0, fs1, fs2}; a.ws = target ? ws : nullptr; a.dpre = dpre;
+    a.xr = xr; a.target = target; a.tfm = FrameMap{fd1, fd2, fs0, fs1, fs2}; a.ws = target ? ws : nullptr; a.dpre = dpre;
     a.gscale = gscale; a.N = N; a.IH = IH; a.IW = IW; a.C1 = C1; a.NYP = NYP; a.Cout = Cout;
     const size_t lds = dl_lds(C1);
     static size_t attr_lds[2] = {0, 0};

@@ -13,13 +13,9 @@
 // Arithmetic is that of gather_gemm_k element for element (two 32-deep MFMAs in k order, + bias, round to bf16);
 // the optional column sums of the STORED values (the bias gradient of the layer below the encoder's fc) come out
 // per 128-row tile in gather_gemm_k's layout [tile][N], summed in a different (fixed) order.
-#include "common.h"
+#include "mma.h"
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 struct FcArgs {
     const unsigned char* A;      // [M][lda] bf16, K used columns
@@ -29,18 +25,6 @@ struct FcArgs {
     float* colsum_ws;            // [ceil(M/128)][N] or null
     int M, N, lda, ldo;
 };
-
-template <int CTRL> __device__ __forceinline__ float fc_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// sum over the 16 lanes of a DPP row (lane & 15), every lane gets the total
-__device__ __forceinline__ float fc_row_sum(float v) {
-    v += fc_dpp<0x128>(v);     // row_ror:8
-    v += fc_dpp<0x124>(v);     // row_ror:4
-    v += fc_dpp<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += fc_dpp<0xB1>(v);      // quad_perm [1,0,3,2]
-    return v;
-}
 
 // grid (N / 16, ceil(M / 256)), 256 threads: wave w owns rows 64 w .. 64 w + 63 of the workgroup's 256.
 // KH = 32-deep MFMA steps: K = 64 (latent_dim <= 64) or 128 (latent_dim 65 .. 128).
@@ -93,7 +77,7 @@ __global__ __launch_bounds__(256) void fc_gemm_k(const FcArgs p) {
     if (p.colsum_ws) {
         __shared__ float red[4][16];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) cs[r] = fc_row_sum(cs[r]);
+        for (int r = 0; r < 4; ++r) cs[r] = row_sum(cs[r]);
         if (fi == 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) red[w][4 * fg + r] = cs[r];
@@ -184,7 +168,7 @@ __global__ __launch_bounds__(256) void fc_gemm_wide_k(const FcArgs p) {
     if (p.colsum_ws) {
         __shared__ float red[4][64];
 #pragma unroll
-        for (int c = 0; c < 16; ++c) cs[c] = fc_row_sum(cs[c]);
+        for (int c = 0; c < 16; ++c) cs[c] = row_sum(cs[c]);
         if (fi == 0) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) red[w][16 * fg + c] = cs[c];

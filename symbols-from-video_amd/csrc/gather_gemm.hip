@@ -21,15 +21,11 @@
 // The accumulator is produced transposed (weights as the MFMA row operand) so a
 // lane owns 4 consecutive output channels of one pixel; the tile goes through
 // LDS once more and leaves as whole 16-B chunks of NHWC rows.
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 struct TapClass {
     int ntaps;
@@ -65,37 +61,6 @@ struct GgArgs {
     unsigned long long* stamps; // debug (rbvae_dbg_gg_stamps): [workgroup][8] phase time stamps (100 MHz), or null
     TapClass cls[4];
 };
-
-__device__ __forceinline__ void glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-    // one 128-B LDS row slice = 64 k: two 32-k MFMAs, lane group g reads chunk 4*kk+g
-    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& rowop, const u32x4_t& colop) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&rowop, *(const bf16x8_t*)&colop, acc,
-                                                      0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    // 32 k per row slice; lane group g holds k = 16*kk + 4*g + c for MFMA c (same on both operands)
-    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& rowop, const u32x4_t& colop) {
-        const f32x4_t r = *(const f32x4_t*)&rowop, c = *(const f32x4_t*)&colop;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(r[q], c[q], acc, 0, 0, 0);
-    }
-};
-
-template <typename T> __device__ __forceinline__ bool elem_pos(const unsigned char* p, int e);
-template <> __device__ __forceinline__ bool elem_pos<float>(const unsigned char* p, int e) {
-    return ((const float*)p)[e] > 0.f;
-}
-template <> __device__ __forceinline__ bool elem_pos<bf16_t>(const unsigned char* p, int e) {
-    const bf16_t v = ((const bf16_t*)p)[e];
-    return (v & 0x8000u) == 0 && (v & 0x7fffu) != 0 && (v & 0x7fffu) <= 0x7f80u;   // > 0 (NaN excluded)
-}
 
 constexpr int GG_BM = 128;
 
@@ -136,12 +101,6 @@ __device__ __forceinline__ void split_row(const GgArgs& p, int m, int& n, int& a
                 wall_clock64();                                          \
     } while (0)
 #endif
-
-template <int N> __device__ __forceinline__ void wait_vmcnt_barrier() {
-    // counted wait (LDS-DMA of the slice about to be read has landed for THIS wave), then the
-    // workgroup barrier; no vmcnt(0) drain, so younger slices stay in flight across the barrier
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // GG_NS = LDS ring depth.  3: two K-slices in flight behind the one being multiplied (one workgroup per
 // CU, deep K); 2: classic double buffer, two workgroups per CU; 1: single buffer for 1-2 slice problems
@@ -379,7 +338,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
         for (int s = 0; s < nsteps; ++s) {
             if (s > 0) __syncthreads();              // everyone is done reading the single buffer
             stage_next();
-            wait_vmcnt_barrier<0>();
+            wait_vm_lgkm_barrier<0>();
             // one fragment set, reused by both halves (registers, see the launch bounds)
             read_half(lds0, 0, fa0, fb0);
             landed(None{}, fa0, fb0);
@@ -396,8 +355,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
 #pragma unroll
         for (int i = 0; i < GG_NS - 1; ++i)
             if (i < nsteps) stage_next();
-        if (nsteps > GG_NS - 1 && GG_NS > 2) wait_vmcnt_barrier<(GG_NS > 2 ? GG_NS - 2 : 0) * LOADS>();
-        else wait_vmcnt_barrier<0>();
+        if (nsteps > GG_NS - 1 && GG_NS > 2) wait_vm_lgkm_barrier<(GG_NS > 2 ? GG_NS - 2 : 0) * LOADS>();
+        else wait_vm_lgkm_barrier<0>();
         if (GG_NS - 1 < nsteps) stage_next();
         int cbuf = 0;
         read_half(lds0, 0, fa0, fb0);
@@ -417,8 +376,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
             landed(None{}, fa1, fb1);                    // issued a whole MFMA group ago (one wait site per set)
             // slice s+1 landed (GG_NS-2 younger ones may stay in flight); after the barrier every wave
             // holds both halves of slice s in registers, so its buffer can be refilled
-            if (GG_NS > 2 && nsteps - s - 2 >= GG_NS - 2) wait_vmcnt_barrier<(GG_NS > 2 ? GG_NS - 2 : 0) * LOADS>();
-            else wait_vmcnt_barrier<0>();
+            if (GG_NS > 2 && nsteps - s - 2 >= GG_NS - 2) wait_vm_lgkm_barrier<(GG_NS > 2 ? GG_NS - 2 : 0) * LOADS>();
+            else wait_vm_lgkm_barrier<0>();
             if (!late && s + GG_NS < nsteps) stage_next();
             read_half(lds0 + cbuf * STAGE, 0, fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
@@ -567,11 +526,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     if (p.colsum_ws) {
         // bias gradient: column sums of this tile's stored rows, reduced over the row lanes in LDS.  LDS-only barriers:
         // __syncthreads() also waits vmcnt(0), i.e. for the round trip of the tile's global stores just issued
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         float* red = (float*)smem;                     // [RL][BN]
 #pragma unroll
         for (int e = 0; e < EC; ++e) red[rl * BN + sch * EC + e] = csum[e];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if (tid < BN && n0 + tid < p.Nout) {
             float t = 0.f;
 #pragma unroll

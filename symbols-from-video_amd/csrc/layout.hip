@@ -2,14 +2,10 @@
 // slab reduction back to torch layouts, im2col for the few-channel ends of the
 // network, the col2im + sigmoid + MSE epilogue of the last ConvTranspose2d, column
 // sums (bias gradients), f32 -> T casts, the skinny Linear (N <= 128) and Adam.
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 // out[i0*s0 + i1*s1 + i2*s2] = in[i0][i1][i2]   (in: contiguous f32)
 template <typename T>
@@ -137,19 +133,6 @@ __global__ __launch_bounds__(256) void colsum_final_k(const float* __restrict__ 
     }
 }
 
-// Frame n of a batch -> element offset of its first value.  d1 == 0: n * s2.  Otherwise n is read as the
-// mixed-radix number (n / d1, (n % d1) / d2, n % d2) with strides (s0, s1, s2): the fused trainer runs both
-// views of an item batch [B][2][T] as frames v*(B*T) + b*T + t without first copying them into that order.
-struct FrameMap {
-    int d1, d2;
-    long s0, s1, s2;
-};
-template <typename I> __device__ __forceinline__ I frame_off(const FrameMap& f, I n) {
-    if (f.d1 == 0) return n * (I)f.s2;
-    const I a = n / (I)f.d1, r = n - a * (I)f.d1;
-    const I b = r / (I)f.d2, c = r - b * (I)f.d2;
-    return a * (I)f.s0 + b * (I)f.s1 + c * (I)f.s2;
-}
 static long frame_span(const FrameMap& f, int N) {      // largest frame offset (non-negative strides)
     if (f.d1 == 0) return (long)(N - 1) * f.s2;
     return (long)((N - 1) / f.d1) * f.s0 + (long)(f.d1 / f.d2 - 1) * f.s1 + (long)(f.d2 - 1) * f.s2;

@@ -9,7 +9,7 @@
 //
 // Weight block layout (= the reference's registration order, per layer):
 //   w_ih [4L][L], w_hh [4L][L], b_ih [4L], b_hh [4L]      -> 8*L*L + 8*L floats per layer
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 
 // Wave priority of the latency-bound kernels that share the chip with full-grid GEMMs on the side stream (the LSTM
@@ -50,21 +50,19 @@ __global__ __launch_bounds__(512) void lstm_fwd_k(const float* __restrict__ wblk
     for (int i = j; i < T * L; i += blockDim.x) xin[i] = hs_all[((long)s * T) * L + i];
     for (int l = 0; l < layers; ++l) {
         const float* wl = wblk + l * lstm_layer_floats(L);
-        float wih[LMAX > 0 ? LMAX : 1], whh[LMAX > 0 ? LMAX : 1];
+        float wih[LMAX], whh[LMAX];
         float bsum = 0.f;
         if (row) {
             bsum = wl[8l * L * L + j] + wl[8l * L * L + 4 * L + j];
-            if constexpr (LMAX > 0) {
-                // clamped index: every load is unconditional (no branch per element)
-                const float* pi = wl + j * L;
-                const float* ph = pi + 4 * L * L;
+            // clamped index: every load is unconditional (no branch per element)
+            const float* pi = wl + j * L;
+            const float* ph = pi + 4 * L * L;
 #pragma unroll
-                for (int k = 0; k < LMAX; ++k) {
-                    const int kk = k < L ? k : L - 1;
-                    const float a = pi[kk], b = ph[kk];
-                    wih[k] = k < L ? a : 0.f;
-                    whh[k] = k < L ? b : 0.f;
-                }
+            for (int k = 0; k < LMAX; ++k) {
+                const int kk = k < L ? k : L - 1;
+                const float a = pi[kk], b = ph[kk];
+                wih[k] = k < L ? a : 0.f;
+                whh[k] = k < L ? b : 0.f;
             }
         }
         if (j < L) hcur[j] = 0.f;
@@ -74,19 +72,12 @@ __global__ __launch_bounds__(512) void lstm_fwd_k(const float* __restrict__ wblk
             if (row) {
                 float a = bsum;
                 const float* xt = xin + t * L;
-                if constexpr (LMAX > 0) {
 #pragma unroll
-                    for (int k = 0; k < LMAX; ++k)
-                        if (k < L) a = fmaf(wih[k], xt[k], a);
+                for (int k = 0; k < LMAX; ++k)
+                    if (k < L) a = fmaf(wih[k], xt[k], a);
 #pragma unroll
-                    for (int k = 0; k < LMAX; ++k)
-                        if (k < L) a = fmaf(whh[k], hcur[k], a);
-                } else {
-                    const float* wi = wl + (long)j * L;
-                    const float* wh = wl + 4l * L * L + (long)j * L;
-                    for (int k = 0; k < L; ++k) a = fmaf(wi[k], xt[k], a);
-                    for (int k = 0; k < L; ++k) a = fmaf(wh[k], hcur[k], a);
-                }
+                for (int k = 0; k < LMAX; ++k)
+                    if (k < L) a = fmaf(whh[k], hcur[k], a);
                 gates[j] = a;
             }
             __syncthreads();
@@ -134,18 +125,16 @@ __global__ __launch_bounds__(512) void lstm_bwd_k(const float* __restrict__ wblk
     for (int i = j; i < T * L; i += blockDim.x) dhout[i] = g_top[((long)s * T) * L + i];
     for (int l = layers - 1; l >= 0; --l) {
         const float* wl = wblk + l * lstm_layer_floats(L);
-        float wic[LMAX > 0 ? LMAX : 1], whc[LMAX > 0 ? LMAX : 1];
-        if constexpr (LMAX > 0) {
-            if (row) {
-                const float* pi = wl + prt * L * L + kcol;
-                const float* ph = pi + 4 * L * L;
+        float wic[LMAX], whc[LMAX];
+        if (row) {
+            const float* pi = wl + prt * L * L + kcol;
+            const float* ph = pi + 4 * L * L;
 #pragma unroll
-                for (int jj = 0; jj < LMAX; ++jj) {
-                    const int o = (jj < L ? jj : L - 1) * L;
-                    const float a = pi[o], b = ph[o];
-                    wic[jj] = jj < L ? a : 0.f;
-                    whc[jj] = jj < L ? b : 0.f;
-                }
+            for (int jj = 0; jj < LMAX; ++jj) {
+                const int o = (jj < L ? jj : L - 1) * L;
+                const float a = pi[o], b = ph[o];
+                wic[jj] = jj < L ? a : 0.f;
+                whc[jj] = jj < L ? b : 0.f;
             }
         }
         if (j < L) dhrec[j] = 0.f;
@@ -174,17 +163,9 @@ __global__ __launch_bounds__(512) void lstm_bwd_k(const float* __restrict__ wblk
             if (row) {
                 float ax = 0.f, ah = 0.f;
                 const float* dgp = dg + prt * L;
-                if constexpr (LMAX > 0) {
 #pragma unroll
-                    for (int jj = 0; jj < LMAX; ++jj)
-                        if (jj < L) { ax = fmaf(wic[jj], dgp[jj], ax); ah = fmaf(whc[jj], dgp[jj], ah); }
-                } else {
-                    for (int jj = 0; jj < L; ++jj) {
-                        const float d = dgp[jj];
-                        ax = fmaf(wl[(long)(prt * L + jj) * L + kcol], d, ax);
-                        ah = fmaf(wl[4l * L * L + (long)(prt * L + jj) * L + kcol], d, ah);
-                    }
-                }
+                for (int jj = 0; jj < LMAX; ++jj)
+                    if (jj < L) { ax = fmaf(wic[jj], dgp[jj], ax); ah = fmaf(whc[jj], dgp[jj], ah); }
                 part[(prt * 2 + 0) * L + kcol] = ax;
                 part[(prt * 2 + 1) * L + kcol] = ah;
             }
@@ -199,31 +180,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_k(const float* __restrict__ wblk
     }
     for (int i = j; i < T * L; i += blockDim.x) dx[((long)s * T) * L + i] = dhout[i];
 }
-
-// Weight gradients of every layer in one launch.
-//   grad block (same layout as the weight block): dW_ih = dG^T X, dW_hh = dG^T Hprev, db_ih = db_hh = colsum(dG)
-// grid = (ceil(4L*(L+1)/256), 2, layers): y = 0 -> ih (+ b_ih), y = 1 -> hh (+ b_hh); column L is the bias.
-__global__ __launch_bounds__(256) void lstm_wgrad_k(const float* __restrict__ dG, const float* __restrict__ hs_all,
-                                                    const float* __restrict__ hprev, float* __restrict__ gblk,
-                                                    int S, int T, int L, int accumulate) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= 4 * L * (L + 1)) return;
-    const int l = blockIdx.z, hh = blockIdx.y;
-    const int k = e / (4 * L), jrow = e - k * (4 * L);      // consecutive threads -> consecutive gate rows
-    const long R = (long)S * T;
-    const float* g = dG + (long)l * R * 4 * L + jrow;
-    const float* x = (hh ? hprev + (long)l * R * L : hs_all + (long)l * R * L) + k;
-    float acc = 0.f;
-    if (k < L)
-        for (long r = 0; r < R; ++r) acc = fmaf(g[r * 4 * L], x[r * L], acc);
-    else
-        for (long r = 0; r < R; ++r) acc += g[r * 4 * L];
-    float* out = gblk + l * (8l * L * L + 8l * L);
-    float* dst = k < L ? out + (hh ? 4l * L * L : 0) + (long)jrow * L + k
-                       : out + 8l * L * L + (hh ? 4 * L : 0) + jrow;
-    *dst = accumulate ? *dst + acc : acc;
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // Wavefront variants: every layer gets its own group of G = roundup64(4L) threads with its weight
@@ -240,10 +196,6 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)) - 1.0f;
 }
 
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // ---------------------------------------------------------------------------------------------
 // 32 < L <= 128 (the reference's sweeps and best models use latent_dim 50 / 75 / 100): one workgroup per sequence,
 // layer by layer.  A layer's two weight matrices do not fit one thread's registers any more (2L values per gate row),
@@ -254,8 +206,8 @@ __device__ __forceinline__ void lds_barrier() {
 //   * one lane per gate row, L <= 128 weights in its registers, at most 512 threads (two waves per SIMD: a 256-register
 //     budget -- with two lanes per row and 1024 threads the 128-register budget spilled, and every spill reload in
 //     the time loop waited, through the shared vmcnt counter, for the step's global stores: 2.3 us per step).
-// The layer-sequential kernel this replaces for these sizes read its weights from memory inside the time loop
-// (L > 64) or spilled them (L <= 64): 3.76 ms per fused step at L = 100 against 0.46 ms at L = 32.
+// The wider instances of the layer-sequential kernel that this replaced (since removed) read their weights from memory
+// inside the time loop (L > 64) or spilled them (L <= 64): 3.76 ms per fused step at L = 100 against 0.46 ms at L = 32.
 // Vector rows (x_t, h_t) live in LDS at a stride of 128 floats, zero-filled, so 16-byte reads past L see zeros (the
 // weights there are zero too).
 // ---------------------------------------------------------------------------------------------
@@ -384,9 +336,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_big_k(const float* __restrict__ 
 // one batch per layer.  dG rows sit in LDS in four 132-float segments (one per lane of a group: conflict-free 16-byte
 // reads).
 constexpr int BIG_SEG = 132;
-template <int CTRL> __device__ __forceinline__ float big_quad(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
 template <int NCH>
 __global__ __launch_bounds__(512) void lstm_bwd_big_k(const float* __restrict__ wblk, const float* __restrict__ wT,
                                                       const float* __restrict__ acts, const float* __restrict__ cs,
@@ -462,8 +411,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_big_k(const float* __restrict__ 
             }
             lds_barrier();
             float a = big_dot<NCH>(w, dgall + t * DS + p * BIG_SEG);
-            a += big_quad<0xB1>(a);          // + lane ^ 1   (DPP quad_perm [1,0,3,2]; a + b == b + a: the sums of __shfl_xor)
-            a += big_quad<0x4E>(a);          // + lane ^ 2   (quad_perm [2,3,0,1])
+            a += dpp<0xB1>(a);          // + lane ^ 1   (DPP quad_perm [1,0,3,2]; a + b == b + a: the sums of __shfl_xor)
+            a += dpp<0x4E>(a);          // + lane ^ 2   (quad_perm [2,3,0,1])
             if (p == 0 && col) dhrec[k] = a;
             lds_barrier();
         }
@@ -471,8 +420,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_big_k(const float* __restrict__ 
 #pragma unroll 1
         for (int t = 0; t < T; ++t) {
             float a = big_dot<NCH>(w, dgall + t * DS + p * BIG_SEG);
-            a += big_quad<0xB1>(a);          // + lane ^ 1   (DPP quad_perm [1,0,3,2]; a + b == b + a: the sums of __shfl_xor)
-            a += big_quad<0x4E>(a);          // + lane ^ 2   (quad_perm [2,3,0,1])
+            a += dpp<0xB1>(a);          // + lane ^ 1   (DPP quad_perm [1,0,3,2]; a + b == b + a: the sums of __shfl_xor)
+            a += dpp<0x4E>(a);          // + lane ^ 2   (quad_perm [2,3,0,1])
             if (p == 0 && col) dxin[t * BIG_VS + k] = a;
         }
         __syncthreads();
@@ -1519,86 +1468,16 @@ __global__ __launch_bounds__(512) void lstm_pair_bwd_unit_k(const PairBwdArgs p)
     if (vl == 0 && hf == 0 && p.dx_colsum) p.dx_colsum[(long)s * L + j] = dx_sum;
 }
 
-// Weight gradients, LDS-tiled: block = (8 gate rows, ih|hh, layer); thread (jj, kq) owns gate row jj and
-// the columns kq, kq+32, ... (column L = the bias).  Rows of dG / X stream through LDS 128 at a time.
-constexpr int LW_ROWS = 128;
-constexpr int LW_JT = 8;
-template <int LW_KMAX>          // ceil((L + 1) / 32): 2 for L <= 32, 3 for L <= 64, 5 for L <= 128
-__global__ __launch_bounds__(256) void lstm_wgrad_tiled_k(const float* __restrict__ dG, const float* __restrict__ hs_all,
-                                                          const float* __restrict__ hprev, float* __restrict__ gblk,
-                                                          const float* __restrict__ dG2, const float* __restrict__ hs_all2,
-                                                          const float* __restrict__ hprev2, float* __restrict__ gblk2,
-                                                          int S, int T, int L, int layers, int accumulate) {
-    extern __shared__ float sm[];
-    float* sg = sm;                         // [LW_ROWS][LW_JT gate rows]
-    float* sx = sg + LW_ROWS * LW_JT;       // [LW_ROWS][L + 1]   (column L holds 1.0: the bias column)
-    // grid.z = layers of the first stack, then (optionally) layers of a second one: encoder and decoder
-    // stacks share one launch
-    int l = blockIdx.z;
-    if (l >= layers) { l -= layers; dG = dG2; hs_all = hs_all2; hprev = hprev2; gblk = gblk2; }
-    const int hh = blockIdx.y, j0 = blockIdx.x * LW_JT;
-    const int jj = threadIdx.x & (LW_JT - 1), kq = threadIdx.x / LW_JT;     // kq in [0, 32)
-    const int R = S * T, LP = L + 1;
-    const float* g = dG + (long)l * R * 4 * L;
-    const float* x = hh ? hprev + (long)l * R * L : hs_all + (long)l * R * L;
-    float acc[LW_KMAX];
-#pragma unroll
-    for (int i = 0; i < LW_KMAX; ++i) acc[i] = 0.f;
-    for (int r0 = 0; r0 < R; r0 += LW_ROWS) {
-        const int nr = min(LW_ROWS, R - r0);
-        // clamped indices: every load is unconditional, so a thread's loads are all in flight together
-#pragma unroll
-        for (int it = 0; it < LW_ROWS * LW_JT / 256; ++it) {
-            const int i = threadIdx.x + it * 256;
-            const int r = i / LW_JT, c = i & (LW_JT - 1);
-            const float v = g[(long)(r0 + min(r, nr - 1)) * 4 * L + min(j0 + c, 4 * L - 1)];
-            sg[i] = (r < nr && j0 + c < 4 * L) ? v : 0.f;
-        }
-        for (int i0 = 0; i0 < LW_ROWS * L; i0 += 256 * 8) {
-#pragma unroll
-            for (int it = 0; it < 8; ++it) {
-                const int i = i0 + threadIdx.x + it * 256;
-                const float v = x[(long)r0 * L + min(i, nr * L - 1)];
-                if (i < LW_ROWS * L) { const int r = i / L; sx[r * LP + (i - r * L)] = i < nr * L ? v : 0.f; }
-            }
-        }
-        if (threadIdx.x < LW_ROWS) sx[threadIdx.x * LP + L] = threadIdx.x < nr ? 1.f : 0.f;
-        __syncthreads();
-#pragma unroll 8
-        for (int r = 0; r < LW_ROWS; ++r) {
-            const float gv = sg[r * LW_JT + jj];
-            const float* xr = sx + r * LP;
-#pragma unroll
-            for (int i = 0; i < LW_KMAX; ++i) {
-                const int k = min(kq + 32 * i, L);           // clamped: column L is the ones column
-                acc[i] = fmaf(gv, xr[k], acc[i]);
-            }
-        }
-        __syncthreads();
-    }
-    const int jrow = j0 + jj;
-    if (jrow >= 4 * L) return;
-    float* out = gblk + l * (8l * L * L + 8l * L);
-#pragma unroll
-    for (int i = 0; i < LW_KMAX; ++i) {
-        const int k = kq + 32 * i;
-        if (k > L) continue;
-        float* dst = k < L ? out + (hh ? 4l * L * L : 0) + (long)jrow * L + k : out + 8l * L * L + (hh ? 4 * L : 0) + jrow;
-        *dst = accumulate ? *dst + acc[i] : acc[i];
-    }
-}
-
 // Weight gradients on the f32 matrix cores (v_mfma_f32_16x16x4_f32: an exact f32 fma chain).  One workgroup per
 // 16 x 16 tile of one (stack, layer, ih|hh) gradient [4L gate rows][L inputs + bias column]; its four waves take a
 // quarter of the S*T rows each, operands straight from global memory in MFMA layout (a lane's loads are all
-// independent: one batch per 16 rows), partial tiles meet in LDS in wave order.  The LDS-tiled kernel above spends
-// ~20 us on this at the bench shape (256 rows): it is all latency, and this form has a tenth of the dependent steps.
+// independent: one batch per 16 rows), partial tiles meet in LDS in wave order.  The LDS-tiled scalar kernel this
+// replaced spent ~20 us at the bench shape (256 rows): it is all latency, and this form has a tenth of the dependent steps.
 __global__ __launch_bounds__(256) void lstm_wgrad_mfma_k(const float* __restrict__ dG, const float* __restrict__ hs_all,
                                                          const float* __restrict__ hprev, float* __restrict__ gblk,
                                                          const float* __restrict__ dG2, const float* __restrict__ hs_all2,
                                                          const float* __restrict__ hprev2, float* __restrict__ gblk2,
                                                          int S, int T, int L, int layers, int accumulate) {
-    typedef __attribute__((ext_vector_type(4))) float f32x4_t;
     RBVAE_RAISE_PRIO();
     __shared__ float part[4][256];
     int l = blockIdx.z;
@@ -1728,12 +1607,8 @@ static int lstm_fwd_impl(const float* wblk, const float* wT, float* hs_all, floa
         RBVAE_CHECK_LAUNCH("lstm_fwd_big");
         return RBVAE_OK;
     }
-    if (L <= 32)
-        hipLaunchKernelGGL(lstm_fwd_k<32>, dim3(S), dim3(threads), lds, st, wblk, hs_all, hprev, acts, cs, S, T, L, layers);
-    else if (L <= 64)
-        hipLaunchKernelGGL(lstm_fwd_k<64>, dim3(S), dim3(threads), lds, st, wblk, hs_all, hprev, acts, cs, S, T, L, layers);
-    else
-        hipLaunchKernelGGL(lstm_fwd_k<0>, dim3(S), dim3(threads), lds, st, wblk, hs_all, hprev, acts, cs, S, T, L, layers);
+    // L <= 32 past the wavefront kernel's LDS or thread budget: layer by layer, a gate row's weights in LMAX registers
+    hipLaunchKernelGGL(lstm_fwd_k<32>, dim3(S), dim3(threads), lds, st, wblk, hs_all, hprev, acts, cs, S, T, L, layers);
     RBVAE_CHECK_LAUNCH("lstm_fwd");
     return RBVAE_OK;
 }
@@ -1843,12 +1718,8 @@ static int lstm_bwd_impl(const float* wblk, const float* wT, const float* acts, 
         RBVAE_CHECK_LAUNCH("lstm_bwd_big");
         return RBVAE_OK;
     }
-    if (L <= 32)
-        hipLaunchKernelGGL(lstm_bwd_k<32>, dim3(S), dim3(threads), lds, st, wblk, acts, cs, g_top, dG, dx, S, T, L, layers);
-    else if (L <= 64)
-        hipLaunchKernelGGL(lstm_bwd_k<64>, dim3(S), dim3(threads), lds, st, wblk, acts, cs, g_top, dG, dx, S, T, L, layers);
-    else
-        hipLaunchKernelGGL(lstm_bwd_k<0>, dim3(S), dim3(threads), lds, st, wblk, acts, cs, g_top, dG, dx, S, T, L, layers);
+    // L <= 32 past the wavefront kernel's range (as lstm_fwd_impl)
+    hipLaunchKernelGGL(lstm_bwd_k<32>, dim3(S), dim3(threads), lds, st, wblk, acts, cs, g_top, dG, dx, S, T, L, layers);
     RBVAE_CHECK_LAUNCH("lstm_bwd");
     return RBVAE_OK;
 }
@@ -1930,27 +1801,10 @@ int rbvae_lstm_pair_bwd(const float* wblk_enc, const float* wblk_dec, const floa
 static int launch_lstm_wgrad(const float* dG, const float* hs_all, const float* hprev, float* gblk, const float* dG2,
                              const float* hs_all2, const float* hprev2, float* gblk2, int S, int T, int L, int layers,
                              int accumulate, void* stream) {
-    constexpr int use_mfma = 1;
-    if (use_mfma) {
-        dim3 mgrid(cdiv(4 * L, 16) * cdiv(L + 1, 16), 2, dG2 ? 2 * layers : layers);
-        hipLaunchKernelGGL(lstm_wgrad_mfma_k, mgrid, dim3(256), 0, (hipStream_t)stream, dG, hs_all, hprev, gblk, dG2,
-                           hs_all2, hprev2, gblk2, S, T, L, layers, accumulate);
-        RBVAE_CHECK_LAUNCH("lstm_wgrad_mfma");
-        return RBVAE_OK;
-    }
-    dim3 grid(cdiv(4 * L, LW_JT), 2, dG2 ? 2 * layers : layers);
-    const size_t lds = (size_t)(LW_ROWS * LW_JT + LW_ROWS * (L + 1)) * sizeof(float);
-    RBVAE_CHECK_ARG(lds <= 64 * 1024, "lstm_wgrad: L=%d too large", L);
-    if (L <= 32)
-        hipLaunchKernelGGL(lstm_wgrad_tiled_k<2>, grid, dim3(256), lds, (hipStream_t)stream, dG, hs_all, hprev, gblk, dG2,
-                           hs_all2, hprev2, gblk2, S, T, L, layers, accumulate);
-    else if (L <= 64)
-        hipLaunchKernelGGL(lstm_wgrad_tiled_k<3>, grid, dim3(256), lds, (hipStream_t)stream, dG, hs_all, hprev, gblk, dG2,
-                           hs_all2, hprev2, gblk2, S, T, L, layers, accumulate);
-    else
-        hipLaunchKernelGGL(lstm_wgrad_tiled_k<5>, grid, dim3(256), lds, (hipStream_t)stream, dG, hs_all, hprev, gblk, dG2,
-                           hs_all2, hprev2, gblk2, S, T, L, layers, accumulate);
-    RBVAE_CHECK_LAUNCH("lstm_wgrad");
+    dim3 mgrid(cdiv(4 * L, 16) * cdiv(L + 1, 16), 2, dG2 ? 2 * layers : layers);
+    hipLaunchKernelGGL(lstm_wgrad_mfma_k, mgrid, dim3(256), 0, (hipStream_t)stream, dG, hs_all, hprev, gblk, dG2,
+                       hs_all2, hprev2, gblk2, S, T, L, layers, accumulate);
+    RBVAE_CHECK_LAUNCH("lstm_wgrad_mfma");
     return RBVAE_OK;
 }
 

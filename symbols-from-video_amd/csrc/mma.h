@@ -1,0 +1,117 @@
+// Shared device helpers of the matrix-core kernels (gfx950 only): vector types, the LDS-DMA wrapper, the LDS-only and
+// counted-vmcnt barriers, DPP row sums, static_for, the MFMA dispatch, the transposing-read swizzle, the ReLU-gate test
+// and the frame map.  Everything is __forceinline__: a kernel that takes a helper from here compiles to the code it had
+// with a private copy (tools/isa_diff.py proves it).  New kernels take these; they do not copy them.
+#pragma once
+#include "common.h"
+#include <type_traits>
+
+namespace rbvae {
+
+typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
+typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+
+// LDS-DMA: 16 bytes per lane from global memory straight into LDS (counted by vmcnt)
+__device__ __forceinline__ void glds16(const void* g, void* lds) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+}
+
+// workgroup barrier that orders LDS traffic only.  __syncthreads() also waits vmcnt(0): behind global stores or LDS-DMA in
+// flight every barrier then costs a full memory round trip.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Counted waits in front of the workgroup barrier: all but the N youngest vector-memory operations of THIS wave (the
+// LDS-DMA of the slice about to be read) have landed; no vmcnt(0) drain, so younger slices stay in flight across the barrier.
+// Two forms; the question is whether the wave's OWN LDS writes must have landed before the barrier:
+//   wait_vm_barrier       no: everything the other waves will read arrived by LDS-DMA, which vmcnt counts
+//                         (attn_flash_db_k, conv_s2_k, wgrad_row_k, wgrad_halo_k: no ds_write feeds another wave);
+//   wait_vm_lgkm_barrier  yes: the wave also filled LDS with ds_write (register-staged patches, gather-index and row
+//                         tables), which lgkmcnt counts, not vmcnt.
+// An existing kernel keeps the form it was measured and ISA-checked with.
+template <int N> __device__ __forceinline__ void wait_vm_barrier() {
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_vm_lgkm_barrier() {
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+
+template <int CTRL> __device__ __forceinline__ float dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+// sum over the 16 lanes of a DPP row (lane & 15), every lane gets the total
+__device__ __forceinline__ float row_sum(float v) {
+    v += dpp<0x128>(v);     // row_ror:8
+    v += dpp<0x124>(v);     // row_ror:4
+    v += dpp<0x4E>(v);      // quad_perm [2,3,0,1]
+    v += dpp<0xB1>(v);      // quad_perm [1,0,3,2]
+    return v;
+}
+
+// f(integral_constant<int, I>{}) for I in [I, N): a loop whose index is a constant expression in the body
+template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
+
+// acc += rowop x colop over one 16-byte fragment per lane of both operands
+template <typename T> struct Mma;
+template <> struct Mma<bf16_t> {
+    // one 128-B LDS row slice = 64 k: two 32-k MFMAs, lane group g reads chunk 4*kk+g
+    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& rowop, const u32x4_t& colop) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&rowop, *(const bf16x8_t*)&colop, acc,
+                                                      0, 0, 0);
+    }
+};
+template <> struct Mma<float> {
+    // 32 k per row slice; lane group g holds k = 16*kk + 4*g + c for MFMA c (same on both operands)
+    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& rowop, const u32x4_t& colop) {
+        const f32x4_t r = *(const f32x4_t*)&rowop, c = *(const f32x4_t*)&colop;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(r[q], c[q], acc, 0, 0, 0);
+    }
+};
+
+// XOR applied to the 16-B chunk index of an LDS image row (RB bytes per row) so that the transposed
+// reads of a 32-lane half (rows {q, 8+q} or {4+q, 12+q}) hit distinct banks.
+template <int RB> __device__ __forceinline__ int tr_swz(int row) {
+    if constexpr (RB >= 256) return ((row & 3) | (((row >> 3) & 1) << 2)) << 1;   // 8 chunk pairs
+    else return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1;                // 128-B rows: 4 pairs
+}
+
+// ReLU gate: element e of a stored activation is > 0 (NaN excluded)
+template <typename T> __device__ __forceinline__ bool elem_pos(const unsigned char* p, int e);
+template <> __device__ __forceinline__ bool elem_pos<float>(const unsigned char* p, int e) {
+    return ((const float*)p)[e] > 0.f;
+}
+template <> __device__ __forceinline__ bool elem_pos<bf16_t>(const unsigned char* p, int e) {
+    const bf16_t v = ((const bf16_t*)p)[e];
+    return (v & 0x8000u) == 0 && (v & 0x7fffu) != 0 && (v & 0x7fffu) <= 0x7f80u;
+}
+
+// Frame n of a batch -> element offset of its first value.  d1 == 0: n * s2.  Otherwise n is read as the
+// mixed-radix number (n / d1, (n % d1) / d2, n % d2) with strides (s0, s1, s2): the fused trainer runs both
+// views of an item batch [B][2][T] as frames v*(B*T) + b*T + t without first copying them into that order.
+struct FrameMap {
+    int d1, d2;
+    long s0, s1, s2;
+};
+template <typename I> __device__ __forceinline__ I frame_off(const FrameMap& f, I n) {
+    if (f.d1 == 0) return n * (I)f.s2;
+    const I a = n / (I)f.d1, r = n - a * (I)f.d1;
+    const I b = r / (I)f.d2, c = r - b * (I)f.d2;
+    return a * (I)f.s0 + b * (I)f.s1 + c * (I)f.s2;
+}
+// the same offset with the divisions in 32 bits and the products in 64 (the fused end kernels: one frame per workgroup)
+__device__ __forceinline__ long frame_off_u32(const FrameMap& f, unsigned n) {
+    if (f.d1 == 0) return (long)n * f.s2;
+    const unsigned a = n / (unsigned)f.d1, r = n - a * (unsigned)f.d1;
+    const unsigned b = r / (unsigned)f.d2, c = r - b * (unsigned)f.d2;
+    return (long)a * f.s0 + (long)b * f.s1 + (long)c * f.s2;
+}
+
+}  // namespace rbvae

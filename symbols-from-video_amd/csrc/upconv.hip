@@ -45,10 +45,6 @@ template <typename T> constexpr int uc_lds_main() {
     return ring > epi ? ring : epi;
 }
 
-template <int N> __device__ __forceinline__ void uc_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
 template <typename T>
 __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     constexpr int ES = sizeof(T);
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
         const unsigned char* src = wtile + ((size_t)j * p.Kc) * ES + (size_t)kc * 128;
         unsigned char* lb = smem + A_BYTES + j * CH_BBYTES + (w * LOADS) * 1024;
 #pragma unroll
-        for (int i = 0; i < LOADS; ++i) ch_glds16(src + blane[i], lb + i * 1024);
+        for (int i = 0; i < LOADS; ++i) glds16(src + blane[i], lb + i * 1024);
     };
 
     // ---- fragment addresses: the class shifts every patch read by (p, q), a tap by its constant (th, tw)
@@ -200,7 +196,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) ChMma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
+            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
     };
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     b_issue(0, std::integral_constant<int, 3>{});
     a_landed(std::integral_constant<int, 0>{}, areg);
     a_write(0);
-    uc_wait_barrier<0>();
+    wait_vm_lgkm_barrier<0>();
     u32x4_t fa0[MT], fb0[NTW], fa1[MT], fb1[NTW];
     set_slice(0);
     read_half(K0{}, K0{}, fa0, fb0);
@@ -230,7 +226,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     // slice follows the barrier.
     auto slice = [&](int kc, auto more_tag) {
         constexpr bool more = decltype(more_tag)::value;       // another slice follows (the last slice is its own instance)
-        ch_static_for<0, UC_TAPS>([&](auto j_tag) {
+        static_for<0, UC_TAPS>([&](auto j_tag) {
             constexpr int j = decltype(j_tag)::value;
             constexpr int nj = (j + 1) % UC_TAPS;            // tap of the next step
             using NJ = std::integral_constant<int, nj>;
@@ -249,15 +245,15 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
                         a_landed(std::integral_constant<int, 2 * LOADS>{}, areg);
                         a_write((kc + 1) & 1);
                     }
-                    if constexpr (j == 1 || j == 2) uc_wait_barrier<2 * LOADS + CH_NA>();
-                    else uc_wait_barrier<2 * LOADS>();
+                    if constexpr (j == 1 || j == 2) wait_vm_lgkm_barrier<2 * LOADS + CH_NA>();
+                    else wait_vm_lgkm_barrier<2 * LOADS>();
                     b_issue(kc + 1, j_tag);
                     if constexpr (j == 0) a_load(kc + 1);
                 } else {
                     // the last slice issues nothing: tiles j+1 .. 3 are all that is in flight
-                    if constexpr (j == 0) uc_wait_barrier<2 * LOADS>();
-                    else if constexpr (j == 1) uc_wait_barrier<LOADS>();
-                    else uc_wait_barrier<0>();
+                    if constexpr (j == 0) wait_vm_lgkm_barrier<2 * LOADS>();
+                    else if constexpr (j == 1) wait_vm_lgkm_barrier<LOADS>();
+                    else wait_vm_lgkm_barrier<0>();
                 }
                 if constexpr (nj == 0) set_slice(kc + 1);
                 read_half(NJ{}, K0{}, fa0, fb0);
@@ -300,7 +296,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
             }
         }
     }
-    ch_lds_barrier();
+    lds_barrier();
 
     // ---- store phase: whole 16-B chunks of NHWC rows (+ addend) to the class's stride-2 output pixels; one pixel's 128
     // channels are one contiguous run of 128 * ES bytes

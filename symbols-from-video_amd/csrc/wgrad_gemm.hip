@@ -14,15 +14,10 @@
 // (ROLES: waves 8-11 issue the LDS-DMA, waves 0-7 only multiply; see the kernel).  grid = (co tiles, ci tiles, taps * ksplit); each
 // K-slice writes its own f32 slab (summed later in a fixed order by
 // rbvae_permute_reduce, so gradients are bitwise reproducible -- no float atomics).
-#include "common.h"
+#include "mma.h"
 #include <type_traits>
-#include <utility>
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 struct WgArgs {
     const unsigned char* Dy;   // [P][ldy] T
@@ -35,18 +30,6 @@ struct WgArgs {
     int xcd_order;             // 1: workgroup id -> (K-slice, tile) so that one XCD's workgroups cover <= 2 K-slices
     unsigned long long* stamps;   // -DWG_STAMPS=1 builds only (rbvae_dbg_wg_stamps): [workgroup][8] phase stamps, 100 MHz
 };
-
-__device__ __forceinline__ void glds16w(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-// XOR applied to the 16-B chunk index of an LDS image row so that the transposed
-// reads of a 32-lane half (rows {q, 8+q} or {4+q, 12+q}) hit distinct banks.
-template <int RB> __device__ __forceinline__ int tr_swz(int row) {
-    if constexpr (RB >= 256) return ((row & 3) | (((row >> 3) & 1) << 2)) << 1;   // 8 chunk pairs
-    else return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1;                // 128-B rows: 4 pairs
-}
 
 // Measured and not kept (round 2, same-GPU A/B of the bench step; the variants are gone from the source): scheduling barriers
 // around the MFMA groups 0.735 vs 0.74 us per K step, the two waves of a SIMD staging at different points of the step, the
@@ -66,14 +49,6 @@ template <int RB> __device__ __forceinline__ int tr_swz(int row) {
 
 constexpr int WG_BM = 128;      // co per workgroup
 constexpr int WG_MAXP = 4096;   // pixels of one K-slice (their gather indices live in LDS)
-
-template <class F, int... Ks> __device__ __forceinline__ void wg_static_for(F&& f, std::integer_sequence<int, Ks...>) {
-    (f(std::integral_constant<int, Ks>{}), ...);
-}
-
-template <int N> __device__ __forceinline__ void wg_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // 8 waves as 2 (co) x 4 (ci); a wave owns 64 co x 16*NT ci; BN = 64*NT ci per workgroup.
 // WG_NS = LDS ring depth.  3: two K steps in flight behind the one being multiplied, one workgroup per CU;
@@ -196,7 +171,7 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
 #pragma unroll
                 for (int j = 0; j < PA; ++j) {
                     const bool v = a_cval[j] && base + a_row[j] < npix;
-                    glds16w(v ? acur[j] : p.zero, la + j * 4096);
+                    glds16(v ? acur[j] : p.zero, la + j * 4096);
                     acur[j] += a_stride;
                 }
                 unsigned char* lb = la + A_BYTES;
@@ -206,7 +181,7 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
 #pragma unroll
                 for (int j = 0; j < PB; ++j) {
                     const bool v = b_cval[j] && src[j] >= 0;
-                    glds16w(v ? bbase[j] + (size_t)src[j] * ldi_b : p.zero, lb + j * 4096);
+                    glds16(v ? bbase[j] + (size_t)src[j] * ldi_b : p.zero, lb + j * 4096);
                 }
                 ++pstep;
                 pbuf = (pbuf + 1 == WG_NS) ? 0 : pbuf + 1;
@@ -216,10 +191,10 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
 #pragma unroll
             for (int i = 0; i < WG_NS - 1; ++i)
                 if (i < nsteps) stage();
-            if (nsteps >= WG_NS - 1) wg_wait_barrier<(WG_NS - 2) * PP>(); else wg_wait_barrier<0>();
+            if (nsteps >= WG_NS - 1) wait_vm_lgkm_barrier<(WG_NS - 2) * PP>(); else wait_vm_lgkm_barrier<0>();
             if (WG_NS - 1 < nsteps) stage();
             for (int s = 0; s + 1 < nsteps; ++s) {
-                if (nsteps - s - 2 >= WG_NS - 2) wg_wait_barrier<(WG_NS - 2) * PP>(); else wg_wait_barrier<0>();
+                if (nsteps - s - 2 >= WG_NS - 2) wait_vm_lgkm_barrier<(WG_NS - 2) * PP>(); else wait_vm_lgkm_barrier<0>();
                 if (s + WG_NS < nsteps) stage();
             }
             return;
@@ -264,7 +239,7 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
 #pragma unroll
         for (int i = 0; i < A_INSTR; ++i) {
             const bool v = a_cval[i] && base + a_row[i] < npix;
-            glds16w(v ? acur[i] : p.zero, la + i * 1024);
+            glds16(v ? acur[i] : p.zero, la + i * 1024);
             acur[i] += a_stride;
         }
         if (b_wave) {
@@ -273,7 +248,7 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
             for (int i = 0; i < B_INSTR; ++i) {
                 const int src = s_idx[base + b_row[i]];
                 const bool v = b_cval[i] && src >= 0;
-                glds16w(v ? bbase[i] + (size_t)src * ldi_b : p.zero, lb + i * 1024);
+                glds16(v ? bbase[i] + (size_t)src * ldi_b : p.zero, lb + i * 1024);
             }
         }
         ++pstep;
@@ -317,10 +292,10 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
     auto wait_stage = [&](int younger_ok) {
         if (younger_ok) {
             // WG_NS-2 younger stages stay in flight; the immediate must match this wave's own load count
-            if (my_loads == A_INSTR + B_INSTR) wg_wait_barrier<(WG_NS - 2) * (A_INSTR + B_INSTR)>();
-            else wg_wait_barrier<(WG_NS - 2) * A_INSTR>();
+            if (my_loads == A_INSTR + B_INSTR) wait_vm_lgkm_barrier<(WG_NS - 2) * (A_INSTR + B_INSTR)>();
+            else wait_vm_lgkm_barrier<(WG_NS - 2) * A_INSTR>();
         } else {
-            wg_wait_barrier<0>();       // tail: drain (conservative)
+            wait_vm_lgkm_barrier<0>();       // tail: drain (conservative)
         }
     };
     if constexpr (ES == 2) {

@@ -25,7 +25,7 @@
 // Workgroup -> (tile, K-slice): XCD x (= workgroup id % 8) takes the K-slices x, x + 8, .. with all their channel tiles, so
 // the 16 tile workgroups of a 256 x 256 layer that walk the same pixels share them in ONE L2.
 // Each K-slice writes its own f32 slab [a][t][b] (rbvae_wgrad_gemm's layout: the same fixed-order reduction jobs follow).
-#include "common.h"
+#include "mma.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -37,10 +37,6 @@
 #endif
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short wh_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short wh_s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float wh_f32x4_t;
 
 struct WhArgs {
     const unsigned char* S;    // [Nimg*OH*OW][lds] bf16
@@ -60,19 +56,8 @@ constexpr int WH_RING = 4;
 constexpr int WH_DI = (WH_STAGE / 1024) / 8;                         // LDS-DMA instructions per wave and stage: 4
 constexpr int WH_UNITS = 5;                                          // (tap, b sub-tile) units per wave: taps w/4 + 2j, sub-tile w % 4
 
-__device__ __forceinline__ void wh_glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-__device__ __forceinline__ int wh_swz_s(int row) {      // tr_swz<128> of wgrad_gemm.hip
-    return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1;
-}
 __device__ __forceinline__ int wh_swz_g(int slot) { return ((slot >> 1) & 3) << 1; }
 __device__ __forceinline__ int wh_plane(int ph, int pw) { return ph ? (pw ? WH_P11 : WH_P10) : (pw ? WH_P01 : WH_P00); }
-
-template <int N> __device__ __forceinline__ void wh_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -97,7 +82,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
         if (s_wave) {
             const int k = 8 * j + (lane >> 3);                     // row of the S tile: (rr = j, cc = lane / 8)
             d_r[j] = j; d_c[j] = lane >> 3;
-            d_off[j] = (((lane & 7) ^ wh_swz_s(k)) * 16) + a0 * 2;
+            d_off[j] = (((lane & 7) ^ tr_swz<128>(k)) * 16) + a0 * 2;
         } else {
             const int slot = 8 * (4 * w + j - 4) + (lane >> 3);
             int ph, pw, rem;
@@ -129,7 +114,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
             const bool v = (unsigned)r < (unsigned)d_H && (unsigned)c < (unsigned)d_W;
             const unsigned char* src = d_base + ((size_t)(n * d_H + r) * d_W + c) * d_ld + d_off[j];
 #if WH_ABL != 1
-            if (d_r[j] > -100) wh_glds16(v ? src : p.zero, ld + j * 1024);     // slots no tap reads stay unfilled
+            if (d_r[j] > -100) glds16(v ? src : p.zero, ld + j * 1024);     // slots no tap reads stay unfilled
 #endif
         }
     };
@@ -143,7 +128,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
         const int row = 8 * fg + q;                      // + 4 for the second read
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-            const int chunk = (mt * 2 + (pp >> 1)) ^ wh_swz_s(row);
+            const int chunk = (mt * 2 + (pp >> 1)) ^ tr_swz<128>(row);
             offA[mt] = row * 128 + chunk * 16 + (pp & 1) * 8;
         }
     }
@@ -157,15 +142,15 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
     }
     const bool unit4 = th == 0;          // waves 4-7 have no fifth tap: its reads are issued (uniform wait counts), its MFMAs are not
 
-    wh_f32x4_t acc[WH_UNITS][4];
+    f32x4_t acc[WH_UNITS][4];
 #pragma unroll
     for (int j = 0; j < WH_UNITS; ++j)
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[j][mt] = wh_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < 4; ++mt) acc[j][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     // the 8 + 10 transposing reads of one block
-    auto read_frags = [&](int step, wh_s16x4_t (&al)[4], wh_s16x4_t (&ah)[4], wh_s16x4_t (&bl)[WH_UNITS], wh_s16x4_t (&bh)[WH_UNITS]) {
+    auto read_frags = [&](int step, s16x4_t (&al)[4], s16x4_t (&ah)[4], s16x4_t (&bl)[WH_UNITS], s16x4_t (&bh)[WH_UNITS]) {
         const unsigned lb = lds0 + (step & (WH_RING - 1)) * WH_STAGE;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
@@ -182,8 +167,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
     };
     // at most YOUNGER reads (of the next block) outstanding: this block's have landed.  The wait is tied to the registers it
     // guards; the fragments leave as MFMA operands.
-    auto landed = [&](auto younger_tag, wh_s16x4_t (&al)[4], wh_s16x4_t (&ah)[4], wh_s16x4_t (&bl)[WH_UNITS],
-                      wh_s16x4_t (&bh)[WH_UNITS], wh_bf16x8_t (&fa)[4], wh_bf16x8_t (&fb)[WH_UNITS]) {
+    auto landed = [&](auto younger_tag, s16x4_t (&al)[4], s16x4_t (&ah)[4], s16x4_t (&bl)[WH_UNITS],
+                      s16x4_t (&bh)[WH_UNITS], bf16x8_t (&fa)[4], bf16x8_t (&fb)[WH_UNITS]) {
         constexpr int YOUNGER = decltype(younger_tag)::value;
         asm volatile("s_waitcnt lgkmcnt(%18)"
                      : "+v"(al[0]), "+v"(ah[0]), "+v"(al[1]), "+v"(ah[1]), "+v"(al[2]), "+v"(ah[2]), "+v"(al[3]), "+v"(ah[3]),
@@ -192,12 +177,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
                      : "n"(YOUNGER));
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
-            fa[mt] = wh_bf16x8_t{al[mt][0], al[mt][1], al[mt][2], al[mt][3], ah[mt][0], ah[mt][1], ah[mt][2], ah[mt][3]};
+            fa[mt] = bf16x8_t{al[mt][0], al[mt][1], al[mt][2], al[mt][3], ah[mt][0], ah[mt][1], ah[mt][2], ah[mt][3]};
 #pragma unroll
         for (int j = 0; j < WH_UNITS; ++j)
-            fb[j] = wh_bf16x8_t{bl[j][0], bl[j][1], bl[j][2], bl[j][3], bh[j][0], bh[j][1], bh[j][2], bh[j][3]};
+            fb[j] = bf16x8_t{bl[j][0], bl[j][1], bl[j][2], bl[j][3], bh[j][0], bh[j][1], bh[j][2], bh[j][3]};
     };
-    auto mma = [&](const wh_bf16x8_t (&fa)[4], const wh_bf16x8_t (&fb)[WH_UNITS]) {
+    auto mma = [&](const bf16x8_t (&fa)[4], const bf16x8_t (&fb)[WH_UNITS]) {
 #pragma unroll
         for (int j = 0; j < WH_UNITS - 1; ++j)
 #pragma unroll
@@ -212,12 +197,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
 
     if (nsteps > 0) {
         using Y0 = std::integral_constant<int, 0>;
-        wh_s16x4_t xal[4], xah[4], xbl[WH_UNITS], xbh[WH_UNITS], yal[4], yah[4], ybl[WH_UNITS], ybh[WH_UNITS];
-        wh_bf16x8_t fa[4], fb[WH_UNITS];
+        s16x4_t xal[4], xah[4], xbl[WH_UNITS], xbh[WH_UNITS], yal[4], yah[4], ybl[WH_UNITS], ybh[WH_UNITS];
+        bf16x8_t fa[4], fb[WH_UNITS];
         stage(0);
         if (nsteps > 1) stage(1);
         if (nsteps > 2) stage(2);
-        if (nsteps > 2) wh_wait_barrier<2 * WH_DI>(); else if (nsteps > 1) wh_wait_barrier<WH_DI>(); else wh_wait_barrier<0>();
+        if (nsteps > 2) wait_vm_barrier<2 * WH_DI>(); else if (nsteps > 1) wait_vm_barrier<WH_DI>(); else wait_vm_barrier<0>();
         // Four blocks per loop iteration; NOTHING asynchronous crosses the loop's back edge (a fragment register still in
         // flight there is what the compiler copies when it splits a live range: isa_check rejects the listing), so the
         // first block of an iteration reads its own fragments (their latency sits under the barrier wait) and blocks
@@ -227,7 +212,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
         // them it would have to let 18 younger reads pass, which the 4-bit lgkmcnt cannot say.)
         auto sync_and_stage = [&](int s) {
             if (s + 1 < nsteps) {
-                if (s + 2 < nsteps) wh_wait_barrier<WH_DI>(); else wh_wait_barrier<0>();
+                if (s + 2 < nsteps) wait_vm_barrier<WH_DI>(); else wait_vm_barrier<0>();
                 if (s + 3 < nsteps) stage(s + 3);
             }
         };
@@ -276,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             const int a = a0 + mt * 16 + fi, b = b0 + bs * 16 + 4 * fg;
-            *(wh_f32x4_t*)(slab + ((size_t)a * 9 + tap) * p.Cb + b) = acc[j][mt];
+            *(f32x4_t*)(slab + ((size_t)a * 9 + tap) * p.Cb + b) = acc[j][mt];
         }
     }
 }

@@ -34,7 +34,7 @@
 // Workgroup -> (tile, K-slice): XCD x (= workgroup id % 8) takes a contiguous eighth of the (K-slice, tile) items in
 // slice-major order: the 12 tiles of a K-slice share its pixels in that XCD's L2.  Each K-slice writes its own f32 slab [a][t][b] (rbvae_wgrad_gemm's layout: the
 // same fixed-order reduction jobs follow; bitwise reproducible, no float atomics).
-#include "common.h"
+#include "mma.h"
 #include <type_traits>
 
 #ifndef WR_ABL          // timing ablations (results wrong on purpose; RBVAE_ABLATION builds only): 1 no LDS-DMA, 2 no fragment reads / MFMAs, 3 see stage(), 5 no fragment reads, 6 one MFMA wave per SIMD
@@ -49,10 +49,6 @@
 #endif
 
 namespace rbvae {
-
-typedef __attribute__((ext_vector_type(8))) short wr_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short wr_s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float wr_f32x4_t;
 
 struct WrArgs {
     const unsigned char* S;    // [Nimg*OH*OW][lds] bf16
@@ -69,19 +65,10 @@ constexpr int WR_RING = 3;
 constexpr int WR_A_BYTES = 64 * 256;
 constexpr int WR_MAXP = 13;                    // LDS-DMA instructions per producer wave and stage, at most
 
-__device__ __forceinline__ void wr_glds16(const void* g, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-__device__ __forceinline__ int wr_swz_a(int row) { return ((row & 3) | (((row >> 3) & 1) << 2)) << 1; }   // tr_swz<256>
 // chunk-pair swizzle of patch slot (block row rr, slot jj): the eight pixel rows a 32-lane half of a transposing read touches
 // (four consecutive slots of two block rows: rr, rr + 1 for W = 8; rr, rr + 2 for W = 4) get eight distinct values, and the
 // pixels k + 4 / k + 32 of a lane get the SAME value as pixel k (their reads are immediate offsets of one address)
 template <int W> __device__ __forceinline__ int wr_swz_g(int rr, int jj) { return (jj & 3) | ((((W == 8) ? rr : rr >> 1) & 1) << 2); }
-
-template <int N> __device__ __forceinline__ void wr_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 template <int W>
 __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
@@ -134,7 +121,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
                 const int k = 4 * i + (lane >> 4);
                 const int rr = k / W, cc = k % W;
                 d_rr[j] = rr; d_c[j] = cc; d_rm[j] = 0;
-                d_off[j] = (rr * p.OW + cc) * lds_b + (((lane & 15) ^ wr_swz_a(k)) * 16) + a0 * 2;
+                d_off[j] = (rr * p.OW + cc) * lds_b + (((lane & 15) ^ tr_swz<256>(k)) * 16) + a0 * 2;
             } else {
                 const int s = min(4 * (i - 16) + (lane >> 4), NSLOT - 1);
                 const int rr = s / SPR, jj = s - rr * SPR;
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
         // block s: own pieces of stage s landed (stage s + 1's may be in flight) -> barrier: the MFMA waves start on stage s and
         // are past stage s - 1, whose ring slot stage s + 2 takes
         for (int s = 0; s < nsteps; ++s) {
-            if (s + 1 < nsteps) { if (thirteen) wr_wait_barrier<13>(); else wr_wait_barrier<12>(); } else wr_wait_barrier<0>();
+            if (s + 1 < nsteps) { if (thirteen) wait_vm_barrier<13>(); else wait_vm_barrier<12>(); } else wait_vm_barrier<0>();
             if (s + 2 < nsteps) stage();
         }
         return;
@@ -205,7 +192,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
     int offA;                                            // a sub-tile 4 wr; sub-tile 4 wr + mt: chunk index ^ 2 mt = byte address ^ 32 mt
     {
         const int row = 8 * fg + q;                      // + 4 for the second read, + 32 for the second half
-        const int chunk = ((wr * 4) * 2 + (pp >> 1)) ^ wr_swz_a(row);
+        const int chunk = ((wr * 4) * 2 + (pp >> 1)) ^ tr_swz<256>(row);
         offA = row * 256 + chunk * 16 + (pp & 1) * 8;
     }
     int offB[3];                                         // [kw]: pixel k = 8 fg + q of the first half, b sub-tile 2 wc
@@ -218,20 +205,20 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
         offB[kw] = WR_A_BYTES + (rr * SPR + jj) * 256 + chunk * 16 + (pp & 1) * 8;
     }
 
-    wr_f32x4_t acc[3][4][2];
+    f32x4_t acc[3][4][2];
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[kw][mt][nt] = wr_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int nt = 0; nt < 2; ++nt) acc[kw][mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     // Fragment reads are inline asm (invisible to the compiler's wait-count pass); every group is followed by a counted
     // s_waitcnt lgkmcnt tied ("+v") to the registers it guards, and isa_check proves on the listing that nothing touches a
     // register before its wait.
     // reads of the S fragments of a sub-tiles m0, m0 + 1 (4 reads) / of one tap's G fragments (4 reads)
-    auto read_a2 = [&](unsigned lb, auto ksub_tag, auto m0_tag, wr_s16x4_t (&al)[4], wr_s16x4_t (&ah)[4]) {
+    auto read_a2 = [&](unsigned lb, auto ksub_tag, auto m0_tag, s16x4_t (&al)[4], s16x4_t (&ah)[4]) {
         constexpr int KS_ = decltype(ksub_tag)::value, M0 = decltype(m0_tag)::value;
 #pragma unroll
         for (int mt = M0; mt < M0 + 2; ++mt) {
@@ -243,7 +230,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
             asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(ah[mt]) : "v"(ad), "n"(KS_ * 32 * 256 + 4 * 256));
         }
     };
-    auto read_b = [&](unsigned lb, auto ksub_tag, int kw, wr_s16x4_t (&bl)[2], wr_s16x4_t (&bh)[2]) {
+    auto read_b = [&](unsigned lb, auto ksub_tag, int kw, s16x4_t (&bl)[2], s16x4_t (&bh)[2]) {
         constexpr int KS_ = decltype(ksub_tag)::value;
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -256,30 +243,30 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
         }
     };
     // counted waits tied to the registers they guard: at most Y younger reads stay outstanding
-    auto wait_b = [&](auto y_tag, wr_s16x4_t (&bl)[2], wr_s16x4_t (&bh)[2]) {
+    auto wait_b = [&](auto y_tag, s16x4_t (&bl)[2], s16x4_t (&bh)[2]) {
         constexpr int Y = decltype(y_tag)::value;
         asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(bl[0]), "+v"(bh[0]), "+v"(bl[1]), "+v"(bh[1]) : "n"(Y));
     };
-    auto wait_a2 = [&](auto y_tag, auto m0_tag, wr_s16x4_t (&al)[4], wr_s16x4_t (&ah)[4]) {
+    auto wait_a2 = [&](auto y_tag, auto m0_tag, s16x4_t (&al)[4], s16x4_t (&ah)[4]) {
         constexpr int Y = decltype(y_tag)::value, M0 = decltype(m0_tag)::value;
         asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(al[M0]), "+v"(ah[M0]), "+v"(al[M0 + 1]), "+v"(ah[M0 + 1]) : "n"(Y));
     };
-    auto wait_a2b = [&](auto y_tag, auto m0_tag, wr_s16x4_t (&al)[4], wr_s16x4_t (&ah)[4], wr_s16x4_t (&bl)[2], wr_s16x4_t (&bh)[2]) {
+    auto wait_a2b = [&](auto y_tag, auto m0_tag, s16x4_t (&al)[4], s16x4_t (&ah)[4], s16x4_t (&bl)[2], s16x4_t (&bh)[2]) {
         constexpr int Y = decltype(y_tag)::value, M0 = decltype(m0_tag)::value;
         asm volatile("s_waitcnt lgkmcnt(%8)"
                      : "+v"(al[M0]), "+v"(ah[M0]), "+v"(al[M0 + 1]), "+v"(ah[M0 + 1]), "+v"(bl[0]), "+v"(bh[0]), "+v"(bl[1]), "+v"(bh[1])
                      : "n"(Y));
     };
     // the MFMAs of tap kw on a sub-tiles m0 .. m0 + NM - 1 (fragments that have passed their wait)
-    auto mma = [&](int kw, auto m0_tag, auto nm_tag, const wr_s16x4_t (&al)[4], const wr_s16x4_t (&ah)[4], const wr_s16x4_t (&bl)[2],
-                   const wr_s16x4_t (&bh)[2]) {
+    auto mma = [&](int kw, auto m0_tag, auto nm_tag, const s16x4_t (&al)[4], const s16x4_t (&ah)[4], const s16x4_t (&bl)[2],
+                   const s16x4_t (&bh)[2]) {
         constexpr int M0 = decltype(m0_tag)::value, NM = decltype(nm_tag)::value;
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            const wr_bf16x8_t fb = {bl[nt][0], bl[nt][1], bl[nt][2], bl[nt][3], bh[nt][0], bh[nt][1], bh[nt][2], bh[nt][3]};
+            const bf16x8_t fb = {bl[nt][0], bl[nt][1], bl[nt][2], bl[nt][3], bh[nt][0], bh[nt][1], bh[nt][2], bh[nt][3]};
 #pragma unroll
             for (int mt = M0; mt < M0 + NM; ++mt) {
-                const wr_bf16x8_t fa = {al[mt][0], al[mt][1], al[mt][2], al[mt][3], ah[mt][0], ah[mt][1], ah[mt][2], ah[mt][3]};
+                const bf16x8_t fa = {al[mt][0], al[mt][1], al[mt][2], al[mt][3], ah[mt][0], ah[mt][1], ah[mt][2], ah[mt][3]};
                 acc[kw][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb, fa, acc[kw][mt][nt], 0, 0, 0);
             }
         }
@@ -295,11 +282,11 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
 
 #define WR_SB() __builtin_amdgcn_sched_barrier(0)
     if (nsteps > 0) {
-        wr_s16x4_t a0l[4], a0h[4], a1l[4], a1h[4], xbl[2], xbh[2], ybl[2], ybh[2], zbl[2], zbh[2];
+        s16x4_t a0l[4], a0h[4], a1l[4], a1h[4], xbl[2], xbh[2], ybl[2], ybh[2], zbl[2], zbh[2];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a1l[i] = a1h[i] = wr_s16x4_t{0, 0, 0, 0};
+        for (int i = 0; i < 4; ++i) a1l[i] = a1h[i] = s16x4_t{0, 0, 0, 0};
 #pragma unroll
-        for (int i = 0; i < 2; ++i) zbl[i] = zbh[i] = wr_s16x4_t{0, 0, 0, 0};
+        for (int i = 0; i < 2; ++i) zbl[i] = zbh[i] = s16x4_t{0, 0, 0, 0};
         unsigned lb = lds0;
         // Block s: barrier (stage s landed: the producer waves waited for their pieces in front of it).  Six (half, tap) units
         // of 8 MFMAs: u0..u2 = taps 0..2 on the first 32 pixels (S fragments a0), u3..u5 on the second (a1); G fragments
@@ -369,7 +356,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const int b = b0 + (wc * 2 + nt) * 16 + 4 * fg;
-                *(wr_f32x4_t*)(slab + ((size_t)a * 9 + kh * 3 + kw) * p.Cb + b) = acc[kw][mt][nt];
+                *(f32x4_t*)(slab + ((size_t)a * 9 + kh * 3 + kw) * p.Cb + b) = acc[kw][mt][nt];
             }
         }
 #if WR_STAMPS

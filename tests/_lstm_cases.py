@@ -158,7 +158,7 @@ def pair_bwd_dispatch(T, L, layers, unit_threads=1):
 
 
 def wgrad_dispatch(pair=False, accumulate=0):
-    """launch_lstm_wgrad: use_mfma is a constexpr 1."""
+    """launch_lstm_wgrad: one kernel, launched over one stack or a pair of stacks."""
     return f"lstm_wgrad_mfma_k[{'pair' if pair else 'single'},accumulate={int(bool(accumulate))}]"
 
 
@@ -170,16 +170,6 @@ REACHABLE = (
     + ["lstm_pair_fwd_unit_k", "lstm_pair_fwd_k<32,true>", "lstm_pair_fwd_k<32,false,28>", "lstm_pair_fwd_k<32,false>"]
     + ["lstm_pair_bwd_unit_k", "lstm_pair_bwd_k<32,true>", "lstm_pair_bwd_k<32,false>"]
     + [wgrad_dispatch(p, a) for p in (False, True) for a in (0, 1)])
-
-# Instances in csrc/lstm.hip that no argument of the entry points reaches (not tested; removing them is separate work)
-UNREACHABLE = {
-    "lstm_fwd_k<64>": "L > 32 always takes lstm_fwd_big_k (or is refused with 'T too long') before the L <= 64 branch",
-    "lstm_fwd_k<0>": "as lstm_fwd_k<64>: the branch for L > 64 sits behind the L > 32 return",
-    "lstm_bwd_k<64>": "L > 32 always takes lstm_bwd_big_k (or is refused) before the L <= 64 branch",
-    "lstm_bwd_k<0>": "as lstm_bwd_k<64>",
-    "lstm_wgrad_k": "never launched: launch_lstm_wgrad only knows the MFMA and the tiled kernel",
-    "lstm_wgrad_tiled_k": "behind `constexpr int use_mfma = 1` in launch_lstm_wgrad",
-}
 
 
 def first_change(fn, Tmax=4096):
