@@ -669,6 +669,58 @@ int rbvae_probe_finish_parts(long P);
 int rbvae_probe_finish(const double* sums, long P, int m, double* r2, double* evs, double* part, double* metrics,
                        int* n_constant, void* stream);
 
+/* ---- latent-space projections (csrc/project.hip) --------------------------------------------------------
+ * scripts/evaluation/clustering_eval/embedding_umap.py: the soft latents of the test frames (:214, :224) projected to 2-D
+ * by PCA (:111-112), t-SNE (:87-88) and UMAP (:63-64).  PCA and t-SNE run here as scikit-learn 1.7.2 computes them
+ * (DESIGN.md section 7 names the two deliberate differences); of UMAP only the exact neighbour graph it starts from.
+ * Every reduction has a fixed order (no atomics): two runs agree bit for bit.
+ *
+ * rbvae_knn (:63 n_neighbors = 24, :87 perplexity = 30 -> k = 91): the exact k nearest neighbours of every row of
+ * X f32 [N][L], 2 <= N <= 16384 (all N distances of a row sit in LDS as f64), 1 <= L <= 128, 1 <= k <= min(N - 1, 128).
+ * d2 [N][k] = sum_l (x_il - x_jl)^2 in f64, l ascending, each difference exact and each square rounded once; idx [N][k];
+ * row i is never its own neighbour; a row's neighbours are sorted by (d2, j) ascending, ties to the lower index.
+ * X must be finite: the entry point does not look (projection.knn_graph does); where NaN or infinite rows leave a query
+ * fewer than k finite distances, the rest of its row is d2 = inf with idx = 0x7fffffff, and nothing is written elsewhere.
+ * rbvae_knn_ok: 1 when (N, L, k) is covered; anything else makes rbvae_knn return RBVAE_E_INVALID without a launch. */
+int rbvae_knn_ok(int N, int L, int k);
+int rbvae_knn(const float* X, int N, int L, int k, int* idx, double* d2, void* stream);
+/* :87-88 (TSNE.fit_transform -> _joint_probabilities_nn -> sklearn.manifold._utils._binary_search_perplexity): per row,
+ * over the k <= 128 distances d2 [N][k] rounded to f32, the f64 bisection on beta (start 1, doubling / halving until
+ * bracketed, at most 100 entropy evaluations, tolerance (double)1e-5f, a zero sum replaced by (double)1e-8f) towards
+ * entropy log((double)perplexity), 0 < perplexity < k.  P [N][k] the conditional probabilities, beta [N] the value P
+ * was evaluated at, steps [N] the number of entropy evaluations.  One wave per row; the two sums of an evaluation are
+ * butterfly sums over the wave. */
+int rbvae_tsne_perplexity(const double* d2, int N, int k, float perplexity, double* P, double* beta, int* steps,
+                          void* stream);
+/* :88, one gradient iteration of TSNE._tsne (sklearn.manifold._t_sne._gradient_descent over _kl_divergence_bh, with the
+ * exact repulsion that angle = 0 gives) as three launches.  Y f32 [N][2], 8-byte aligned.
+ * rbvae_tsne_repulse: part [splits][N][3] f32 = (R_x, R_y, Z_i) over the j slice s, R_i = sum_{j != i} q^2 (y_i - y_j),
+ * Z_i = sum_{j != i} q, q = 1 / (1 + |y_i - y_j|^2) in f32 (hardware reciprocal), splits = rbvae_tsne_repulse_splits(N).
+ * rbvae_tsne_zsum: Z [1] f64 = the sum of every part[s][i][2] (one workgroup: thread t of 1024 adds the elements t,
+ * t + 1024, ... of the [splits][N] array in ascending order, then a halving tree).
+ * rbvae_tsne_step: the joint P as CSR (indptr int32 [N + 1], indices int32, data f32), sched = device floats
+ * (exaggeration, momentum, learning rate), N >= 2.  Per row, p = exaggeration * data in f32:
+ *   A = sum_e p q (y_i - y_j),  R = sum_s part[s][i] (s ascending),  g = 4 (float)((double)A - (double)R / Z)
+ *   gains = update * g < 0 ? gains + 0.2 : gains * 0.8, at least 0.01;  update = momentum * update - lr * (gains * g)
+ *   Y_out = Y + update (Y_out != Y: rows read their neighbours' old positions)
+ * and stats [rbvae_tsne_step_parts(N)][3] f64 = the workgroup's sums of |g|^2, |gains g|^2 (the vector whose norm
+ * _gradient_descent compares with min_grad_norm) and p log(max(p, FLT_MIN) / max(q / Z, FLT_MIN)) (the error of
+ * _barnes_hut_tsne's compute_gradient_positive). */
+int rbvae_tsne_repulse_splits(int N);
+int rbvae_tsne_repulse(const float* Y, int N, float* part, void* stream);
+int rbvae_tsne_zsum(const float* part, int N, double* Z, void* stream);
+int rbvae_tsne_step_parts(int N);
+int rbvae_tsne_step(const float* Y, float* Y_out, float* update, float* gains, const int* indptr, const int* indices,
+                    const float* data, const float* part, const double* Z, const float* sched, int N, double* stats,
+                    void* stream);
+/* :111-112 (PCA(n_components=2).fit_transform; the covariance_eigh solver): mean f64 [L] = (sum_rows x) / N and
+ * cov f64 [L][L] = sum_rows (x_a - mean_a)(x_b - mean_b) / (N - 1), symmetric by construction, N >= 2, L <= 128; the host
+ * takes the eigenvectors.  rbvae_pca_project: out f64 [N][n_components] = (X - mean) V^T, V f64 [n_components][L],
+ * n_components <= min(L, 8), l ascending. */
+int rbvae_pca_moments(const float* X, int N, int L, double* mean, double* cov, void* stream);
+int rbvae_pca_project(const float* X, int N, int L, const double* mean, const double* V, int n_components, double* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

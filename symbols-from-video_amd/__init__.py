@@ -22,3 +22,6 @@ from .robustness import (adjacent_hamming, most_common_codes, reference_draws, s
                          state_consistency_under)
 from . import probe  # noqa: F401  (probe.split_indices is the probe's train/test split; data.split_indices the trainer's)
 from .probe import ProbeResult, fit_factor, frame_embeddings, frame_probe, linear_probe  # noqa: F401
+from . import projection  # noqa: F401
+from .projection import (PCAResult, TSNEAffinities, TSNEResult, knn_graph, latent_projections, pca_project,  # noqa: F401
+                         tsne_affinities, tsne_project)

@@ -1,0 +1,297 @@
+"""Latent-space projections (the reference's scripts/evaluation/clustering_eval/embedding_umap.py): the soft latents
+model.encode(..., temperature=0.2, hard=False, noise_ratio=0.3) of the frames (:214, :224) projected to 2-D by
+PCA(n_components=2) (:111-112) and TSNE(n_components=2, random_state=42, perplexity=30) (:87-88), on the device
+(csrc/project.hip), as scikit-learn 1.7.2 computes them:
+  knn_graph        the exact k nearest neighbours in f64, sorted by (d2, index): what t-SNE (k = 3 perplexity + 1 = 91) and
+                   UMAP (:63, n_neighbors = 24) both start from
+  tsne_affinities  _binary_search_perplexity on the device; P + P^T, normalised, as one merged CSR on the host, once per fit
+  tsne_project     TSNE._tsne: 250 iterations with momentum 0.5 and P x early_exaggeration, then momentum 0.8, learning rate
+                   max(N / early_exaggeration / 4, 50), gains as _gradient_descent keeps them; every 50 iterations the KL
+                   and the gradient norm come back once, nothing else synchronises
+  pca_project      covariance on the device, numpy.linalg.eigh of the L x L matrix, svd_flip(u_based_decision=False),
+                   projection on the device, all f64
+Two deliberate differences from scikit-learn's defaults: the repulsion is exact (what
+_kl_divergence_bh(angle=0) computes) instead of Barnes-Hut at angle 0.5, and the initial map is this module's exact PCA
+instead of the randomised-SVD PCA seeded by random_state.  UMAP's fuzzy graph and layout are not built: knn_graph(X, 24)
+is the part of it that is pinned.  The plots stay with the caller.
+There is no host path: inputs on the CPU raise.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MAX_COMPONENTS = 8                                  # rbvae_pca_project; rbvae_knn: L <= 128, k <= 128, N <= 16384
+EXPLORATION_ITERS, N_ITER_CHECK = 250, 50           # TSNE._EXPLORATION_MAX_ITER, TSNE._N_ITER_CHECK
+MACHINE_EPSILON = float(np.finfo(np.float64).eps)
+
+
+def _device_matrix(X, name, dtype=torch.float32):
+    if not isinstance(X, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor on the GPU, got {type(X).__name__}")
+    if not X.is_cuda:
+        raise ValueError(f"{name} must be on the GPU (there is no CPU path)")
+    if X.dim() != 2 or X.dtype != dtype:
+        raise ValueError(f"{name} must be a 2-D {dtype} tensor, got {X.dtype} {tuple(X.shape)}")
+    if not X.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return X
+
+
+def knn_graph(X: torch.Tensor, k: int):
+    """rbvae_knn: X f32 [N, L] on the device -> (idx int32 [N, k], d2 f64 [N, k]); row i's k nearest other rows by
+    squared Euclidean distance in f64, sorted by (d2, index) ascending."""
+    X = _device_matrix(X, "X")
+    N, Ld = X.shape
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("X holds NaN or infinite values")
+    idx = torch.empty((N, int(k)), dtype=torch.int32, device=X.device)
+    d2 = torch.empty((N, int(k)), dtype=torch.float64, device=X.device)
+    L.call("rbvae_knn", X, N, Ld, int(k), idx, d2)
+    return idx, d2
+
+
+@dataclasses.dataclass
+class TSNEAffinities:
+    """conditional [N, k] f64, beta [N] f64 and steps [N] int32 from the perplexity search (device); the joint
+    distribution (P + P^T) / sum as CSR (indptr int32 [N + 1], indices int32, data f32), on the device."""
+    conditional: torch.Tensor
+    beta: torch.Tensor
+    steps: torch.Tensor
+    indptr: torch.Tensor
+    indices: torch.Tensor
+    data: torch.Tensor
+
+
+def joint_csr(idx: np.ndarray, cond: np.ndarray):
+    """_joint_probabilities_nn's P = P + P.T; P /= max(P.sum(), eps) as (indptr int32, indices int32, data f32): the
+    entries (i, idx[i, r]) and their transposes merged by a stable sort on (row, column), exact zeros dropped as the
+    sparse sum drops them."""
+    N, k = idx.shape
+    if idx.min() < 0 or idx.max() >= N:
+        raise ValueError(f"neighbour indices outside [0, {N})")
+    own = np.repeat(np.arange(N, dtype=np.int64), k)
+    nb = idx.reshape(-1).astype(np.int64)
+    rows, cols = np.concatenate([own, nb]), np.concatenate([nb, own])
+    vals = np.concatenate([cond.reshape(-1), cond.reshape(-1)]).astype(np.float64)
+    key = rows * N + cols
+    order = np.argsort(key, kind="stable")
+    key, vals = key[order], vals[order]
+    first = np.concatenate([[True], key[1:] != key[:-1]])
+    starts = np.nonzero(first)[0]
+    data = np.add.reduceat(vals, starts)
+    key = key[starts]
+    keep = data != 0.0
+    key, data = key[keep], data[keep]
+    data = data / max(float(data.sum()), MACHINE_EPSILON)
+    indptr = np.zeros(N + 1, dtype=np.int64)
+    np.add.at(indptr, key // N + 1, 1)
+    return np.cumsum(indptr).astype(np.int32), (key % N).astype(np.int32), data.astype(np.float32)
+
+
+def tsne_affinities(idx: torch.Tensor, d2: torch.Tensor, perplexity: float = 30.0, timers=None) -> TSNEAffinities:
+    """_joint_probabilities_nn on knn_graph's output: the perplexity search on the device, the symmetrised CSR on the
+    host."""
+    idx = _device_matrix(idx, "idx", torch.int32)
+    d2 = _device_matrix(d2, "d2", torch.float64)
+    if idx.shape != d2.shape:
+        raise ValueError(f"idx {tuple(idx.shape)} and d2 {tuple(d2.shape)} differ in shape")
+    N, k = d2.shape
+    dev = d2.device
+    P = torch.empty((N, k), dtype=torch.float64, device=dev)
+    beta = torch.empty(N, dtype=torch.float64, device=dev)
+    steps = torch.empty(N, dtype=torch.int32, device=dev)
+    (timers or _Timers(None)).span("perplexity", lambda: L.call("rbvae_tsne_perplexity", d2, N, k, float(perplexity), P,
+                                                                 beta, steps))
+    Ph = P.cpu().numpy()
+    if not np.all(np.isfinite(Ph)):
+        raise ValueError("the conditional probabilities are not finite (are the distances?)")
+    indptr, indices, data = joint_csr(idx.cpu().numpy(), Ph)
+    return TSNEAffinities(P, beta, steps, torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev),
+                          torch.from_numpy(data).to(dev))
+
+
+@dataclasses.dataclass
+class PCAResult:
+    """embedding f64 [N, n_components] on the device; components [n_components, L], explained_variance
+    [n_components] and mean [L] as f64 host arrays (PCA.components_, .explained_variance_, .mean_)."""
+    embedding: torch.Tensor
+    components: np.ndarray
+    explained_variance: np.ndarray
+    mean: np.ndarray
+
+
+def pca_moments(X: torch.Tensor):
+    """rbvae_pca_moments -> (mean f64 [L], covariance f64 [L, L], divisor N - 1) on the device"""
+    X = _device_matrix(X, "X")
+    N, Ld = X.shape
+    mean = torch.empty(Ld, dtype=torch.float64, device=X.device)
+    cov = torch.empty((Ld, Ld), dtype=torch.float64, device=X.device)
+    L.call("rbvae_pca_moments", X, N, Ld, mean, cov)
+    return mean, cov
+
+
+def pca_project(X: torch.Tensor, n_components: int = 2) -> PCAResult:
+    """PCA(n_components).fit_transform(X) (:111-112) in f64: the covariance_eigh solver, the sign of each component fixed
+    as svd_flip(u_based_decision=False) fixes it (its entry of largest magnitude is positive)."""
+    X = _device_matrix(X, "X")
+    N, Ld = X.shape
+    nc = int(n_components)
+    if not 1 <= nc <= min(Ld, MAX_COMPONENTS):
+        raise ValueError(f"n_components={nc} outside 1..min(L = {Ld}, {MAX_COMPONENTS})")
+    mean, cov = pca_moments(X)
+    w, v = np.linalg.eigh(cov.cpu().numpy())
+    order = np.argsort(w, kind="stable")[::-1][:nc]
+    comp = np.ascontiguousarray(v[:, order].T)
+    big = np.argmax(np.abs(comp), axis=1)
+    comp *= np.sign(comp[np.arange(nc), big])[:, None]
+    out = torch.empty((N, nc), dtype=torch.float64, device=X.device)
+    L.call("rbvae_pca_project", X, N, Ld, mean, torch.from_numpy(comp).to(X.device), nc, out)
+    return PCAResult(out, comp, np.maximum(w[order], 0.0), mean.cpu().numpy())
+
+
+@dataclasses.dataclass
+class TSNEResult:
+    """embedding f32 [N, 2] on the device; kl_divergence and n_iter as TSNE.kl_divergence_ and TSNE.n_iter_ (the index
+    of the last iteration run).  One edge differs: at max_iter = 250 scikit-learn still enters its second phase, which
+    runs no iteration, and reports n_iter_ = 250 with the largest float as kl_divergence_; here that run ends with
+    n_iter = 249 and the KL of the first phase's last iteration."""
+    embedding: torch.Tensor
+    kl_divergence: float
+    n_iter: int
+
+
+class _Timers:
+    """device milliseconds per launch kind, summed over the run, into a dict, when one is given"""
+
+    def __init__(self, sink):
+        self.sink, self.spans = sink, []
+
+    def span(self, name, fn):
+        if self.sink is None:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        self.spans.append((name, a, b))
+
+    def close(self):
+        if self.sink is not None:
+            torch.cuda.synchronize()
+            for name, a, b in self.spans:
+                self.sink[name] = self.sink.get(name, 0.0) + a.elapsed_time(b)
+
+
+def tsne_optimise(Y0: torch.Tensor, aff: TSNEAffinities, max_iter: int = 1000, early_exaggeration: float = 12.0,
+                  learning_rate: float = 200.0, n_iter_without_progress: int = 300, min_grad_norm: float = 1e-7,
+                  timings: Optional[dict] = None) -> TSNEResult:
+    """TSNE._tsne from the map Y0 f32 [N, 2]: three launches per iteration, one read-back every 50."""
+    Y0 = _device_matrix(Y0, "Y0")
+    N = Y0.shape[0]
+    if Y0.shape[1] != 2:
+        raise ValueError(f"the map must be [N, 2], got {tuple(Y0.shape)}")
+    dev = Y0.device
+    Y, Yn = Y0.clone(), torch.empty_like(Y0)
+    update, gains = torch.zeros_like(Y0), torch.ones_like(Y0)
+    part = torch.empty((L.query("rbvae_tsne_repulse_splits", N), N, 3), dtype=torch.float32, device=dev)
+    Z = torch.empty(1, dtype=torch.float64, device=dev)
+    stats = torch.empty((L.query("rbvae_tsne_step_parts", N), 3), dtype=torch.float64, device=dev)
+    sched = torch.empty(3, dtype=torch.float32, device=dev)
+    t = _Timers(timings)
+    error, it = float(np.finfo(float).max), -1
+
+    def phase(start, stop, exaggeration, momentum, patience):
+        nonlocal Y, Yn, error
+        sched.copy_(torch.tensor([exaggeration, momentum, learning_rate], dtype=torch.float32))
+        best_error, best_iter, i = float(np.finfo(float).max), start, start
+        for i in range(start, stop):
+            t.span("repulse", lambda: L.call("rbvae_tsne_repulse", Y, N, part))
+            t.span("zsum", lambda: L.call("rbvae_tsne_zsum", part, N, Z))
+            t.span("step", lambda: L.call("rbvae_tsne_step", Y, Yn, update, gains, aff.indptr, aff.indices, aff.data,
+                                          part, Z, sched, N, stats))
+            Y, Yn = Yn, Y
+            check = (i + 1) % N_ITER_CHECK == 0
+            if check or i == stop - 1:
+                s = stats.cpu().numpy().sum(axis=0)         # the one synchronisation of these 50 iterations
+                error = float(s[2])
+            if check:
+                if error < best_error:
+                    best_error, best_iter = error, i
+                elif i - best_iter > patience:
+                    break
+                if float(np.sqrt(s[1])) <= min_grad_norm:
+                    break
+        return i
+
+    it = phase(0, EXPLORATION_ITERS, float(early_exaggeration), 0.5, EXPLORATION_ITERS)
+    if it + 1 < max_iter:
+        it = phase(it + 1, max_iter, 1.0, 0.8, int(n_iter_without_progress))
+    t.close()
+    return TSNEResult(Y, error, it)
+
+
+def tsne_project(X: torch.Tensor, perplexity: float = 30.0, max_iter: int = 1000, early_exaggeration: float = 12.0,
+                 learning_rate="auto", init: Optional[torch.Tensor] = None, timings: Optional[dict] = None) -> TSNEResult:
+    """TSNE(n_components=2, perplexity=perplexity).fit_transform(X) (:87-88) for X f32 [N, L] on the device, with the
+    exact repulsion and, unless `init` f32 [N, 2] is given, the exact PCA of X scaled to std(Y[:, 0]) = 1e-4 as the
+    initial map.  max_iter >= 250 as in scikit-learn.  timings: a dict that receives the device milliseconds of "knn",
+    "perplexity", "pca" and, summed over the iterations, "repulse", "zsum" and "step"."""
+    X = _device_matrix(X, "X")
+    N = X.shape[0]
+    if max_iter < EXPLORATION_ITERS:
+        raise ValueError(f"max_iter={max_iter} must be at least {EXPLORATION_ITERS}")
+    if not perplexity < N:
+        raise ValueError(f"perplexity={perplexity} must be less than the {N} rows")
+    k = min(N - 1, int(3.0 * perplexity + 1))
+    t = _Timers(timings)
+    graph, res = [], []
+    t.span("knn", lambda: graph.extend(knn_graph(X, k)))
+    aff = tsne_affinities(graph[0], graph[1], perplexity, timers=t)
+    if init is None:
+        t.span("pca", lambda: res.append(pca_project(X, 2)))
+        t.close()
+        emb = res[0].embedding.cpu().numpy().astype(np.float32)
+        Y0 = torch.from_numpy((emb / np.std(emb[:, 0]) * 1e-4).astype(np.float32)).to(X.device)
+    else:
+        t.close()
+        Y0 = _device_matrix(init, "init")
+        if tuple(Y0.shape) != (N, 2):
+            raise ValueError(f"init must be [{N}, 2], got {tuple(Y0.shape)}")
+    lr = max(N / early_exaggeration / 4.0, 50.0) if learning_rate == "auto" else float(learning_rate)
+    return tsne_optimise(Y0, aff, max_iter, early_exaggeration, lr, timings=timings)
+
+
+@torch.no_grad()
+def latent_projections(model, x: torch.Tensor, temperature: float = 0.2, noise_ratio: float = 0.3,
+                       frame_indices: Optional[Sequence[int]] = None, flags: Optional[Sequence[int]] = None,
+                       u=None, **tsne_kw) -> dict:
+    """The script's loop (:209-228) as one batched call: x [F, C, H, W] frames (or latents) on the device, one
+    sequence of length 1 per frame, z = model.encode(x, temperature, hard=False, noise_ratio) (:214, :224), then both
+    projections of the soft latents.  Labels (:228) come from data.assign_label(frame_indices[f], flags) when both are
+    given; u [F, L]: the binarisation uniforms instead of the host draw.  tsne_kw goes to tsne_project.
+    -> {"latents": f32 [F, L], "pca": PCAResult, "tsne": TSNEResult, "labels": int64 array or None}"""
+    from .data import assign_label
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be on the GPU (there is no CPU path)")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
+    was_training = model.training
+    model.eval()
+    try:
+        z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio,
+                         u=None if u is None else u.to(x.device))[:, 0]
+    finally:
+        model.train(was_training)
+    z = z.float().contiguous()
+    labels = None
+    if frame_indices is not None and flags is not None:
+        if len(frame_indices) != x.shape[0]:
+            raise ValueError(f"{len(frame_indices)} frame indices for {x.shape[0]} frames")
+        labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+    return {"latents": z, "pca": pca_project(z, 2), "tsne": tsne_project(z, **tsne_kw), "labels": labels}
