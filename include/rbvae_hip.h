@@ -721,6 +721,38 @@ int rbvae_pca_moments(const float* X, int N, int L, double* mean, double* cov, v
 int rbvae_pca_project(const float* X, int N, int L, const double* mean, const double* V, int n_components, double* out,
                       void* stream);
 
+/* ---- latent scores (csrc/scores.hip) ---------------------------------------------------------------------
+ * What embedding_umap.py leaves to the eye, as numbers: how faithful a 2-D map is (trustworthiness, continuity) and how
+ * well the labelled latents separate (silhouette), as scikit-learn 1.7.2 computes them; scores.py finishes both on the
+ * host.  Counts are integers and every f64 sum has one fixed order (no atomics): two runs agree bit for bit.
+ * d2(i, j) = sum_l (x_il - x_jl)^2 is rbvae_knn's, from the same device function: f64, l ascending, each difference exact,
+ * each square rounded once.
+ *
+ * rbvae_nbr_ranks (sklearn.manifold.trustworthiness): X f32 [N][L] and nbr int32 [N][k], row i's neighbours in some other
+ * space (rbvae_knn of the map); limits as rbvae_knn: 2 <= N <= 16384 (a row's N distances sit in LDS as f64),
+ * 1 <= L <= 128, 1 <= k <= min(N - 1, 128).  rank [N][k]: the 1-based position of j = nbr[i][r] among the N - 1 other rows
+ * of X ordered by (d2(i, .), index) ascending, rank = 1 + #{m != i : d2(i,m) < d2(i,j) or (d2(i,m) == d2(i,j) and m < j)};
+ * excess [N] = sum_r max(0, rank[i][r] - k).  An entry of nbr outside [0, N) (rbvae_knn's 0x7fffffff) or equal to i gets
+ * rank -1, adds nothing to excess and reads nothing outside X.  X must be finite.
+ * rbvae_nbr_ranks_ok: 1 when (N, L, k) is covered; anything else makes rbvae_nbr_ranks return RBVAE_E_INVALID without a
+ * launch. */
+int rbvae_nbr_ranks_ok(int N, int L, int k);
+int rbvae_nbr_ranks(const float* X, int N, int L, const int* nbr, int k, int* rank, int* excess, void* stream);
+/* sklearn.metrics.silhouette_samples' reduction: the rows grouped by state, order int32 [N] (a stable sort by label: rows
+ * ascend within a state) and seg int32 [S + 1] (the states' offsets into order; an empty state has an empty segment);
+ * 1 <= N <= 16384, 1 <= L <= 128, 1 <= S <= 256.  sums [N][S], indexed by the original row i:
+ *   rbvae_label_dist_sums     f64: sum over the rows j of segment s, in segment order, of sqrt(d2(i, j)) (an IEEE square
+ *                             root; the j = i term is an exact 0)
+ *   rbvae_label_hamming_sums  int32: sum_j popcount(key_i xor key_j), the 128-bit keys packed as rbvae_state_vote packs
+ *                             them (bit = value > 0.5)
+ * Entries of order outside [0, N) are skipped and seg is clamped to [0, N]: nothing is read outside X or order.
+ * rbvae_label_sums_ok: 1 when (N, L, S) is covered; anything else returns RBVAE_E_INVALID without a launch. */
+int rbvae_label_sums_ok(int N, int L, int S);
+int rbvae_label_dist_sums(const float* X, int N, int L, const int* order, const int* seg, int S, double* sums,
+                          void* stream);
+int rbvae_label_hamming_sums(const float* codes, int N, int L, const int* order, const int* seg, int S, int* sums,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

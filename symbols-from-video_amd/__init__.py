@@ -25,3 +25,6 @@ from .probe import ProbeResult, fit_factor, frame_embeddings, frame_probe, linea
 from . import projection  # noqa: F401
 from .projection import (PCAResult, TSNEAffinities, TSNEResult, knn_graph, latent_projections, pca_project,  # noqa: F401
                          tsne_affinities, tsne_project)
+from . import scores  # noqa: F401
+from .scores import (continuity, knn_label_agreement, label_distance_sums, latent_scores, neighbour_ranks,  # noqa: F401
+                     silhouette_samples, silhouette_score, trustworthiness)

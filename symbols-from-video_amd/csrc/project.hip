@@ -14,6 +14,7 @@
 // No float atomics: every sum has a fixed order, two runs agree bit for bit.  Contraction is off: sums round where the
 // text says they do, fused products are explicit fma calls.
 #include "common.h"
+#include "pairdist.h"
 
 #include <float.h>
 #include <math.h>
@@ -26,10 +27,6 @@ constexpr int PJ_THREADS = 256;
 constexpr int PJ_MAX_L = 128, PJ_MAX_K = 128, PJ_MAX_N = 16384, PJ_MAX_COMP = 8;
 constexpr int RP_TI = 256;              // i rows per workgroup of the repulsion, one per lane
 constexpr int RP_JC = 256;              // j points per LDS chunk; a chunk's sums start from zero
-
-__device__ __forceinline__ bool key_less(double da, int ja, double db, int jb) {
-    return da < db || (da == db && ja < jb);
-}
 
 // Dynamic LDS: dist f64 [N] | xq f64 [L] | wave minima d [2][4] | out_d f64 [k] | wave minima j [2][4] | out_j [k]
 __global__ __launch_bounds__(PJ_THREADS) void knn_k(const float* __restrict__ X, int N, int L, int k,
@@ -49,12 +46,7 @@ __global__ __launch_bounds__(PJ_THREADS) void knn_k(const float* __restrict__ X,
     double ld = inf;
     int lj = 0x7fffffff;
     for (int j = tid; j < N; j += PJ_THREADS) {             // ascending j: the first minimum is the lowest index
-        const float* xr = X + (long)j * L;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double df = xq[l] - (double)xr[l];        // exact
-            s += df * df;
-        }
+        double s = row_d2(xq, X + (long)j * L, L);
         if (j == i) s = inf;
         dist[j] = s;
         if (s < ld) { ld = s; lj = j; }
