@@ -672,7 +672,7 @@ int rbvae_probe_finish(const double* sums, long P, int m, double* r2, double* ev
 /* ---- latent-space projections (csrc/project.hip) --------------------------------------------------------
  * scripts/evaluation/clustering_eval/embedding_umap.py: the soft latents of the test frames (:214, :224) projected to 2-D
  * by PCA (:111-112), t-SNE (:87-88) and UMAP (:63-64).  PCA and t-SNE run here as scikit-learn 1.7.2 computes them
- * (DESIGN.md section 7 names the two deliberate differences); of UMAP only the exact neighbour graph it starts from.
+ * (DESIGN.md section 7 names the two deliberate differences); UMAP's fuzzy graph and layout follow below (csrc/umap.hip).
  * Every reduction has a fixed order (no atomics): two runs agree bit for bit.
  *
  * rbvae_knn (:63 n_neighbors = 24, :87 perplexity = 30 -> k = 91): the exact k nearest neighbours of every row of
@@ -720,6 +720,50 @@ int rbvae_tsne_step(const float* Y, float* Y_out, float* update, float* gains, c
 int rbvae_pca_moments(const float* X, int N, int L, double* mean, double* cov, void* stream);
 int rbvae_pca_project(const float* X, int N, int L, const double* mean, const double* V, int n_components, double* out,
                       void* stream);
+
+/* ---- UMAP (csrc/umap.hip) ---------------------------------------------------------------------------------
+ * embedding_umap.py:63-64, umap.UMAP(n_neighbors=24, min_dist=0.25, metric='euclidean', random_state=42), after McInnes,
+ * Healy, Melville 2018 (Algorithms 2-5) and umap-learn's published defaults; DESIGN.md section 7 has the formulation and
+ * the two deliberate differences (the initial map, the synchronous epoch).  n_neighbors = k counts the point itself: the
+ * graph is rbvae_knn with K1 = k - 1 <= 127 columns, d = (double)(float)sqrt(d2).  Every sum has one fixed order.
+ *
+ * rbvae_umap_smooth_knn, all arithmetic f64: dsum [1] = the sum of every d (one workgroup: thread t of 1024 adds the
+ * elements t, t + 1024, ... in ascending order, then a halving tree).  Per row (one wave, two neighbours per lane):
+ * rho = the smallest d > 0, or 0; the bisection on sigma from lo = 0, hi = inf, mid = 1, at most 64 evaluations of
+ *   psum = sum_r (d_r - rho > 0 ? exp(-(d_r - rho) / mid) : 1)           (a butterfly sum over the wave)
+ * stopping at |psum - log2 k| < 1e-5; psum > log2 k: hi = mid, mid = (lo + hi) / 2; otherwise lo = mid and mid doubles
+ * while hi = inf, else (lo + hi) / 2.  steps [N] = the evaluations.  sigma = max(mid, 1e-3 m), m = (sum_r d_r) / k where
+ * rho > 0 and dsum / (N k) where rho = 0.  w [N][K1] = 1 where d_r - rho <= 0 or sigma = 0, else exp(-(d_r - rho) / sigma).
+ * rho [N], sigma [N] and w are stored as f32.  rbvae_umap_smooth_knn_ok: 1 when N >= 1 and 1 <= K1 <= 127; anything else
+ * makes the call return RBVAE_E_INVALID without a launch.
+ *
+ * rbvae_umap_epoch: epoch n of n_epochs on the symmetric fuzzy graph as CSR (indptr int32 [N + 1], indices int32 [E]) with
+ * the schedule period f32 [E] = max(W) / W_e and the state next, next_neg f32 [E] (initially period and period /
+ * neg_rate), updated in place.  Y, Y_out f32 [N][2], 8-byte aligned, Y_out != Y: every vertex moves from the epoch-start
+ * map.  2 <= N <= 16384.  alpha = 1 - (float)n / (float)n_epochs.  One wave per vertex i, its row's edges in chunks of 64,
+ * one per lane; an edge e = (i -> j) with next_e <= n adds, in f32,
+ *   2 clip(c D, +-4),  D = y_i - y_j,  r2 = |D|^2,  c = r2 > 0 ? fl(-2ab) pow(r2, b - 1) / (a pow(r2, b) + 1) : 0
+ * (twice: the mirror edge j -> i shares weight and schedule, and its move of the other end is this same vector), then for
+ * q = clamp((int)((n - next_neg_e) / neg_period_e), 0, 32), neg_period_e = period_e / neg_rate, and p = 0 .. q - 1
+ *   m = ((uint64)hash_u32(seed, (uint64)n << 40 | (uint64)e << 8 | p) * N) >> 32,  skipped when m = i,
+ *   clip(c D, +-4),  D = y_i - y_m,  c = r2 > 0 ? fl(2 gamma b) / ((0.001 + r2)(a pow(r2, b) + 1)) : 0
+ * and next_e += period_e, next_neg_e += q neg_period_e.  A butterfly adds a chunk, the chunks are added in order,
+ * Y_out_i = y_i + alpha sum.  An edge whose index is outside [0, N) is left alone.  hash_u32 is csrc/common.h's.
+ * rbvae_umap_epoch_samples: the same schedule arithmetic and draws for the epoch the state stands before, written out and
+ * not applied: count int32 [E] = q (0 for an edge that is not active), samples int32 [E][32] = m, -1 in a slot that is not
+ * drawn or drew i itself.
+ * rbvae_umap_epoch_ok: 1 when (N, n_epochs <= 2^20, 1 <= neg_rate <= 64) is covered; refused arguments (also epoch outside
+ * 0 .. n_epochs - 1, a or b <= 0, gamma < 0, Y_out = Y) return RBVAE_E_INVALID without a launch. */
+int rbvae_umap_smooth_knn_ok(int N, int K1);
+int rbvae_umap_smooth_knn(const double* d2, int N, int K1, double* dsum, float* rho, float* sigma, float* w, int* steps,
+                          void* stream);
+int rbvae_umap_epoch_ok(int N, int n_epochs, int neg_rate);
+int rbvae_umap_epoch(const float* Y, float* Y_out, const int* indptr, const int* indices, const float* period, float* next,
+                     float* next_neg, int N, int epoch, int n_epochs, float a, float b, float gamma, int neg_rate,
+                     unsigned long long seed, void* stream);
+int rbvae_umap_epoch_samples(const int* indptr, const float* period, const float* next, const float* next_neg, int N,
+                             int epoch, int n_epochs, int neg_rate, unsigned long long seed, int* count, int* samples,
+                             void* stream);
 
 /* ---- latent scores (csrc/scores.hip) ---------------------------------------------------------------------
  * What embedding_umap.py leaves to the eye, as numbers: how faithful a 2-D map is (trustworthiness, continuity) and how

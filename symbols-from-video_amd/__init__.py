@@ -23,8 +23,9 @@ from .robustness import (adjacent_hamming, most_common_codes, reference_draws, s
 from . import probe  # noqa: F401  (probe.split_indices is the probe's train/test split; data.split_indices the trainer's)
 from .probe import ProbeResult, fit_factor, frame_embeddings, frame_probe, linear_probe  # noqa: F401
 from . import projection  # noqa: F401
-from .projection import (PCAResult, TSNEAffinities, TSNEResult, knn_graph, latent_projections, pca_project,  # noqa: F401
-                         tsne_affinities, tsne_project)
+from .projection import (PCAResult, TSNEAffinities, TSNEResult, UMAPGraph, UMAPResult, fuzzy_csr,  # noqa: F401
+                         fuzzy_graph, knn_graph, latent_projections, pca_project, tsne_affinities, tsne_project, umap_ab,
+                         umap_optimise, umap_project)
 from . import scores  # noqa: F401
 from .scores import (continuity, knn_label_agreement, label_distance_sums, latent_scores, neighbour_ranks,  # noqa: F401
                      silhouette_samples, silhouette_score, trustworthiness)

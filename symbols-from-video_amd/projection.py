@@ -3,7 +3,7 @@ model.encode(..., temperature=0.2, hard=False, noise_ratio=0.3) of the frames (:
 PCA(n_components=2) (:111-112) and TSNE(n_components=2, random_state=42, perplexity=30) (:87-88), on the device
 (csrc/project.hip), as scikit-learn 1.7.2 computes them:
   knn_graph        the exact k nearest neighbours in f64, sorted by (d2, index): what t-SNE (k = 3 perplexity + 1 = 91) and
-                   UMAP (:63, n_neighbors = 24) both start from
+                   UMAP (:63, n_neighbors = 24 counts the point itself: k = 23) both start from
   tsne_affinities  _binary_search_perplexity on the device; P + P^T, normalised, as one merged CSR on the host, once per fit
   tsne_project     TSNE._tsne: 250 iterations with momentum 0.5 and P x early_exaggeration, then momentum 0.8, learning rate
                    max(N / early_exaggeration / 4, 50), gains as _gradient_descent keeps them; every 50 iterations the KL
@@ -12,13 +12,26 @@ PCA(n_components=2) (:111-112) and TSNE(n_components=2, random_state=42, perplex
                    projection on the device, all f64
 Two deliberate differences from scikit-learn's defaults: the repulsion is exact (what
 _kl_divergence_bh(angle=0) computes) instead of Barnes-Hut at angle 0.5, and the initial map is this module's exact PCA
-instead of the randomised-SVD PCA seeded by random_state.  UMAP's fuzzy graph and layout are not built: knn_graph(X, 24)
-is the part of it that is pinned.  The plots stay with the caller.
+instead of the randomised-SVD PCA seeded by random_state.
+
+umap.UMAP(n_neighbors=24, min_dist=0.25, metric='euclidean', random_state=42) (:63-64) follows McInnes, Healy, Melville 2018
+(Algorithms 2-5) and umap-learn's published defaults (csrc/umap.hip; umap-learn itself is not a dependency):
+  umap_ab          a, b of 1 / (1 + a x^(2b)) by scipy's curve fit to the offset exponential (find_ab_params)
+  fuzzy_graph      the smooth kNN distances (rho, the bisection on sigma, the memberships) on the device from
+                   knn_graph(X, n_neighbors - 1); the fuzzy union W = A + A^T - A o A^T as one merged CSR on the host
+  umap_optimise    the edge schedule (entries below max(W) / n_epochs dropped, period = max(W) / W) and one launch per
+                   epoch: attraction along the active edges, hashed negative samples, learning rate 1 - n / n_epochs
+  umap_project     kNN graph, fuzzy graph, initial map, n_epochs = 500 (200 above 10 000 rows) epochs
+Two deliberate differences from umap-learn: the initial map is this module's exact PCA (scaled to
+[0, 10] with 1e-4 noise) instead of the spectral layout, and an epoch is synchronous: every vertex moves from the
+epoch-start map, the attraction of an edge counted twice for the mirror edge's move of the other end, negatives drawn by a
+counter hash, so that two runs with one seed agree bit for bit.  The plots stay with the caller.
 There is no host path: inputs on the CPU raise.
 """
 from __future__ import annotations
 
 import dataclasses
+import time
 from typing import Optional, Sequence
 
 import numpy as np
@@ -267,15 +280,208 @@ def tsne_project(X: torch.Tensor, perplexity: float = 30.0, max_iter: int = 1000
     return tsne_optimise(Y0, aff, max_iter, early_exaggeration, lr, timings=timings)
 
 
+# ---- UMAP --------------------------------------------------------------------------------------------------------------
+
+MAX_UMAP_NEIGHBORS = 128                            # rbvae_umap_smooth_knn: n_neighbors - 1 <= 127, two per lane
+MAX_UMAP_ROWS = 16384                               # rbvae_umap_epoch
+
+
+def umap_ab(spread: float = 1.0, min_dist: float = 0.1):
+    """umap-learn's find_ab_params: (a, b) of 1 / (1 + a x^(2b)) fitted by scipy.optimize.curve_fit to y = 1 for
+    x < min_dist, else exp(-(x - min_dist) / spread), on linspace(0, 3 spread, 300)."""
+    from scipy.optimize import curve_fit
+    x = np.linspace(0.0, 3.0 * float(spread), 300)
+    y = np.where(x < min_dist, 1.0, np.exp(-(x - min_dist) / spread))
+    (a, b), _ = curve_fit(lambda x, a, b: 1.0 / (1.0 + a * x ** (2 * b)), x, y)
+    return float(a), float(b)
+
+
+def fuzzy_csr(idx: np.ndarray, w: np.ndarray):
+    """The fuzzy union W = A + A^T - A o A^T, A[i, idx[i, r]] = w[i, r] (a row's neighbours distinct), as (indptr int32,
+    indices int32, data f32): the entries and their transposes merged by a stable sort on (row, column), the products
+    formed in f64 from the f32 memberships as (a + b) - a b, which is the same number for (i, j) and (j, i); exact zeros
+    dropped."""
+    N, K1 = idx.shape
+    if idx.min() < 0 or idx.max() >= N:
+        raise ValueError(f"neighbour indices outside [0, {N})")
+    own = np.repeat(np.arange(N, dtype=np.int64), K1)
+    nb = idx.reshape(-1).astype(np.int64)
+    vals = np.asarray(w, dtype=np.float32).reshape(-1).astype(np.float64)
+    zero = np.zeros_like(vals)
+    key = np.concatenate([own * N + nb, nb * N + own])
+    order = np.argsort(key, kind="stable")
+    key = key[order]
+    starts = np.nonzero(np.concatenate([[True], key[1:] != key[:-1]]))[0]
+    a = np.add.reduceat(np.concatenate([vals, zero])[order], starts)
+    b = np.add.reduceat(np.concatenate([zero, vals])[order], starts)
+    data = (a + b) - a * b
+    key = key[starts]
+    keep = data != 0.0
+    key, data = key[keep], data[keep]
+    indptr = np.zeros(N + 1, dtype=np.int64)
+    np.add.at(indptr, key // N + 1, 1)
+    return np.cumsum(indptr).astype(np.int32), (key % N).astype(np.int32), data.astype(np.float32)
+
+
+@dataclasses.dataclass
+class UMAPGraph:
+    """rho [N] f32, sigma [N] f32, steps [N] int32 and membership [N, n_neighbors - 1] f32 from the smooth kNN distances
+    (device); the fuzzy union as CSR (indptr int32 [N + 1], indices int32, data f32), on the device."""
+    rho: torch.Tensor
+    sigma: torch.Tensor
+    steps: torch.Tensor
+    membership: torch.Tensor
+    indptr: torch.Tensor
+    indices: torch.Tensor
+    data: torch.Tensor
+
+
+def fuzzy_graph(idx: torch.Tensor, d2: torch.Tensor, n_neighbors: int, timers=None) -> UMAPGraph:
+    """The fuzzy simplicial set of knn_graph(X, n_neighbors - 1)'s output: rbvae_umap_smooth_knn on the device, the union
+    on the host."""
+    idx = _device_matrix(idx, "idx", torch.int32)
+    d2 = _device_matrix(d2, "d2", torch.float64)
+    if idx.shape != d2.shape:
+        raise ValueError(f"idx {tuple(idx.shape)} and d2 {tuple(d2.shape)} differ in shape")
+    N, K1 = d2.shape
+    k = int(n_neighbors)
+    if not 2 <= k <= min(N, MAX_UMAP_NEIGHBORS):
+        raise ValueError(f"n_neighbors={k} outside 2..min(N = {N}, {MAX_UMAP_NEIGHBORS})")
+    if K1 != k - 1:
+        raise ValueError(f"n_neighbors={k} counts the point itself: the graph must have {k - 1} columns, not {K1}")
+    dev = d2.device
+    dsum = torch.empty(1, dtype=torch.float64, device=dev)
+    rho = torch.empty(N, dtype=torch.float32, device=dev)
+    sigma = torch.empty(N, dtype=torch.float32, device=dev)
+    w = torch.empty((N, K1), dtype=torch.float32, device=dev)
+    steps = torch.empty(N, dtype=torch.int32, device=dev)
+    (timers or _Timers(None)).span("smooth_knn", lambda: L.call("rbvae_umap_smooth_knn", d2, N, K1, dsum, rho, sigma, w,
+                                                                 steps))
+    wh = w.cpu().numpy()
+    if not np.all(np.isfinite(wh)):
+        raise ValueError("the memberships are not finite (are the distances?)")
+    indptr, indices, data = fuzzy_csr(idx.cpu().numpy(), wh)
+    return UMAPGraph(rho, sigma, steps, w, torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev),
+                     torch.from_numpy(data).to(dev))
+
+
+def umap_schedule(indptr: np.ndarray, indices: np.ndarray, data: np.ndarray, n_epochs: int, negative_sample_rate: int = 5):
+    """The layout's edges and their f32 schedule: entries below max(W) / n_epochs dropped, period = max(W) / W,
+    next = period, next_neg = period / negative_sample_rate -> (indptr, indices, period, next, next_neg)."""
+    data = np.asarray(data, dtype=np.float32)
+    N = len(indptr) - 1
+    if data.size == 0:
+        raise ValueError("the graph has no edges")
+    top = data.max()
+    keep = ~(data < top / np.float32(n_epochs))
+    rows = np.repeat(np.arange(N), np.diff(indptr))[keep]
+    ip = np.zeros(N + 1, dtype=np.int64)
+    np.add.at(ip, rows + 1, 1)
+    period = (top / data[keep]).astype(np.float32)
+    return (np.cumsum(ip).astype(np.int32), np.asarray(indices)[keep].astype(np.int32), period, period.copy(),
+            (period / np.float32(negative_sample_rate)).astype(np.float32))
+
+
+@dataclasses.dataclass
+class UMAPResult:
+    """embedding f32 [N, 2] on the device; the epochs run and the curve parameters used"""
+    embedding: torch.Tensor
+    n_epochs: int
+    a: float
+    b: float
+
+
+def umap_optimise(Y0: torch.Tensor, graph: UMAPGraph, n_epochs: Optional[int] = None, a: Optional[float] = None,
+                  b: Optional[float] = None, gamma: float = 1.0, negative_sample_rate: int = 5, seed: int = 42,
+                  timings: Optional[dict] = None) -> UMAPResult:
+    """The layout from the map Y0 f32 [N, 2]: the schedule on the host, then one launch per epoch and no read-back.
+    n_epochs None: 500 up to 10 000 rows, else 200; a, b None: umap_ab() of umap-learn's default min_dist 0.1."""
+    Y0 = _device_matrix(Y0, "Y0")
+    N = Y0.shape[0]
+    if Y0.shape[1] != 2:
+        raise ValueError(f"the map must be [N, 2], got {tuple(Y0.shape)}")
+    if graph.indptr.numel() != N + 1:
+        raise ValueError(f"the graph has {graph.indptr.numel() - 1} rows, the map {N}")
+    if n_epochs is None:
+        n_epochs = 500 if N <= 10000 else 200
+    n_epochs, rate = int(n_epochs), int(negative_sample_rate)
+    if not L.query("rbvae_umap_epoch_ok", N, n_epochs, rate):
+        raise ValueError(f"N={N} (2..{MAX_UMAP_ROWS}), n_epochs={n_epochs} or negative_sample_rate={rate} is not covered")
+    if a is None or b is None:
+        a, b = umap_ab()
+    dev = Y0.device
+    sch = umap_schedule(graph.indptr.cpu().numpy(), graph.indices.cpu().numpy(), graph.data.cpu().numpy(), n_epochs, rate)
+    indptr, indices, period, nxt, nxt_neg = (torch.from_numpy(x).to(dev) for x in sch)
+    Y, Yn = Y0.clone(), torch.empty_like(Y0)
+    t = _Timers(timings)
+
+    def run():
+        nonlocal Y, Yn
+        for n in range(n_epochs):
+            L.call("rbvae_umap_epoch", Y, Yn, indptr, indices, period, nxt, nxt_neg, N, n, n_epochs, float(a), float(b),
+                   float(gamma), rate, int(seed))
+            Y, Yn = Yn, Y
+
+    t.span("epochs", run)
+    t.close()
+    return UMAPResult(Y, n_epochs, float(a), float(b))
+
+
+def umap_initial_map(pca_embedding: np.ndarray, seed: int = 42) -> np.ndarray:
+    """The exact PCA scaled by 10 / max |.|, plus RandomState(seed).normal(scale=1e-4), each column min-max scaled to
+    [0, 10]; f64 on the host, cast to f32."""
+    Y = np.asarray(pca_embedding, dtype=np.float64)
+    Y = Y * (10.0 / max(float(np.abs(Y).max()), np.finfo(np.float64).tiny))
+    Y = Y + np.random.RandomState(seed).normal(scale=1e-4, size=Y.shape)
+    lo, hi = Y.min(0), Y.max(0)
+    return (10.0 * (Y - lo) / np.where(hi > lo, hi - lo, 1.0)).astype(np.float32)
+
+
+def umap_project(X: torch.Tensor, n_neighbors: int = 15, min_dist: float = 0.1, spread: float = 1.0,
+                 n_epochs: Optional[int] = None, seed: int = 42, init: Optional[torch.Tensor] = None,
+                 timings: Optional[dict] = None) -> UMAPResult:
+    """umap.UMAP(n_neighbors, min_dist, metric='euclidean', random_state=seed).fit_transform(X) (:63-64) for X f32 [N, L]
+    on the device, as this module states it: the exact kNN graph, the synchronous epoch and, unless `init` f32 [N, 2] is
+    given, umap_initial_map of the exact PCA.  timings: a dict that receives the device milliseconds of "knn",
+    "smooth_knn", "pca" and "epochs", and the host's wall milliseconds for "fuzzy_csr"."""
+    X = _device_matrix(X, "X")
+    N = X.shape[0]
+    k = int(n_neighbors)
+    if not 2 <= k <= min(N, MAX_UMAP_NEIGHBORS):
+        raise ValueError(f"n_neighbors={k} outside 2..min(N = {N}, {MAX_UMAP_NEIGHBORS})")
+    if N > MAX_UMAP_ROWS:
+        raise ValueError(f"N={N} above {MAX_UMAP_ROWS}")
+    a, b = umap_ab(spread, min_dist)
+    t = _Timers(timings)
+    knn, res = [], []
+    t.span("knn", lambda: knn.extend(knn_graph(X, k - 1)))
+    t0 = time.perf_counter()
+    graph = fuzzy_graph(knn[0], knn[1], k, timers=t)
+    if timings is not None:
+        timings["fuzzy_csr"] = 1e3 * (time.perf_counter() - t0)     # includes the wait for the kNN and smooth-kNN launches
+    if init is None:
+        t.span("pca", lambda: res.append(pca_project(X, 2)))
+        t.close()
+        Y0 = torch.from_numpy(umap_initial_map(res[0].embedding.cpu().numpy(), seed)).to(X.device)
+    else:
+        t.close()
+        Y0 = _device_matrix(init, "init")
+        if tuple(Y0.shape) != (N, 2):
+            raise ValueError(f"init must be [{N}, 2], got {tuple(Y0.shape)}")
+    return umap_optimise(Y0, graph, n_epochs, a, b, seed=seed, timings=timings)
+
+
 @torch.no_grad()
 def latent_projections(model, x: torch.Tensor, temperature: float = 0.2, noise_ratio: float = 0.3,
                        frame_indices: Optional[Sequence[int]] = None, flags: Optional[Sequence[int]] = None,
-                       u=None, **tsne_kw) -> dict:
+                       u=None, umap: Optional[dict] = None, **tsne_kw) -> dict:
     """The script's loop (:209-228) as one batched call: x [F, C, H, W] frames (or latents) on the device, one
     sequence of length 1 per frame, z = model.encode(x, temperature, hard=False, noise_ratio) (:214, :224), then both
     projections of the soft latents.  Labels (:228) come from data.assign_label(frame_indices[f], flags) when both are
-    given; u [F, L]: the binarisation uniforms instead of the host draw.  tsne_kw goes to tsne_project.
-    -> {"latents": f32 [F, L], "pca": PCAResult, "tsne": TSNEResult, "labels": int64 array or None}"""
+    given; u [F, L]: the binarisation uniforms instead of the host draw.  tsne_kw goes to tsne_project.  umap: keyword
+    arguments of umap_project (the script's: {"n_neighbors": 24, "min_dist": 0.25, "seed": 42}); None leaves UMAP out.
+    -> {"latents": f32 [F, L], "pca": PCAResult, "tsne": TSNEResult, "labels": int64 array or None} and, with `umap`,
+    "umap": UMAPResult"""
     from .data import assign_label
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be on the GPU (there is no CPU path)")
@@ -294,4 +500,7 @@ def latent_projections(model, x: torch.Tensor, temperature: float = 0.2, noise_r
         if len(frame_indices) != x.shape[0]:
             raise ValueError(f"{len(frame_indices)} frame indices for {x.shape[0]} frames")
         labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
-    return {"latents": z, "pca": pca_project(z, 2), "tsne": tsne_project(z, **tsne_kw), "labels": labels}
+    out = {"latents": z, "pca": pca_project(z, 2), "tsne": tsne_project(z, **tsne_kw), "labels": labels}
+    if umap is not None:
+        out["umap"] = umap_project(z, **umap)
+    return out

@@ -163,7 +163,7 @@ def latent_scores(model, x: torch.Tensor, frame_indices: Sequence[int], flags: S
     -> {"latents" f32 [F, L], "codes" f32 [F, L], "labels" int64 array, "silhouette" (soft latents, Euclidean),
         "silhouette_hamming" (hard codes), "knn_purity", "knn_accuracy" (soft latents, k = n_neighbors)} and, when
     `projections` (latent_projections' dict) is given, "trustworthiness_pca", "continuity_pca", "trustworthiness_tsne" and
-    "continuity_tsne" of its maps at n_neighbors."""
+    "continuity_tsne" of its maps at n_neighbors, and "trustworthiness_umap" and "continuity_umap" when it holds "umap"."""
     from .data import assign_label
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be on the GPU (there is no CPU path)")
@@ -192,7 +192,7 @@ def latent_scores(model, x: torch.Tensor, frame_indices: Sequence[int], flags: S
            "silhouette": silhouette_score(z, labels, S), "silhouette_hamming": silhouette_score(codes, labels, S, "hamming"),
            "knn_purity": agree["purity"], "knn_accuracy": agree["accuracy"]}
     if projections is not None:
-        for name in ("pca", "tsne"):
+        for name in ("pca", "tsne") + (("umap",) if "umap" in projections else ()):
             Y = projections[name].embedding.float().contiguous()
             out[f"trustworthiness_{name}"] = trustworthiness(z, Y, n_neighbors)
             out[f"continuity_{name}"] = continuity(z, Y, n_neighbors)
