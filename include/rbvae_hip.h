@@ -797,6 +797,41 @@ int rbvae_label_dist_sums(const float* X, int N, int L, const int* order, const 
 int rbvae_label_hamming_sums(const float* codes, int N, int L, const int* order, const int* seg, int S, int* sums,
                              void* stream);
 
+/* ---- unsupervised symbols (csrc/kmeans.hip) ------------------------------------------------------------------
+ * Do the latents fall into the states by themselves?  Lloyd's k-means with k-means++ seeding as scikit-learn 1.7.2's
+ * KMeans(n_init=1, algorithm="lloyd") runs it, and the per-cluster sums behind the Davies-Bouldin and Calinski-Harabasz
+ * indices; symbols.py keeps the RandomState draws and finishes the scores on the host.  X f32 [N][L], centres f64 [K][L];
+ * 1 <= L <= 128, 1 <= K <= 256, K <= N <= 1048576 (rbvae_kmeans_ok); anything else makes every entry return
+ * RBVAE_E_UNSUPPORTED without a launch.  All arithmetic is f64, never contracted; d2_ik = sum_l (x_il - c_kl)^2 with l
+ * ascending (the difference now rounds: c is any f64 value).  No floating-point atomics: every sum has one fixed order.
+ *
+ * state int32 [4] = {done, n_iter, why (1 strict, 2 tol, 3 max_iter), changed}, zero before the first iteration; may be
+ * NULL in rbvae_kmeans_assign and rbvae_kmeans_update.  With done set, assign, update and decide return without writing
+ * anything, so iterations may be enqueued ahead of the decision.
+ * rbvae_kmeans_assign: label int32 [N] = the k with the smallest (d2, k) (ties to the lower centre), d2 f64 [N] = that
+ * distance; the number of rows with label != label_prev (NULL: every row) is added to state[3].  The centres pass through
+ * LDS rbvae_kmeans_chunk_centres(L) = 4096 / round_up(L, 8) at a time.  With own int32 [N] given, label = own and d2 =
+ * the distance to the row's own centre (label -1, d2 inf where own is no centre).
+ * rbvae_kmeans_update: centres_k = (sum of the rows labelled k) / count_k in place, shift2 [K] = |new - old|^2,
+ * within [K] = sum of d2 and spread [K] = sum of sqrt(d2) over the cluster's rows (0 with d2 = NULL), count int32 [K].
+ * Stage one: min(256, ceil(N / 256)) blocks of consecutive rows, each cell of a block's partial added in ascending row
+ * order; stage two adds the partials in block order.  An empty cluster keeps its centre: shift2 = 0, count = 0 (scikit-learn
+ * moves it to the row farthest from its centre).  A label outside [0, K) is skipped.  ws: rbvae_kmeans_ws_bytes(N, L, K).
+ * rbvae_kmeans_decide: n_iter += 1; changed == 0: done, strict; else sum_k shift2 (k ascending) <= tol_abs: done, tol; else
+ * n_iter >= max_iter: done; changed = 0.
+ * rbvae_kmeans_pp_trials: cand int32 [T], T <= 8 -> out f64 [T][N] = min(closest_i, d2(x_i, x_cand_t)) and pot f64 [T] =
+ * its sum (a halving tree per 256 rows, then over the workgroups' sums); a candidate outside [0, N) leaves closest. */
+int rbvae_kmeans_ok(int N, int L, int K);
+int rbvae_kmeans_chunk_centres(int L);
+size_t rbvae_kmeans_ws_bytes(int N, int L, int K);
+int rbvae_kmeans_assign(const float* X, int N, int L, const double* centres, int K, const int* label_prev, const int* own,
+                        int* label, double* d2, int* state, void* stream);
+int rbvae_kmeans_update(const float* X, int N, int L, const int* label, const double* d2, int K, double* centres, int* count,
+                        double* shift2, double* within, double* spread, double* ws, const int* state, void* stream);
+int rbvae_kmeans_decide(const double* shift2, int K, double tol_abs, int max_iter, int* state, void* stream);
+int rbvae_kmeans_pp_trials(const float* X, int N, int L, const int* cand, int T, const double* closest, double* out,
+                           double* pot, double* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

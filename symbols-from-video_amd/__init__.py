@@ -29,3 +29,6 @@ from .projection import (PCAResult, TSNEAffinities, TSNEResult, UMAPGraph, UMAPR
 from . import scores  # noqa: F401
 from .scores import (continuity, knn_label_agreement, label_distance_sums, latent_scores, neighbour_ranks,  # noqa: F401
                      silhouette_samples, silhouette_score, trustworthiness)
+from . import symbols  # noqa: F401
+from .symbols import (KMeansResult, calinski_harabasz, cluster_sums, clustering_agreement, code_symbols,  # noqa: F401
+                      contingency, davies_bouldin, kmeans, kmeans_plusplus, latent_symbols)
