@@ -832,6 +832,34 @@ int rbvae_kmeans_decide(const double* shift2, int K, double tol_abs, int max_ite
 int rbvae_kmeans_pp_trials(const float* X, int N, int L, const int* cand, int T, const double* closest, double* out,
                            double* pot, double* ws, void* stream);
 
+/* ---- state boundaries (csrc/segment.hip) ---------------------------------------------------------------------
+ * Where do the states change?  The optimal partition of the N rows of X f32 [N][L] (in time order) into K contiguous
+ * segments with the least within-segment sum of squared deviations, by the exact dynamic programme over (segments, end
+ * row); segments.py traces and scores it.  2 <= N <= 65536, 1 <= L <= 128, 1 <= K <= 256, min_size >= 1,
+ * K min_size <= N (rbvae_segment_ok); anything else makes every entry return RBVAE_E_UNSUPPORTED without a launch.  All
+ * arithmetic is f64, never contracted, l ascending.  No floating-point atomics: two runs agree bit for bit.
+ *
+ * rbvae_segment_prefix: P f64 [N + 1][L] and Q f64 [N + 1], the running sums of the rows and of r_i = sum_l x_il^2, with
+ * P[0] = 0 and Q[0] = 0.  Rows are taken in blocks of 256: inside block b the local running sums start from the block's
+ * first row and add one row at a time, P[256 b + i + 1] = off_b + local_i, off_{b + 1} = off_b + local_last, off_0 = 0
+ * (numpy: off + np.cumsum(block, axis=0)).  X is not centred: on 0/1 codes every sum is an exact integer.
+ * rbvae_segment_layer: cost(s, t) = (Q[t] - Q[s]) - d2(P[t], P[s]) / (double)(t - s), d2 = sum_l (a_l - b_l)^2 (not clamped
+ * where rounding leaves it slightly negative).  For every end 0 <= t <= N the candidates are prev[s] + cost(s, t) over
+ * 0 <= s <= t - min_size with prev[s] finite (prev f64 [N + 1]); out f64 [N + 1] is the smallest in the order (value, s)
+ * ascending, arg int32 [N + 1] its s (a tie goes to the lower s), and (+inf, -1) where there is no candidate.  The minimum
+ * is exact: the result does not depend on how the starts are split over workgroups.  ws: rbvae_segment_ws_bytes(N, L).
+ * The table of K layers is D_1 = layer(prev = [0, +inf, ...]), D_k = layer(D_{k - 1}); D_k[N] is the cost of the best
+ * k-segmentation.
+ * rbvae_segment_trace: cost f64 [K][N + 1] and arg int32 [K][N + 1] are the table; cuts int32 [K][K]: row k - 1 holds the
+ * k - 1 interior boundaries of the best k-segmentation (each the position of the first row of a new segment) ascending,
+ * padded with -1; all -1 where D_k[N] is not finite.  A thread per k walks t <- arg[j][t] from t = N, j = k down to 2. */
+int rbvae_segment_ok(int N, int L, int K, int min_size);
+size_t rbvae_segment_ws_bytes(int N, int L);
+int rbvae_segment_prefix(const float* X, int N, int L, double* P, double* Q, void* stream);
+int rbvae_segment_layer(const double* P, const double* Q, int N, int L, const double* prev, int min_size, double* out,
+                        int* arg, void* ws, void* stream);
+int rbvae_segment_trace(const int* arg, int N, int K, const double* cost, int* cuts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,3 +32,6 @@ from .scores import (continuity, knn_label_agreement, label_distance_sums, laten
 from . import symbols  # noqa: F401
 from .symbols import (KMeansResult, calinski_harabasz, cluster_sums, clustering_agreement, code_symbols,  # noqa: F401
                       contingency, davies_bouldin, kmeans, kmeans_plusplus, latent_symbols)
+from . import segments  # noqa: F401
+from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
+                       segment_layer, segment_prefix, segment_table)
