@@ -235,3 +235,19 @@ def assert_guards(g, what=""):
     unwritten = (sent & inner).nonzero()
     assert unwritten.shape[0] == 0, (f"{what}: {unwritten.shape[0]} output elements were never written; first at "
                                      f"(row {int(unwritten[0, 0]) - g.g}, col {int(unwritten[0, 1])})")
+
+
+def assert_guards_where(g, written, what=""):
+    """assert_guards for an output that declares only part of its interior (a strided scatter, an offset workspace):
+    `written` marks the declared elements of g.view ([rows][ld], or [n] of a GuardedFlat); everything else, inside the
+    interior and around it, still holds the sentinel, and every declared element was written."""
+    ib, pat = SENTINEL[g.dtype]
+    sent = g.buf.view(ib).cpu() == pat
+    inner = torch.zeros_like(sent)
+    inner[g.g:g.g + g.rows] = written.reshape(g.rows, -1).cpu()
+    stray = (~sent & ~inner).nonzero()
+    assert stray.shape[0] == 0, (f"{what}: {stray.shape[0]} undeclared elements were written; first at buffer "
+                                 f"(row {int(stray[0, 0]) - g.g}, col {int(stray[0, 1])}) relative to the interior")
+    unwritten = (sent & inner).nonzero()
+    assert unwritten.shape[0] == 0, (f"{what}: {unwritten.shape[0]} declared elements were never written; first at "
+                                     f"(row {int(unwritten[0, 0]) - g.g}, col {int(unwritten[0, 1])})")
