@@ -860,6 +860,54 @@ int rbvae_segment_layer(const double* P, const double* Q, int N, int L, const do
                         int* arg, void* ws, void* stream);
 int rbvae_segment_trace(const int* arg, int N, int K, const double* cost, int* cuts, void* stream);
 
+/* ---- spectral layout (csrc/spectral.hip) ---------------------------------------------------------------------
+ * The lowest eigenvectors of L = I - S, S = D^-1/2 W D^-1/2, of a symmetric graph W in CSR (indptr int32 [N + 1], indices
+ * int32 [E], data f32 [E]; the fuzzy graph of rbvae_umap_smooth_knn's memberships), by Lanczos with full
+ * reorthogonalisation against a basis on the device; spectral.py enqueues the steps, solves the tridiagonal problem on the
+ * host and applies umap-learn's and scikit-learn's conventions.  2 <= N <= 1048576, E <= 2^31 - 1, 1 <= m_max <= 1024,
+ * 0 <= q <= 8 (rbvae_spectral_ok); anything else makes every entry return RBVAE_E_UNSUPPORTED without a launch, a NULL
+ * pointer or a workspace below rbvae_spectral_ws_bytes(N, m_max, q) RBVAE_E_INVALID.  All arithmetic is f64, never
+ * contracted.  No floating-point atomics: every sum has one fixed order and two runs agree bit for bit.
+ *
+ * rbvae_spectral_degree: deg_i = sum_e (double)data[e] over row i, e ascending from zero; isd_i = 1 / sqrt(deg_i), 0 where
+ * deg_i = 0.  An entry whose column is outside [0, N) is skipped, here and in the product.
+ * rbvae_spectral_matvec: y_i = isd_i * sum_e t_e, t_e = (double)data[e] * (isd_j * x_j), j = indices[e].  A wave per row:
+ * lane l of chunk n holds the row's edge 64 n + l (0 beyond the row), the chunk is added by a butterfly (lane l adds lane
+ * l ^ 32, then ^ 16, ... ^ 1), the chunk sums are added in order from zero.  y must not be x.
+ * rbvae_spectral_dots: c_k = V_k . w for the nv <= 1025 vectors V f64 [nv][N], in two stages.  Rows are taken in blocks of
+ * rbvae_spectral_block_rows() = 1024: in block b thread t (of 256) adds the products of its rows 1024 b + t + 256 s,
+ * s = 0..3, from zero (rows beyond N count 0), a butterfly adds each wave's 64 threads, the four waves' sums are added in
+ * wave order; c_k adds the blocks' partials in block order from zero.  ws: rbvae_spectral_ws_bytes(N, max(nv - 1, 1), 0).
+ * rbvae_spectral_update: w_i = w_i - s_i, s_i = sum_k c_k V_k[i] with k ascending from zero.
+ * rbvae_spectral_step: Lanczos step j on the basis V f64 [q + m_max + 1][N], whose first q rows are locked orthonormal
+ * vectors and whose row q + j is v_j (row q: the caller's unit start vector, orthogonal to the locked ones).  In order:
+ * w = S v_j into row q + j + 1 (the product above); twice: c = V_{0 .. q + j}^T w (the dots above), w -= V^T c (the update
+ * above); alpha[j] = the two passes' c_{q + j} added; beta[j] = sqrt(w . w) (the dots' sum); v_{j + 1} = w / beta[j].
+ * state int32 [2] = {broken, steps}, zero before step 0: steps = j + 1 once alpha[j] and beta[j] are written; beta[j] <=
+ * 2^-40 (or not a number) sets broken: the Krylov space is invariant, row q + j + 1 keeps the unnormalised remainder and is
+ * no basis vector, and every later step returns without writing anything, so steps may be enqueued ahead of the read.
+ * rbvae_spectral_ritz: Y f64 [cols][N], Y_c[i] = sum_j V[q + j][i] s[j][c] with j ascending from zero, for s f64 [m][cols]
+ * on the device, 1 <= cols <= 32, 1 <= m <= 1024.
+ * rbvae_spectral_residuals: res[c] = |S y_c - theta[c] y_c|_2 for Y f64 [cols][N], theta f64 [cols] on the device: the
+ * product above, r_i = (S y)_i - theta y_i, and sqrt(r . r) by the dots' sum.  ws: rbvae_spectral_ws_bytes(N, 1, 0). */
+int rbvae_spectral_ok(int N, int m_max, int q);
+int rbvae_spectral_block_rows(void);
+size_t rbvae_spectral_ws_bytes(int N, int m_max, int q);
+int rbvae_spectral_degree(const int* indptr, const int* indices, const float* data, int N, double* deg, double* isd,
+                          void* stream);
+int rbvae_spectral_matvec(const int* indptr, const int* indices, const float* data, const double* isd, int N,
+                          const double* x, double* y, void* stream);
+int rbvae_spectral_dots(const double* V, int nv, int N, const double* w, double* c, void* ws, size_t ws_bytes,
+                        void* stream);
+int rbvae_spectral_update(const double* V, int nv, int N, const double* c, double* w, void* stream);
+int rbvae_spectral_step(const int* indptr, const int* indices, const float* data, const double* isd, int N, double* V,
+                        int q, int j, int m_max, double* alpha, double* beta, int* state, void* ws, size_t ws_bytes,
+                        void* stream);
+int rbvae_spectral_ritz(const double* V, int q, int m, int N, const double* s, int cols, double* Y, void* stream);
+int rbvae_spectral_residuals(const int* indptr, const int* indices, const float* data, const double* isd, int N,
+                             const double* Y, int cols, const double* theta, double* res, void* ws, size_t ws_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

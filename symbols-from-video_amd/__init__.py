@@ -35,3 +35,6 @@ from .symbols import (KMeansResult, calinski_harabasz, cluster_sums, clustering_
 from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)
+from . import spectral  # noqa: F401
+from .spectral import (EigResult, NormalizedGraph, lanczos_eigsh, latent_spectral, normalized_graph,  # noqa: F401
+                       spectral_clustering, spectral_embedding, spectral_layout)

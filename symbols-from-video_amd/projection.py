@@ -22,9 +22,9 @@ umap.UMAP(n_neighbors=24, min_dist=0.25, metric='euclidean', random_state=42) (:
   umap_optimise    the edge schedule (entries below max(W) / n_epochs dropped, period = max(W) / W) and one launch per
                    epoch: attraction along the active edges, hashed negative samples, learning rate 1 - n / n_epochs
   umap_project     kNN graph, fuzzy graph, initial map, n_epochs = 500 (200 above 10 000 rows) epochs
-Two deliberate differences from umap-learn: the initial map is this module's exact PCA (scaled to
-[0, 10] with 1e-4 noise) instead of the spectral layout, and an epoch is synchronous: every vertex moves from the
-epoch-start map, the attraction of an edge counted twice for the mirror edge's move of the other end, negatives drawn by a
+Two deliberate differences from umap-learn: the default initial map is this module's exact PCA
+(scaled to [0, 10] with 1e-4 noise); umap-learn's own default, the spectral layout of the graph, is init="spectral"
+(spectral.py).  And an epoch is synchronous: every vertex moves from the epoch-start map, the attraction of an edge counted twice for the mirror edge's move of the other end, negatives drawn by a
 counter hash, so that two runs with one seed agree bit for bit.  The plots stay with the caller.
 There is no host path: inputs on the CPU raise.
 """
@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import dataclasses
 import time
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -384,11 +384,13 @@ def umap_schedule(indptr: np.ndarray, indices: np.ndarray, data: np.ndarray, n_e
 
 @dataclasses.dataclass
 class UMAPResult:
-    """embedding f32 [N, 2] on the device; the epochs run and the curve parameters used"""
+    """embedding f32 [N, 2] on the device; the epochs run and the curve parameters used; init: where the initial map came
+    from, "pca", "spectral" or "given" ("pca" after init="spectral" on a graph of several components)"""
     embedding: torch.Tensor
     n_epochs: int
     a: float
     b: float
+    init: str = "given"
 
 
 def umap_optimise(Y0: torch.Tensor, graph: UMAPGraph, n_epochs: Optional[int] = None, a: Optional[float] = None,
@@ -438,12 +440,15 @@ def umap_initial_map(pca_embedding: np.ndarray, seed: int = 42) -> np.ndarray:
 
 
 def umap_project(X: torch.Tensor, n_neighbors: int = 15, min_dist: float = 0.1, spread: float = 1.0,
-                 n_epochs: Optional[int] = None, seed: int = 42, init: Optional[torch.Tensor] = None,
+                 n_epochs: Optional[int] = None, seed: int = 42, init: Union[None, str, torch.Tensor] = None,
                  timings: Optional[dict] = None) -> UMAPResult:
     """umap.UMAP(n_neighbors, min_dist, metric='euclidean', random_state=seed).fit_transform(X) (:63-64) for X f32 [N, L]
-    on the device, as this module states it: the exact kNN graph, the synchronous epoch and, unless `init` f32 [N, 2] is
-    given, umap_initial_map of the exact PCA.  timings: a dict that receives the device milliseconds of "knn",
-    "smooth_knn", "pca" and "epochs", and the host's wall milliseconds for "fuzzy_csr"."""
+    on the device, as this module states it: the exact kNN graph, the synchronous epoch and an initial map: init None or
+    "pca": umap_initial_map of the exact PCA; "spectral": umap_initial_map of spectral.spectral_layout(graph, 2) of the
+    graph just built (umap-learn's default), falling back to the PCA map when the graph has several components; an f32
+    [N, 2] device tensor: that map.  UMAPResult.init says which was used.  timings: a dict that receives the device
+    milliseconds of "knn", "smooth_knn", "pca" and "epochs", and the host's wall milliseconds for "fuzzy_csr" and
+    "spectral"."""
     X = _device_matrix(X, "X")
     N = X.shape[0]
     k = int(n_neighbors)
@@ -459,16 +464,30 @@ def umap_project(X: torch.Tensor, n_neighbors: int = 15, min_dist: float = 0.1, 
     graph = fuzzy_graph(knn[0], knn[1], k, timers=t)
     if timings is not None:
         timings["fuzzy_csr"] = 1e3 * (time.perf_counter() - t0)     # includes the wait for the kNN and smooth-kNN launches
-    if init is None:
+    if isinstance(init, str) and init not in ("pca", "spectral"):
+        raise ValueError(f"init must be 'pca', 'spectral', None or the initial map, got {init!r}")
+    used, Y0 = "given", None
+    if isinstance(init, str) and init == "spectral":
+        from . import spectral
+        t1 = time.perf_counter()
+        ng = spectral.normalized_graph(graph)
+        if ng.n_components == 1:
+            lay = spectral.spectral_layout(ng, 2)
+            Y0, used = torch.from_numpy(umap_initial_map(lay.cpu().numpy(), seed)).to(X.device), "spectral"
+        if timings is not None:
+            timings["spectral"] = 1e3 * (time.perf_counter() - t1)
+    if Y0 is None and (init is None or isinstance(init, str)):
         t.span("pca", lambda: res.append(pca_project(X, 2)))
         t.close()
-        Y0 = torch.from_numpy(umap_initial_map(res[0].embedding.cpu().numpy(), seed)).to(X.device)
-    else:
+        Y0, used = torch.from_numpy(umap_initial_map(res[0].embedding.cpu().numpy(), seed)).to(X.device), "pca"
+    elif Y0 is None:
         t.close()
         Y0 = _device_matrix(init, "init")
         if tuple(Y0.shape) != (N, 2):
             raise ValueError(f"init must be [{N}, 2], got {tuple(Y0.shape)}")
-    return umap_optimise(Y0, graph, n_epochs, a, b, seed=seed, timings=timings)
+    else:
+        t.close()
+    return dataclasses.replace(umap_optimise(Y0, graph, n_epochs, a, b, seed=seed, timings=timings), init=used)
 
 
 @torch.no_grad()
