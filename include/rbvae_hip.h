@@ -832,6 +832,49 @@ int rbvae_kmeans_decide(const double* shift2, int K, double tol_abs, int max_ite
 int rbvae_kmeans_pp_trials(const float* X, int N, int L, const int* cand, int T, const double* closest, double* out,
                            double* pot, double* ws, void* stream);
 
+/* ---- Gaussian mixture (csrc/gmm.hip) -------------------------------------------------------------------------
+ * How many states are there, and how sure is each frame's?  A diagonal-covariance Gaussian mixture of X f32 [N][L] fitted
+ * by EM as scikit-learn 1.7.2's GaussianMixture(covariance_type="diag", n_init=1) fits it; mixture.py enqueues the
+ * iterations and finishes BIC and AIC on the host.  means, covars, prec_chol f64 [K][L] (prec_chol: s_kl = 1 / sqrt(var_kl),
+ * scikit-learn's precisions_cholesky_), weights, logc f64 [K], resp f64 [K][N] (component-major).  1 <= L <= 128,
+ * 1 <= K <= 256, K <= N <= 1048576 and N K <= 2^26, since resp is materialised (rbvae_gmm_ok); anything else makes every
+ * entry return RBVAE_E_UNSUPPORTED without a launch.  All arithmetic is f64, never contracted; exp, log and sqrt are the
+ * device library's.  No floating-point atomics: every sum has one fixed order and two runs agree bit for bit.
+ *
+ * state int32 [4] = {done, n_iter, why (1 converged, 2 max_iter), 0}, zero before the first iteration; may be NULL in
+ * rbvae_gmm_estep and rbvae_gmm_mstep.  With done set, estep, mstep and decide return without writing anything, so
+ * iterations may be enqueued ahead of the decision.  Only rbvae_gmm_decide writes state.
+ * rbvae_gmm_estep: lp_ik = logc_k - (1 / 2) q_ik, q_ik = sum_l t^2 with t = (x_il - mu_kl) s_kl and l ascending from zero
+ * (the difference, the product and the square round once each), logc_k = log w_k + sum_l log s_kl - (1 / 2) L log 2 pi as
+ * rbvae_gmm_mstep writes it; m_i = max_k lp_ik; lognorm_i = m_i + log(sum_k exp(lp_ik - m_i)) with k ascending from zero;
+ * resp_ki = exp(lp_ik - lognorm_i); label_i = the k of the largest lp_ik (a tie goes to the lower k).  lognorm f64 [N];
+ * resp and label int32 [N] may be NULL (scoring, prediction).  The means and roots pass through LDS
+ * rbvae_gmm_chunk_components(L) = 2048 / round_up(L, 8) components at a time.  resp is first used to hold lp.
+ * rbvae_gmm_mstep: two-pass and centred, each pass in two stages.  min(256, ceil(N / 256)) blocks of ceil(N / blocks)
+ * consecutive rows; each cell's partial is added in ascending row order from zero, the partials then in block order from
+ * zero.  nk_k = sum_i resp_ki + 10 * 2^-52; mu_kl = (sum_i resp_ki x_il) / nk_k; var_kl = (sum_i resp_ki d^2) / nk_k +
+ * reg_covar with d = x_il - mu_kl (d, d^2 and the product round once each); weights_k = nk_k / sum_k nk_k (k ascending from
+ * zero); s_kl = 1 / sqrt(var_kl); logc_k = (log weights_k + sum_l log s_kl) - (1 / 2) L log 2 pi (l ascending from zero,
+ * log 2 pi = 1.8378770664093453).  A component without mass follows the same formulas: nk = 10 * 2^-52, mean 0, variance
+ * reg_covar.  ws: rbvae_gmm_ws_bytes(N, L, K) = 16 blocks K (L + 1) bytes, the two passes' block partials f64
+ * [2][blocks][K][L + 1]: cell (k, l) of the first holds the block's sum of resp_ki x_il and cell (k, L) that of resp_ki, cell
+ * (k, l) of the second that of resp_ki d^2 and cell (k, L) zero.
+ * rbvae_gmm_decide: now = (sum_i lognorm_i) / N in rbvae_spectral_dots' order (blocks of 1024 rows: thread t of 256 adds its
+ * rows 1024 b + t + 256 s, s = 0..3, from zero, a butterfly adds each wave's 64 threads, the four waves' sums are added in
+ * wave order from zero, the blocks' sums in block order from zero); n_iter += 1; history[n_iter - 1] = now (history f64
+ * [max_iter]); |now - lb[0]| < tol: done, converged; else n_iter >= max_iter: done; lb[0] = now.  lb f64 [1] holds -inf before
+ * the first iteration. */
+int rbvae_gmm_ok(int N, int L, int K);
+int rbvae_gmm_chunk_components(int L);
+size_t rbvae_gmm_ws_bytes(int N, int L, int K);
+int rbvae_gmm_estep(const float* X, int N, int L, const double* means, const double* prec_chol, const double* logc, int K,
+                    double* resp, double* lognorm, int* label, const int* state, void* stream);
+int rbvae_gmm_mstep(const float* X, int N, int L, const double* resp, int K, double reg_covar, double* weights,
+                    double* means, double* covars, double* prec_chol, double* logc, double* ws, const int* state,
+                    void* stream);
+int rbvae_gmm_decide(const double* lognorm, int N, double tol, int max_iter, double* lb, double* history, int* state,
+                     void* stream);
+
 /* ---- state boundaries (csrc/segment.hip) ---------------------------------------------------------------------
  * Where do the states change?  The optimal partition of the N rows of X f32 [N][L] (in time order) into K contiguous
  * segments with the least within-segment sum of squared deviations, by the exact dynamic programme over (segments, end

@@ -32,6 +32,9 @@ from .scores import (continuity, knn_label_agreement, label_distance_sums, laten
 from . import symbols  # noqa: F401
 from .symbols import (KMeansResult, calinski_harabasz, cluster_sums, clustering_agreement, code_symbols,  # noqa: F401
                       contingency, davies_bouldin, kmeans, kmeans_plusplus, latent_symbols)
+from . import mixture  # noqa: F401
+from .mixture import (GMMResult, gmm, gmm_aic, gmm_bic, gmm_predict, gmm_predict_proba, gmm_score,  # noqa: F401
+                      gmm_score_samples, gmm_select, latent_mixture)
 from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)
