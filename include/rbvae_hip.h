@@ -951,6 +951,65 @@ int rbvae_spectral_residuals(const int* indptr, const int* indices, const float*
                              const double* Y, int cols, const double* theta, double* res, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---- hidden Markov model (csrc/hmm.hip) ----------------------------------------------------------------------
+ * Which state is each frame in, given its neighbours in time?  One sequence X f32 [N][L] in time order, K states with the
+ * mixture's diagonal Gaussian emissions (means, prec_chol f64 [K][L]), pi f64 [K] and a row-stochastic A f64 [K][K] (zeros
+ * allowed); hmm.py drives Baum-Welch with rbvae_gmm_mstep and rbvae_gmm_decide.  1 <= L <= 128, 1 <= K <= 64,
+ * max(K, 2) <= N <= 1048576 and N K <= 2^26 (rbvae_hmm_ok; inside rbvae_gmm_ok): anything else makes every entry return
+ * RBVAE_E_UNSUPPORTED without a launch; a NULL pointer, block_rows < 1 or a workspace below
+ * rbvae_hmm_ws_bytes(N, K, block_rows) RBVAE_E_INVALID.  All arithmetic is f64, never contracted; exp and log are the device
+ * library's.  No floating-point atomics: every sum has one fixed order and two runs agree bit for bit.
+ *
+ * state is the mixture's int32 [4] = {done, n_iter, why, 0} and may be NULL; with done set every entry returns without
+ * writing anything.  status int32 [2] = {the number of normalisers that are 0 or not finite, the first row with one}: the
+ * caller sets it to {0, 2^31 - 1} and the entries add to the count and lower the row (integer atomics); nothing else is
+ * done about such a row, whose quotients are what IEEE division gives.
+ * rbvae_hmm_emit: lb_kt = c_k - q_kt / 2 with q_kt as rbvae_gmm_estep's and c_k = (sum_l log s_kl) - (1 / 2) L log 2 pi, l
+ * ascending from zero (no mixture weight).  logb f64 [K][N] = lb; rowmax f64 [N]: m_t = max_k lb_kt; e f64 [N][K]:
+ * e_tk = exp(lb_kt - m_t).
+ * The recurrence.  SUM(y) over the states is a butterfly over 64 lanes, lane j holding y_j and the lanes from K on zero:
+ * lane l adds lane l ^ 32, then ^ 16, ... ^ 1 (a halving tree: 0..31 + 32..63, then 0..15 + 16..31, ...).  DOT_j(x, M) =
+ * sum_i x_i M_ij with i ascending from zero, every product rounded before it is added.
+ * rbvae_hmm_forward: y_0 = pi e_0 (element-wise), y_t = DOT(alpha_(t-1), A) e_t, c_t = SUM(y_t), alpha_t = y_t / c_t,
+ * ll_t = log c_t + m_t.  alpha f64 [N][K], ll f64 [N].
+ * rbvae_hmm_backward: beta_(N-1) = 1 / K, x = e_(t+1) beta_(t+1) (element-wise), y_ti = sum_j A_ij x_j with j ascending from
+ * zero, beta_t = y_t / SUM(y_t): its own normalisation, independent of c.  beta f64 [N][K].
+ * Both run over blocks of block_rows consecutive rows (rbvae_hmm_block_rows() = 64 is the default; ceil(N / block_rows)
+ * blocks; block_rows >= N is the plain recursion in one launch), in three launches.  (i) For every block but the last
+ * (backward: the first) and every state i, the unit vector of state i is carried through the block's rows by the step above,
+ * u = y / SUM(y) after every row (zeros once SUM(y) = 0) with s_i = the sum of log SUM(y) over the rows in the order they are
+ * taken (-inf once dead); the block that holds the recursion's first row carries the recursion itself.  (ii) One wave walks
+ * the blocks in order: the vector v that enters block b leaves it as y / SUM(y) (zeros where that is 0) with
+ * y_j = sum_i w_i u_ij, i ascending from zero, w_i = v_i exp(s_i - max_i s_i), 0 where s_i = -inf.  (iii) Every block takes
+ * the plain recursion from the vector that enters it and writes its rows.  ws: rbvae_hmm_ws_bytes(N, K, block_rows) =
+ * 8 max(blocks (K K + 2 K), N + xblocks K K) bytes, xblocks = min(256, ceil(N / 256)).
+ * rbvae_hmm_posterior: gamma_kt = (alpha_tk beta_tk) / g_t, g_t = sum_k alpha_tk beta_tk with k ascending from zero; gamma
+ * f64 [K][N] (component-major, as rbvae_gmm_mstep reads it).  n_t(i, j) = (alpha_ti A_ij) (e_(t+1)j beta_(t+1)j),
+ * Z_t = sum_i sum_j n_t(i, j), one running sum from zero with i ascending and j ascending inside it.  xi f64 [K][K]:
+ * Xi_ij = sum_t n_t(i, j) / Z_t over t = 0 .. N - 2 in two stages like the M-step: xblocks blocks of ceil(N / xblocks)
+ * consecutive rows, a cell's partial added in ascending row order from zero, the partials in block order from zero.
+ * A_new_ij = (Xi_ij + eps / K) / (sum_j Xi_ij + eps), j ascending from zero, eps = 10 * 2^-52 (a state without mass gets a
+ * uniform row); pi_new_k = gamma_k0.  A_new may be A and pi_new pi.  Every g_t and Z_t that is 0 or not finite counts into
+ * status.
+ * rbvae_hmm_viterbi: log_pi f64 [K] and log_A f64 [K][K] come from the host (log 0 = -inf).  d_0j = log_pi_j + lb_j0;
+ * d_tj = max_i(d_(t-1)i + log_A_ij) + lb_jt, back_tj = the lowest i that attains the maximum (back_0j = 0); the last state
+ * is the lowest j that attains max_j d_(N-1)j, score[0] that maximum; path_(t-1) = back_t[path_t].  back uint8 [N][K],
+ * path int32 [N].  Only additions and comparisons. */
+int rbvae_hmm_ok(int N, int L, int K);
+int rbvae_hmm_block_rows(void);
+size_t rbvae_hmm_ws_bytes(int N, int K, int block_rows);
+int rbvae_hmm_emit(const float* X, int N, int L, const double* means, const double* prec_chol, int K, double* logb,
+                   double* rowmax, double* e, const int* state, void* stream);
+int rbvae_hmm_forward(const double* e, const double* rowmax, int N, int K, const double* pi, const double* A, int block_rows,
+                      double* alpha, double* ll, int* status, void* ws, size_t ws_bytes, const int* state, void* stream);
+int rbvae_hmm_backward(const double* e, int N, int K, const double* A, int block_rows, double* beta, int* status, void* ws,
+                       size_t ws_bytes, const int* state, void* stream);
+int rbvae_hmm_posterior(const double* alpha, const double* beta, const double* e, int N, int K, const double* A,
+                        double* gamma, double* xi, double* A_new, double* pi_new, int* status, void* ws, size_t ws_bytes,
+                        const int* state, void* stream);
+int rbvae_hmm_viterbi(const double* logb, int N, int K, const double* log_pi, const double* log_A, unsigned char* back,
+                      int* path, double* score, const int* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

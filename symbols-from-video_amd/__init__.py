@@ -35,6 +35,10 @@ from .symbols import (KMeansResult, calinski_harabasz, cluster_sums, clustering_
 from . import mixture  # noqa: F401
 from .mixture import (GMMResult, gmm, gmm_aic, gmm_bic, gmm_predict, gmm_predict_proba, gmm_score,  # noqa: F401
                       gmm_score_samples, gmm_select, latent_mixture)
+from . import hmm as _hmm_module  # noqa: F401  (the module is sfv.hmm_model: the name hmm is the fit, as gmm is the mixture's)
+from .hmm import (HMMResult, hmm, hmm_aic, hmm_bic, hmm_forward_backward, hmm_predict, hmm_predict_proba,  # noqa: F401
+                  hmm_score, hmm_score_samples, hmm_select, hmm_viterbi, latent_hmm)
+hmm_model = _hmm_module
 from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)
