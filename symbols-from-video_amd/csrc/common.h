@@ -51,6 +51,28 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// The f64 butterfly: every lane ends with the same bits.  Its own name, not an overload: no float call site can change
+// meaning by a conversion.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The block's THREADS (= blockDim.x, a power of two) f64 values summed by a fixed halving tree over red[THREADS] in LDS;
+// every thread must call it and every thread returns the total.
+template <int THREADS>
+__device__ __forceinline__ double block_tree_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
 
 // Sum over the whole block in a FIXED order (bitwise reproducible).  `red` holds
 // one float per wave; every thread returns the total.

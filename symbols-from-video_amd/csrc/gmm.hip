@@ -6,18 +6,18 @@
 //                   address (broadcast).  The first sweep over the components stores lp into resp's column of the row and
 //                   keeps the largest (lp, lowest k); the lane then reads its own values back for the sum of exp(lp - m)
 //                   and once more for resp = exp(lp - lognorm).  Without resp the sweep runs twice instead.
-//   gmm_partial_k   stage one of the M-step, run twice: a workgroup owns a block of rows (at most GU_BLOCKS blocks) and 256
+//   gmm_partial_k   stage one of the M-step, run twice: a workgroup owns a block of rows (diag_gauss.h's row_blocks) and 256
 //                   cells (k, c) of [K][L + 1]; a thread walks the block's rows in ascending order and adds r_ki x_ic
 //                   (c = L: r_ki alone).  The centred run first rebuilds nk_k and mu_kc from the first run's partials, in
 //                   block order, and adds r_ki (x_ic - mu_kc)^2.
 //   gmm_finish_k    stage two: a workgroup per component adds the partials in block order and writes weights, means,
 //                   covars, prec_chol and logc
-//   gmm_decide_k    one workgroup: the mean of lognorm in spectral.hip's two-stage order, the history and the stopping rules
+//   gmm_decide_k    one workgroup: the mean of lognorm in sp_dots_k's two-stage order (spectral.hip), the history and the stopping rules
 // state int32 [4] = {done, n_iter, why, 0}: every kernel returns at once when done is set, so the host may enqueue
 // iterations ahead of the decision.  No floating-point atomics; two runs agree bit for bit.  Contraction is off.
 #include "common.h"
+#include "diag_gauss.h"
 
-#include <float.h>
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -25,29 +25,13 @@
 namespace rbvae {
 
 constexpr int GM_THREADS = 256;
-constexpr int GM_MAX_L = 128, GM_MAX_K = 256, GM_MAX_N = 1 << 20;
-constexpr long GM_MAX_NK = 1L << 26;    // resp is materialised: N K f64 values, 512 MB at most
-constexpr int GM_CHUNK = 4096;          // f64 values of means and precision roots per LDS chunk (32 KB)
-constexpr int GU_BLOCKS = 256;          // row blocks of the M-step at most
-constexpr int GD_ROWS = 1024;           // rows per block of the lower bound's sum (spectral.hip's SP_ROWS)
+constexpr int GM_MAX_K = 256, GM_MAX_N = 1 << 20;
+constexpr int GD_ROWS = 1024;           // rows per block of the lower bound's sum: sp_dots_k's blocks (spectral.hip)
 constexpr int GST_DONE = 0, GST_ITER = 1, GST_WHY = 2;
-constexpr double GM_NK_EPS = 10.0 * DBL_EPSILON;            // scikit-learn: 10 * np.finfo(float64).eps
-constexpr double GM_LOG_2PI = 1.8378770664093453;           // np.log(2 * np.pi)
 
-// lp = logc - q / 2, q = sum_l ((x_l - mu_l) s_l)^2 with l ascending; p holds Lp means and then Lp precision roots
+// lp = logc - q / 2
 __device__ __forceinline__ double gm_lp(const float* xi, const double* p, int L, int Lp, double logc) {
-    double q = 0.0;
-#pragma unroll
-    for (int l0 = 0; l0 < GM_MAX_L; l0 += 8) {
-        if (l0 < L) {
-#pragma unroll
-            for (int l = l0; l < l0 + 8; ++l) {
-                const double t = ((double)xi[l] - p[l]) * p[Lp + l];       // padding: (0 - 0) * 0 adds an exact +0
-                q += t * t;
-            }
-        }
-    }
-    return logc - 0.5 * q;
+    return logc - 0.5 * diag_gauss_q(xi, p, L, Lp);
 }
 
 __global__ __launch_bounds__(GM_THREADS) void gmm_estep_k(const float* __restrict__ X, int N, int L,
@@ -56,17 +40,17 @@ __global__ __launch_bounds__(GM_THREADS) void gmm_estep_k(const float* __restric
                                                           const double* __restrict__ logc, int K, double* resp,
                                                           double* __restrict__ lognorm, int* __restrict__ label,
                                                           const int* __restrict__ state) {
-    __shared__ __attribute__((aligned(16))) double ps[GM_CHUNK];
-    __shared__ double lc[GM_CHUNK / 16];
+    __shared__ __attribute__((aligned(16))) double ps[DG_CHUNK];
+    __shared__ double lc[DG_CHUNK / 16];
     if (state && state[GST_DONE]) return;                   // the same in every workgroup: only gmm_decide_k writes it
     const int tid = threadIdx.x;
     const int i = blockIdx.x * GM_THREADS + tid;
     const bool live = i < N;
     const int Lp = (L + 7) & ~7;                            // the row stride in LDS; the padding holds zeros
-    const int KC = GM_CHUNK / (2 * Lp);
-    float xi[GM_MAX_L];                                     // zeros beyond L
+    const int KC = DG_CHUNK / (2 * Lp);
+    float xi[DG_MAX_L];                                     // zeros beyond L
 #pragma unroll
-    for (int l = 0; l < GM_MAX_L; ++l) xi[l] = (live && l < L) ? X[(long)i * L + l] : 0.f;
+    for (int l = 0; l < DG_MAX_L; ++l) xi[l] = (live && l < L) ? X[(long)i * L + l] : 0.f;
     double m = -INFINITY, s = 0.0;
     int bk = 0;
     // with resp: one sweep that stores lp; without: a second sweep computes the same lp again for the sum
@@ -115,7 +99,7 @@ __device__ __forceinline__ void gm_block_sums(const double* __restrict__ ws1, in
         a += p[LS - 1];
         b += p[c];
     }
-    nk = a + GM_NK_EPS;
+    nk = a + DG_NK_EPS;
     sx = b;
 }
 
@@ -158,14 +142,14 @@ __global__ __launch_bounds__(GM_THREADS) void gmm_finish_k(const double* __restr
                                                            double* __restrict__ covars, double* __restrict__ prec,
                                                            double* __restrict__ logc, const int* __restrict__ state) {
     __shared__ double nks[GM_MAX_K];
-    __shared__ double logs[GM_MAX_L];
+    __shared__ double logs[DG_MAX_L];
     __shared__ double total;
     if (state && state[GST_DONE]) return;
     const int c = threadIdx.x, k = blockIdx.x, LS = L + 1;
     if (c < K) {                                            // every component's nk: the weights' denominator
         double a = 0.0;
         for (int blk = 0; blk < blocks; ++blk) a += ws1[((long)blk * K + c) * LS + L];
-        nks[c] = a + GM_NK_EPS;
+        nks[c] = a + DG_NK_EPS;
     }
     __syncthreads();
     if (c == 0) {
@@ -190,14 +174,8 @@ __global__ __launch_bounds__(GM_THREADS) void gmm_finish_k(const double* __restr
         double t = 0.0;
         for (int l = 0; l < L; ++l) t += logs[l];
         weights[k] = w;
-        logc[k] = (log(w) + t) - 0.5 * L * GM_LOG_2PI;
+        logc[k] = (log(w) + t) - 0.5 * L * DG_LOG_2PI;
     }
-}
-
-__device__ __forceinline__ double gm_wave_sum(double v) {       // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // lb f64 [1]: the previous lower bound on entry (-inf before the first iteration), this one on return
@@ -214,7 +192,7 @@ __global__ __launch_bounds__(GM_THREADS) void gmm_decide_k(const double* __restr
             const int i = b * GD_ROWS + tid + GM_THREADS * j;
             v += i < N ? lognorm[i] : 0.0;
         }
-        v = gm_wave_sum(v);
+        v = wave_sum_f64(v);
         if ((tid & 63) == 0) wsum[b * 4 + (tid >> 6)] = v;
     }
     __syncthreads();
@@ -242,10 +220,8 @@ __global__ __launch_bounds__(GM_THREADS) void gmm_decide_k(const double* __restr
 }
 
 static bool gm_ok(int N, int L, int K) {
-    return L >= 1 && L <= GM_MAX_L && K >= 1 && K <= GM_MAX_K && N >= K && N <= GM_MAX_N && (long)N * K <= GM_MAX_NK;
+    return L >= 1 && L <= DG_MAX_L && K >= 1 && K <= GM_MAX_K && N >= K && N <= GM_MAX_N && (long)N * K <= DG_MAX_NK;
 }
-static int gu_blocks(int N) { const int b = cdiv(N, GM_THREADS); return b < GU_BLOCKS ? b : GU_BLOCKS; }
-static int gu_rows(int N) { return cdiv(N, gu_blocks(N)); }
 
 }  // namespace rbvae
 
@@ -256,18 +232,18 @@ using namespace rbvae;
         if (!gm_ok(N, L, K))                                                                                          \
             return fail(RBVAE_E_UNSUPPORTED,                                                                          \
                         name ": (N=%d, L=%d, K=%d) outside 1 <= L <= %d, 1 <= K <= %d, K <= N <= %d, N K <= %ld", N, L, K, \
-                        GM_MAX_L, GM_MAX_K, GM_MAX_N, GM_MAX_NK);                                                     \
+                        DG_MAX_L, GM_MAX_K, GM_MAX_N, DG_MAX_NK);                                                     \
     } while (0)
 
 extern "C" int rbvae_gmm_ok(int N, int L, int K) { return gm_ok(N, L, K) ? 1 : 0; }
 
 extern "C" int rbvae_gmm_chunk_components(int L) {
-    return L >= 1 && L <= GM_MAX_L ? GM_CHUNK / (2 * ((L + 7) & ~7)) : 0;
+    return L >= 1 && L <= DG_MAX_L ? DG_CHUNK / (2 * ((L + 7) & ~7)) : 0;
 }
 
 extern "C" size_t rbvae_gmm_ws_bytes(int N, int L, int K) {
     if (!gm_ok(N, L, K)) return 0;
-    return sizeof(double) * 2 * (size_t)gu_blocks(N) * K * (L + 1);
+    return sizeof(double) * 2 * (size_t)row_blocks(N) * K * (L + 1);
 }
 
 extern "C" int rbvae_gmm_estep(const float* X, int N, int L, const double* means, const double* prec_chol,
@@ -287,7 +263,7 @@ extern "C" int rbvae_gmm_mstep(const float* X, int N, int L, const double* resp,
     GM_CHECK_SHAPE("gmm_mstep");
     RBVAE_CHECK_ARG(X && resp && weights && means && covars && prec_chol && logc && ws, "gmm_mstep: null pointer");
     RBVAE_CHECK_ARG(reg_covar >= 0.0, "gmm_mstep: reg_covar=%g", reg_covar);
-    const int blocks = gu_blocks(N), rows = gu_rows(N);
+    const int blocks = row_blocks(N), rows = row_block_rows(N);
     const dim3 grid(blocks, cdiv((long)K * (L + 1), GM_THREADS));
     double* ws2 = ws + (size_t)blocks * K * (L + 1);
     hipLaunchKernelGGL(gmm_partial_k<false>, grid, dim3(GM_THREADS), 0, (hipStream_t)stream, X, N, L, resp, K, rows,

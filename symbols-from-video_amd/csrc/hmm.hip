@@ -1,4 +1,4 @@
-// Hidden Markov model of the soft latents in time order: the mixture's diagonal Gaussian emissions (csrc/gmm.hip), a K x K
+// Hidden Markov model of the soft latents in time order: the mixture's diagonal Gaussian emissions (csrc/diag_gauss.h), a K x K
 // transition matrix, the scaled forward and backward recursions, the smoothed posterior, the expected transition counts and
 // the most likely state sequence (hmm.py drives Baum-Welch with rbvae_gmm_mstep and rbvae_gmm_decide and finishes BIC / AIC
 // on the host).  DESIGN.md section 7 has the formulation; include/rbvae_hip.h every order.
@@ -17,8 +17,8 @@
 // state int32 [4] is the mixture's {done, n_iter, why, 0}: every kernel returns at once when done is set.  No floating-point
 // atomics (status takes integer atomics, which commute); two runs agree bit for bit.  Contraction is off.
 #include "common.h"
+#include "diag_gauss.h"
 
-#include <float.h>
 #include <limits.h>
 #include <math.h>
 
@@ -26,54 +26,33 @@
 
 namespace rbvae {
 
-constexpr int HM_MAX_L = 128, HM_MAX_K = 64, HM_MAX_N = 1 << 20;
-constexpr long HM_MAX_NK = 1L << 26;
+constexpr int HM_MAX_K = 64, HM_MAX_N = 1 << 20;
 constexpr int HM_BLOCK_ROWS = 64;       // the default block of the recurrence: a constant, never derived from the device
 constexpr int HM_THREADS = 256;
-constexpr int HM_CHUNK = 4096;          // f64 values of means and precision roots per LDS chunk (gmm.hip's GM_CHUNK)
-constexpr int HX_BLOCKS = 256;          // row blocks of the transition counts at most (gmm.hip's GU_BLOCKS)
 constexpr int HG_ROWS = 64;             // rows per workgroup of hmm_gamma_k
 constexpr int HV_ROWS = 256;            // rows of backpointers per LDS chunk of the backtrace
 constexpr int HST_DONE = 0;
-constexpr double HM_EPS = 10.0 * DBL_EPSILON;               // the mixture's nk epsilon
-constexpr double HM_LOG_2PI = 1.8378770664093453;           // np.log(2 * np.pi)
-
-// gmm.hip's gm_lp without the constant: q = sum_l ((x_l - mu_l) s_l)^2 with l ascending
-__device__ __forceinline__ double hm_q(const float* xi, const double* p, int L, int Lp) {
-    double q = 0.0;
-#pragma unroll
-    for (int l0 = 0; l0 < HM_MAX_L; l0 += 8) {
-        if (l0 < L) {
-#pragma unroll
-            for (int l = l0; l < l0 + 8; ++l) {
-                const double t = ((double)xi[l] - p[l]) * p[Lp + l];       // padding: (0 - 0) * 0 adds an exact +0
-                q += t * t;
-            }
-        }
-    }
-    return q;
-}
 
 __global__ __launch_bounds__(HM_THREADS) void hmm_emit_k(const float* __restrict__ X, int N, int L,
                                                          const double* __restrict__ means,
                                                          const double* __restrict__ prec, int K, double* logb,
                                                          double* __restrict__ rowmax, double* __restrict__ e,
                                                          const int* __restrict__ state) {
-    __shared__ __attribute__((aligned(16))) double ps[HM_CHUNK];
+    __shared__ __attribute__((aligned(16))) double ps[DG_CHUNK];
     __shared__ double lc[HM_MAX_K];
     if (state && state[HST_DONE]) return;
     const int tid = threadIdx.x;
     const int i = blockIdx.x * HM_THREADS + tid;
     const bool live = i < N;
     const int Lp = (L + 7) & ~7;
-    const int KC = HM_CHUNK / (2 * Lp);
-    float xi[HM_MAX_L];
+    const int KC = DG_CHUNK / (2 * Lp);
+    float xi[DG_MAX_L];
 #pragma unroll
-    for (int l = 0; l < HM_MAX_L; ++l) xi[l] = (live && l < L) ? X[(long)i * L + l] : 0.f;
+    for (int l = 0; l < DG_MAX_L; ++l) xi[l] = (live && l < L) ? X[(long)i * L + l] : 0.f;
     if (tid < K) {                                          // c_k = sum_l log s_kl - L / 2 log 2 pi, l ascending from zero
         double t = 0.0;
         for (int l = 0; l < L; ++l) t += log(prec[(long)tid * L + l]);
-        lc[tid] = t - 0.5 * L * HM_LOG_2PI;
+        lc[tid] = t - 0.5 * L * DG_LOG_2PI;
     }
     double m = -INFINITY;
     for (int k0 = 0; k0 < K; k0 += KC) {
@@ -86,7 +65,7 @@ __global__ __launch_bounds__(HM_THREADS) void hmm_emit_k(const float* __restrict
         }
         __syncthreads();
         for (int r = 0; r < n; ++r) {
-            const double lb = lc[k0 + r] - 0.5 * hm_q(xi, ps + r * 2 * Lp, L, Lp);
+            const double lb = lc[k0 + r] - 0.5 * diag_gauss_q(xi, ps + r * 2 * Lp, L, Lp);
             if (live) logb[(long)(k0 + r) * N + i] = lb;
             if (lb > m) m = lb;
         }
@@ -97,12 +76,6 @@ __global__ __launch_bounds__(HM_THREADS) void hmm_emit_k(const float* __restrict
 }
 
 // ---- the recurrence -------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ double hm_wave_sum(double v) {       // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ double hm_wave_max(double v) {
 #pragma unroll
@@ -137,7 +110,7 @@ __device__ __forceinline__ double hm_step(double v, double ev, const double (&a)
     const double x = FWD ? v : ev * v;
     const double s = hm_dot(x, a, K);
     const double y = FWD ? s * ev : s;
-    z = hm_wave_sum(y);
+    z = wave_sum_f64(y);
     return y;
 }
 
@@ -162,7 +135,7 @@ __global__ __launch_bounds__(64) void hmm_carry_k(const double* __restrict__ e, 
         int t = r0;
         if (own) {
             const double y = in ? pi[lane] * e[lane] : 0.0;
-            z = hm_wave_sum(y);
+            z = wave_sum_f64(y);
             v = z > 0.0 ? y / z : 0.0;
             t = 1;
         } else {
@@ -220,7 +193,7 @@ __global__ __launch_bounds__(64) void hmm_chain_k(int K, int blocks, const doubl
         const double mx = hm_wave_max(s);
         const double w = s == -INFINITY ? 0.0 : v * exp(s - mx);
         const double y = hm_dot(w, u, K);
-        const double z = hm_wave_sum(y);
+        const double z = wave_sum_f64(y);
         v = z > 0.0 ? y / z : 0.0;
         if (in) VIN[(long)(b + step) * K + lane] = v;
     }
@@ -246,7 +219,7 @@ __global__ __launch_bounds__(64) void hmm_rows_k(const double* __restrict__ e, c
         int t = r0;
         if (b == 0) {
             const double y = in ? pi[lane] * e[lane] : 0.0;
-            z = hm_wave_sum(y);
+            z = wave_sum_f64(y);
             v = y / z;
             if (in) out[lane] = v;
             if (lane == 0) ll[0] = log(z) + rowmax[0];
@@ -373,7 +346,7 @@ __global__ __launch_bounds__(HM_THREADS) void hmm_finish_k(const double* __restr
         pi_new[tid] = gamma[(long)tid * N];
     }
     __syncthreads();
-    for (int c = tid; c < K * K; c += HM_THREADS) A_new[c] = (xs[c] + HM_EPS / (double)K) / (rs[c / K] + HM_EPS);
+    for (int c = tid; c < K * K; c += HM_THREADS) A_new[c] = (xs[c] + DG_NK_EPS / (double)K) / (rs[c / K] + DG_NK_EPS);
 }
 
 // ---- Viterbi --------------------------------------------------------------------------------------------------------------
@@ -441,15 +414,13 @@ __global__ __launch_bounds__(64) void hmm_viterbi_k(const double* __restrict__ l
 }
 
 static bool hm_ok(int N, int L, int K) {
-    return L >= 1 && L <= HM_MAX_L && K >= 1 && K <= HM_MAX_K && N >= (K > 2 ? K : 2) && N <= HM_MAX_N &&
-           (long)N * K <= HM_MAX_NK;
+    return L >= 1 && L <= DG_MAX_L && K >= 1 && K <= HM_MAX_K && N >= (K > 2 ? K : 2) && N <= HM_MAX_N &&
+           (long)N * K <= DG_MAX_NK;
 }
-static int hx_blocks(int N) { const int b = cdiv(N, HM_THREADS); return b < HX_BLOCKS ? b : HX_BLOCKS; }
-static int hx_rows(int N) { return cdiv(N, hx_blocks(N)); }
 static size_t hm_ws_bytes(int N, int K, int R) {
     const size_t blocks = (size_t)cdiv(N, R);
     const size_t rec = blocks * ((size_t)K * K + 2 * (size_t)K);
-    const size_t post = (size_t)N + (size_t)hx_blocks(N) * K * K;
+    const size_t post = (size_t)N + (size_t)row_blocks(N) * K * K;
     return sizeof(double) * (rec > post ? rec : post);
 }
 
@@ -462,7 +433,7 @@ using namespace rbvae;
         if (!hm_ok(N, L, K))                                                                                           \
             return fail(RBVAE_E_UNSUPPORTED,                                                                           \
                         name ": (N=%d, L=%d, K=%d) outside 1 <= L <= %d, 1 <= K <= %d, max(K, 2) <= N <= %d, N K <= %ld", N, \
-                        L, K, HM_MAX_L, HM_MAX_K, HM_MAX_N, HM_MAX_NK);                                                \
+                        L, K, DG_MAX_L, HM_MAX_K, HM_MAX_N, DG_MAX_NK);                                                \
     } while (0)
 
 #define HM_CHECK_WS(name, R)                                                                                           \
@@ -538,7 +509,7 @@ extern "C" int rbvae_hmm_posterior(const double* alpha, const double* beta, cons
     HM_CHECK_SHAPE("hmm_posterior", 1);
     RBVAE_CHECK_ARG(alpha && beta && e && A && gamma && xi && A_new && pi_new && status, "hmm_posterior: null pointer");
     HM_CHECK_WS("hmm_posterior", N);
-    const int blocks = hx_blocks(N), rows = hx_rows(N);
+    const int blocks = row_blocks(N), rows = row_block_rows(N);
     double* Z = (double*)ws;
     double* part = Z + N;
     hipStream_t st = (hipStream_t)stream;

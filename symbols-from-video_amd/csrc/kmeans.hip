@@ -5,7 +5,7 @@
 //                       centres pass through LDS as f64 in chunks of KM_CHUNK values and every lane reads them at the same
 //                       address (broadcast); the lane keeps the smallest (d2, k).  With `own` it keeps d2 to the row's own
 //                       centre instead.  The rows whose label moved are counted with one integer atomic per workgroup.
-//   kmeans_partial_k    stage one of the update: a workgroup owns a block of rows (at most KU_BLOCKS blocks) and a chunk of
+//   kmeans_partial_k    stage one of the update: a workgroup owns a block of rows (diag_gauss.h's row_blocks) and a chunk of
 //                       clusters; thread c owns column c of an LDS slab [clusters][L + 3] (the L coordinates, d2, sqrt(d2)
 //                       and a count of ones) and walks the block's rows in ascending order, so no two threads touch one
 //                       cell and every cell has one order
@@ -17,6 +17,7 @@
 // host may enqueue iterations ahead of the decision.  No floating-point atomics; two runs agree bit for bit.  Contraction
 // is off.
 #include "common.h"
+#include "diag_gauss.h"
 #include "pairdist.h"
 
 #include <math.h>
@@ -29,7 +30,6 @@ constexpr int KM_THREADS = 256;
 constexpr int KM_MAX_L = 128, KM_MAX_K = 256, KM_MAX_N = 1 << 20, KM_MAX_T = 8;
 constexpr int KM_CHUNK = 4096;          // f64 values of centres per LDS chunk (32 KB): KM_CHUNK / round_up(L, 8) centres
 constexpr int KU_SLAB = 8192;           // f64 values of the update's LDS slab (64 KB): KU_SLAB / (L + 3) clusters
-constexpr int KU_BLOCKS = 256;          // row blocks of the update at most
 constexpr int KU_THREADS = 192;         // >= KM_MAX_L + 3 columns
 constexpr int ST_DONE = 0, ST_ITER = 1, ST_WHY = 2, ST_CHANGED = 3;
 
@@ -178,19 +178,6 @@ __global__ void kmeans_decide_k(const double* __restrict__ shift2, int K, double
     }
 }
 
-// a fixed halving tree over the workgroup's 256 values; every thread must call it
-__device__ __forceinline__ double tree_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = KM_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // out f64 [T][N], part f64 [T][gridDim.x]
 __global__ __launch_bounds__(KM_THREADS) void kmeans_pp_k(const float* __restrict__ X, int N, int L,
                                                           const int* __restrict__ cand, int T,
@@ -227,7 +214,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_pp_k(const float* __restric
         }
         const double m = (okc[t] && d < cl) ? d : cl;       // a candidate that is no row changes nothing
         if (live) out[(long)t * N + i] = m;
-        const double s = tree_sum(live ? m : 0.0, red);
+        const double s = block_tree_sum<KM_THREADS>(live ? m : 0.0, red);
         if (tid == 0) part[(long)t * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -238,15 +225,13 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_pp_pot_k(const double* __re
     const int t = blockIdx.x;
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += KM_THREADS) s += part[(long)t * blocks + b];
-    s = tree_sum(s, red);
+    s = block_tree_sum<KM_THREADS>(s, red);
     if (threadIdx.x == 0) pot[t] = s;
 }
 
 static bool km_ok(int N, int L, int K) {
     return L >= 1 && L <= KM_MAX_L && K >= 1 && K <= KM_MAX_K && N >= K && N <= KM_MAX_N;
 }
-static int ku_blocks(int N) { const int b = cdiv(N, KM_THREADS); return b < KU_BLOCKS ? b : KU_BLOCKS; }
-static int ku_rows(int N) { return cdiv(N, ku_blocks(N)); }
 
 }  // namespace rbvae
 
@@ -265,7 +250,7 @@ extern "C" int rbvae_kmeans_chunk_centres(int L) { return L >= 1 && L <= KM_MAX_
 
 extern "C" size_t rbvae_kmeans_ws_bytes(int N, int L, int K) {
     if (!km_ok(N, L, K)) return 0;
-    const size_t upd = (size_t)ku_blocks(N) * K * (L + 3), pp = (size_t)KM_MAX_T * cdiv(N, KM_THREADS);
+    const size_t upd = (size_t)row_blocks(N) * K * (L + 3), pp = (size_t)KM_MAX_T * cdiv(N, KM_THREADS);
     return sizeof(double) * (upd > pp ? upd : pp);
 }
 
@@ -284,9 +269,9 @@ extern "C" int rbvae_kmeans_update(const float* X, int N, int L, const int* labe
                                    void* stream) {
     KM_CHECK_SHAPE("kmeans_update");
     RBVAE_CHECK_ARG(X && label && centres && count && shift2 && within && spread && ws, "kmeans_update: null pointer");
-    const int blocks = ku_blocks(N), chunks = cdiv(K, KU_SLAB / (L + 3));
+    const int blocks = row_blocks(N), chunks = cdiv(K, KU_SLAB / (L + 3));
     hipLaunchKernelGGL(kmeans_partial_k, dim3(blocks, chunks), dim3(KU_THREADS), 0, (hipStream_t)stream, X, N, L, label, d2, K,
-                       ku_rows(N), ws, state);
+                       row_block_rows(N), ws, state);
     RBVAE_CHECK_LAUNCH("kmeans_update (partials)");
     hipLaunchKernelGGL(kmeans_finish_k, dim3(K), dim3(KU_THREADS), 0, (hipStream_t)stream, ws, blocks, L, K, centres, count,
                        shift2, within, spread, state);

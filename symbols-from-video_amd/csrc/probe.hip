@@ -236,18 +236,6 @@ __global__ __launch_bounds__(PB_THREADS) void probe_residual_k(const T* __restri
     }
 }
 
-// the block's 256 values summed by a fixed halving tree; thread 0 returns the total
-__device__ __forceinline__ double block_tree_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = PB_THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // r2_score / explained_variance_score per target (sklearn.metrics._regression, force_finite=True: a zero denominator
 // scores 1 with a zero numerator and 0 otherwise) and the block's partial sums part[block][5] = (r2, evs, sum e^2,
 // sum |e|, constant targets).
@@ -270,7 +258,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_scores_k(const double* __res
     }
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-        const double s = block_tree_sum(v[j], red);
+        const double s = block_tree_sum<PB_THREADS>(v[j], red);
         if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + j] = s;
     }
 }
@@ -285,7 +273,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_means_k(const double* __rest
     for (int j = 0; j < 5; ++j) {
         double s = 0.0;
         for (int b = threadIdx.x; b < nparts; b += PB_THREADS) s += part[(long)b * 5 + j];
-        tot[j] = block_tree_sum(s, red);
+        tot[j] = block_tree_sum<PB_THREADS>(s, red);
     }
     if (threadIdx.x == 0) {
         metrics[0] = tot[0] / (double)P;

@@ -88,12 +88,6 @@ __global__ __launch_bounds__(PJ_THREADS) void knn_k(const float* __restrict__ X,
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {      // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // _binary_search_perplexity on one row per wave: lane l holds neighbours l and l + 64.
 __global__ __launch_bounds__(PJ_THREADS) void tsne_perp_k(const double* __restrict__ d2, int N, int k, double want_entropy,
                                                           double* __restrict__ P, double* __restrict__ beta_out,
@@ -180,19 +174,6 @@ __global__ __launch_bounds__(PJ_THREADS) void tsne_repulse_k(const float* __rest
     }
 }
 
-// the block's THREADS values summed by a fixed halving tree; every thread returns the total
-template <int THREADS = PJ_THREADS>
-__device__ __forceinline__ double pj_tree_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // One workgroup of 1024 threads over the n = splits x N partial sums in memory order: thread t adds the elements t,
 // t + 1024, ... in ascending order (eight loads in flight), then the tree.
 constexpr int ZS_THREADS = 1024, ZS_UNROLL = 8;
@@ -209,14 +190,8 @@ __global__ __launch_bounds__(ZS_THREADS) void tsne_zsum_k(const float* __restric
 #pragma unroll
         for (int u = 0; u < ZS_UNROLL; ++u) acc += (double)v[u];
     }
-    const double tot = pj_tree_sum<ZS_THREADS>(acc, red);
+    const double tot = block_tree_sum<ZS_THREADS>(acc, red);
     if (threadIdx.x == 0) Z[0] = tot;
-}
-
-__device__ __forceinline__ float wave_sum_all(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // sched = (exaggeration, momentum, learning rate) on the device.  Y is read, Y_out written: a neighbour's row may belong
@@ -247,8 +222,8 @@ __global__ __launch_bounds__(PJ_THREADS) void tsne_step_k(const float* __restric
             ay = fmaf(w, dy, ay);
             kl += (double)pe * log(fmax((double)pe, (double)FLT_MIN) / fmax((double)q / Z, (double)FLT_MIN));
         }
-        ax = wave_sum_all(ax);
-        ay = wave_sum_all(ay);
+        ax = wave_sum(ax);
+        ay = wave_sum(ay);
         kl = wave_sum_f64(kl);
         if (lane < 2) {                                     // lane c owns coordinate c
             float r = 0.f;
@@ -284,7 +259,7 @@ __global__ __launch_bounds__(PJ_THREADS) void pca_mean_k(const float* __restrict
     const int l = blockIdx.x;
     double s = 0.0;
     for (int r = threadIdx.x; r < N; r += PJ_THREADS) s += (double)X[(long)r * L + l];
-    const double tot = pj_tree_sum(s, red);
+    const double tot = block_tree_sum<PJ_THREADS>(s, red);
     if (threadIdx.x == 0) mean[l] = tot / (double)N;
 }
 
@@ -300,7 +275,7 @@ __global__ __launch_bounds__(PJ_THREADS) void pca_cov_k(const float* __restrict_
         const double ca = (double)X[(long)r * L + a] - ma, cb = (double)X[(long)r * L + b] - mb;
         s += ca * cb;
     }
-    const double tot = pj_tree_sum(s, red);
+    const double tot = block_tree_sum<PJ_THREADS>(s, red);
     if (threadIdx.x == 0) {
         const double v = tot / (double)(N - 1);
         cov[(long)a * L + b] = v;

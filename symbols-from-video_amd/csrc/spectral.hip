@@ -31,12 +31,6 @@ constexpr int SP_MAX_N = 1 << 20, SP_MAX_M = 1024, SP_MAX_Q = 8, SP_MAX_COLS = 3
 constexpr int ST_BROKEN = 0, ST_STEPS = 1;
 constexpr double SP_BREAKDOWN = 0x1p-40;
 
-__device__ __forceinline__ double sp_wave_sum(double v) {      // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(SP_THREADS) void sp_degree_k(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                           const float* __restrict__ data, int N, double* __restrict__ deg,
                                                           double* __restrict__ isd) {
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_matvec_k(const int* __restrict_
             const int j = indices[e];
             if ((unsigned)j < (unsigned)N) t = (double)data[e] * (isd[j] * x[j]);
         }
-        acc += sp_wave_sum(t);
+        acc += wave_sum_f64(t);
     }
     if (lane == 0) y[i] = isd[i] * acc;
 }
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_dots_k(const double* __restrict
             const int r = r0 + s * SP_THREADS;
             acc += (r < N ? v[r] : 0.0) * wv[s];
         }
-        acc = sp_wave_sum(acc);
+        acc = wave_sum_f64(acc);
         if (lane == 0) red[kk][wave] = acc;
     }
     __syncthreads();

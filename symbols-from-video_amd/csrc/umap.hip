@@ -21,18 +21,6 @@ constexpr int UM_THREADS = 256;
 constexpr int UM_MAX_K1 = 127, UM_MAX_N = 16384, UM_MAX_SAMPLES = 32, UM_SMOOTH_ITERS = 64;
 constexpr int UM_SUM_THREADS = 1024;
 
-__device__ __forceinline__ double um_wave_sum_f64(double v) {   // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float um_wave_sum_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ double um_dist(double d2) { return (double)(float)sqrt(d2); }
 
 // thread t adds the elements t, t + 1024, ... in ascending order, then a halving tree
@@ -73,7 +61,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_smooth_k(const double* __rest
     for (int it = 0; it < UM_SMOOTH_ITERS; ++it) {
         const double t0 = h0 ? (e0 > 0.0 ? exp(-e0 / mid) : 1.0) : 0.0;
         const double t1 = h1 ? (e1 > 0.0 ? exp(-e1 / mid) : 1.0) : 0.0;
-        const double psum = um_wave_sum_f64(t0 + t1);
+        const double psum = wave_sum_f64(t0 + t1);
         n = it + 1;
         if (fabs(psum - target) < 1e-5) break;
         if (psum > target) {
@@ -85,7 +73,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_smooth_k(const double* __rest
         }
     }
     const double k = (double)(K1 + 1);                      // the self distance 0 is one of the k entries
-    const double row = um_wave_sum_f64(d0 + d1);
+    const double row = wave_sum_f64(d0 + d1);
     const double mean = rho > 0.0 ? row / k : dsum[0] / ((double)N * k);
     const double sigma = fmax(mid, 1e-3 * mean);
     if (h0) w[(long)i * K1 + lane] = (e0 <= 0.0 || sigma == 0.0) ? 1.0f : (float)exp(-e0 / sigma);
@@ -153,8 +141,8 @@ __global__ __launch_bounds__(UM_THREADS) void umap_epoch_k(const float* __restri
                 next_neg[e] = nn + (float)q * negp;
             }
         }
-        tx += um_wave_sum_f32(sx);
-        ty += um_wave_sum_f32(sy);
+        tx += wave_sum(sx);
+        ty += wave_sum(sy);
     }
     if (lane == 0) ((float2*)Y_out)[i] = float2{me.x + alpha * tx, me.y + alpha * ty};
 }

@@ -18,7 +18,6 @@ There is no host path: a matrix on the CPU raises.  The shapes are rbvae_hmm_ok'
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -27,10 +26,10 @@ import torch
 
 from . import _lib as L
 from . import mixture, symbols
-from .projection import _device_matrix
+from ._latents import ENQUEUE  # noqa: F401  (the batch of run_until_done)
+from ._latents import checked_matrix, encode_frames, frame_count, frame_labels, run_until_done
 
 MAX_STATES = 64                                     # rbvae_hmm_ok
-ENQUEUE = mixture.ENQUEUE                           # iterations enqueued between two reads of the state and the status
 NO_ROW = 2 ** 31 - 1                                # status[1] before any normaliser failed
 
 
@@ -52,15 +51,8 @@ class HMMResult:
 
 
 def _checked(X, K, what):
-    X = _device_matrix(X, "X")
-    N, Ld = X.shape
-    K = int(K)
-    if L.query("rbvae_hmm_ok", N, Ld, K) != 1:
-        raise ValueError(f"{what}: (N={N}, L={Ld}, K={K}) outside 1 <= L <= 128, 1 <= K <= {MAX_STATES}, "
-                         f"max(K, 2) <= N <= 1048576, N K <= 67108864")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
-    return X, N, Ld, K
+    return checked_matrix(X, what, "rbvae_hmm_ok", f"1 <= L <= 128, 1 <= K <= {MAX_STATES}, max(K, 2) <= N <= 1048576, "
+                          f"N K <= 67108864", K=K)
 
 
 def _f64(a, name, shape, dev):
@@ -138,46 +130,29 @@ def hmm(X: torch.Tensor, n_states: int, init: Union[str, torch.Tensor, np.ndarra
     come from one more pass with the final parameters."""
     X, N, Ld, K = _checked(X, n_states, "hmm")
     dev = X.device
-    max_iter = int(max_iter)
-    if max_iter < 1 or not tol >= 0 or not reg_covar >= 0:
-        raise ValueError(f"max_iter ({max_iter}) must be at least 1, tol ({tol}) and reg_covar ({reg_covar}) non-negative")
+    max_iter, tol, reg_covar = mixture.fit_arguments(max_iter, tol, reg_covar)
     R = _block_rows(block_rows)
-    if isinstance(init, str):
-        if init != "kmeans":
-            raise ValueError(f"init must be 'kmeans' or a label vector, got {init!r}")
-        lab = symbols.kmeans(X, K, seed=seed).labels.long()
-    else:
-        lab = symbols._device_labels(init, "init", dev)
-        if lab.shape[0] != N or int(lab.min()) < 0 or int(lab.max()) >= K:
-            raise ValueError(f"init must be {N} labels in [0, {K}), got {tuple(lab.shape)}")
+    lab = mixture.start_labels(X, K, init, seed)
     buf = _Buffers(N, K, R, dev)
     buf.gamma.zero_()
     buf.gamma.scatter_(0, lab.view(1, N), 1.0)
-    weights, logc = (torch.empty(K, dtype=torch.float64, device=dev) for _ in range(2))
-    means, covars, prec = (torch.empty((K, Ld), dtype=torch.float64, device=dev) for _ in range(3))
-    mws = torch.empty(L.query("rbvae_gmm_ws_bytes", N, Ld, K) // 8, dtype=torch.float64, device=dev)
+    m = mixture.MStep(X, K, reg_covar)                      # its weights and logc are unused
+    means, covars, prec = m.means, m.covars, m.prec
     state = torch.zeros(4, dtype=torch.int32, device=dev)
     lb = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
     history = torch.zeros(max_iter, dtype=torch.float64, device=dev)
-    reg_covar, tol = float(reg_covar), float(tol)
-    L.call("rbvae_gmm_mstep", X, N, Ld, buf.gamma, K, reg_covar, weights, means, covars, prec, logc, mws, None)
+    m.run(buf.gamma)
     A = _initial_transitions(lab, K)
     pi = torch.full((K,), 1.0 / K, dtype=torch.float64, device=dev)
-    it, degenerate = 0, False
-    while True:
-        for _ in range(min(ENQUEUE, max_iter - it)):
-            L.call("rbvae_hmm_emit", X, N, Ld, means, prec, K, buf.logb, buf.rowmax, buf.e, state)
-            buf.recursions(pi, A, state)
-            buf.posterior(A, A, pi, state)
-            L.call("rbvae_gmm_mstep", X, N, Ld, buf.gamma, K, reg_covar, weights, means, covars, prec, logc, mws, state)
-            L.call("rbvae_gmm_decide", buf.ll, N, tol, max_iter, lb, history, state)
-            it += 1
-        done, n_iter, why, _ = state.cpu().tolist()
-        if int(buf.status[0]) != 0:
-            degenerate = True
-            break
-        if done:
-            break
+
+    def iteration(it):
+        L.call("rbvae_hmm_emit", X, N, Ld, means, prec, K, buf.logb, buf.rowmax, buf.e, state)
+        buf.recursions(pi, A, state)
+        buf.posterior(A, A, pi, state)
+        m.run(buf.gamma, state)
+        L.call("rbvae_gmm_decide", buf.ll, N, tol, max_iter, lb, history, state)
+
+    n_iter, why, degenerate = run_until_done(iteration, state, max_iter, also_stop=lambda: int(buf.status[0]) != 0)
     scratch_A, scratch_pi = torch.empty_like(A), torch.empty_like(pi)
     L.call("rbvae_hmm_emit", X, N, Ld, means, prec, K, buf.logb, buf.rowmax, buf.e, None)
     buf.recursions(pi, A)
@@ -262,8 +237,7 @@ def n_parameters(K: int, Ld: int) -> int:
 
 
 def _criteria(score: float, N: int, K: int, Ld: int):
-    p = n_parameters(K, Ld)
-    return -2.0 * score * N + p * math.log(N), -2.0 * score * N + 2.0 * p
+    return mixture.criteria(score, N, n_parameters(K, Ld))
 
 
 def hmm_bic(fit: HMMResult, X: torch.Tensor) -> float:
@@ -277,22 +251,10 @@ def hmm_aic(fit: HMMResult, X: torch.Tensor) -> float:
 
 
 def hmm_select(X: torch.Tensor, ks: Sequence[int], criterion: str = "bic", seed: int = 42, **fit_kwargs):
-    """One fit per K in ks -> (table: a list of {"K", "n_iter", "converged", "score", "bic", "aic"} in ks' order, the chosen
-    K (mixture.choose: the lowest criterion, a tie to the smaller K), its HMMResult)"""
-    ks = [int(k) for k in ks]
-    if not ks:
-        raise ValueError("ks is empty")
-    if criterion not in ("bic", "aic"):
-        raise ValueError(f"criterion must be 'bic' or 'aic', got {criterion!r}")
-    table, fits = [], []
-    for K in ks:
-        fit = hmm(X, K, seed=seed, **fit_kwargs)
-        score = hmm_score(fit, X)
-        bic, aic = _criteria(score, X.shape[0], K, X.shape[1])
-        table.append({"K": K, "n_iter": fit.n_iter, "converged": fit.converged, "score": score, "bic": bic, "aic": aic})
-        fits.append(fit)
-    j = mixture.choose(table, criterion)
-    return table, ks[j], fits[j]
+    """mixture.select with hmm, hmm_score and n_parameters -> (table: a list of {"K", "n_iter", "converged", "score", "bic",
+    "aic"} in ks' order, the chosen K (mixture.choose: the lowest criterion, a tie to the smaller K), its HMMResult)"""
+    return mixture.select(X, ks, criterion, lambda K: hmm(X, K, seed=seed, **fit_kwargs), lambda fit: hmm_score(fit, X),
+                          n_parameters)
 
 
 def change_points(path) -> list:
@@ -306,36 +268,18 @@ def latent_hmm(model, x: torch.Tensor, frame_indices: Sequence[int], flags: Sequ
                tolerance: int = 2, projections: Optional[dict] = None, temperature: float = 0.2, noise_ratio: float = 0.3,
                u=None, max_iter: int = 100, tol: float = 1e-3, reg_covar: float = 1e-6, seed: int = 42) -> dict:
     """The model of the script's data in one call: x [F, C, H, W] frames (or latents) on the device in time order, encoded
-    exactly as mixture.latent_mixture encodes them (projections["latents"] is used instead when present); the states are
+    by _latents.encode_frames' soft pass (projections["latents"] is used instead when present); the states are
     data.assign_label(frame_indices[f], flags) and n_states defaults to their number, len(flags) + 1.
     -> {"latents", "labels" (the states), "hmm": HMMResult, "agreement": clustering_agreement of the Viterbi path against the
         states, "kmeans_agreement": the same for the k-means start, "change_points", "boundaries": segments.boundary_agreement
         of the change points against the positions where the state changes, at `tolerance`, "dwell": f64 [K] on the host,
         1 / (1 - A_kk), "mean_max_posterior"}"""
-    from .data import assign_label
     from .segments import boundary_agreement
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
-    F = x.shape[0]
-    if len(frame_indices) != F:
-        raise ValueError(f"{len(frame_indices)} frame indices for {F} frames")
-    labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+    labels = frame_labels(frame_indices, flags, frame_count(x))
     S = len(flags) + 1
     K = S if n_states is None else int(n_states)
-    z = projections.get("latents") if projections is not None else None
-    if z is None:
-        if u is None:
-            u = torch.rand((F, model.latent_dim))           # the host draw encode() would make
-        u = u.to(x.device)
-        was_training = model.training
-        model.eval()
-        try:
-            z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio, u=u)[:, 0]
-        finally:
-            model.train(was_training)
-    z = z.float().contiguous()
+    z, _ = encode_frames(model, x, hard=False, latents=projections.get("latents") if projections is not None else None,
+                         temperature=temperature, noise_ratio=noise_ratio, u=u)
     start = symbols.kmeans(z, K, seed=seed).labels
     fit = hmm(z, K, init=start, max_iter=max_iter, tol=tol, reg_covar=reg_covar, seed=seed)
     cps = change_points(fit.path)

@@ -8,6 +8,7 @@ responsibilities are soft symbols; its per-frame log-likelihood drops where a fr
   gmm_bic, gmm_aic      -2 score N + p log N and -2 score N + 2 p with p = 2 K L + K - 1 free parameters
   gmm_select            one fit per K, the K with the lowest criterion (ties to the smaller K)
   latent_mixture        the fit at the number of states for the script's data, scored against the states
+  fit_arguments, start_labels, MStep, criteria, select      what hmm.py's Baum-Welch shares with this fit
 The start is symbols.kmeans' labelling (scikit-learn's own start: KMeans(n_clusters=K, n_init=1) from the same RandomState)
 or any labelling; its one-hot responsibilities go through one M-step (which divides the weights by their sum, where
 scikit-learn's initialisation divides by N: the sums differ by K * 10 * 2^-52).  Full, tied and spherical covariance,
@@ -25,10 +26,10 @@ import torch
 
 from . import _lib as L
 from . import symbols
-from .projection import _device_matrix
+from ._latents import ENQUEUE  # noqa: F401  (the batch of run_until_done)
+from ._latents import checked_matrix, encode_frames, frame_count, frame_labels, run_until_done
 
 MAX_COMPONENTS = 256                                # rbvae_gmm_ok
-ENQUEUE = 8                                         # iterations enqueued between two reads of the state
 
 
 @dataclass
@@ -46,15 +47,8 @@ class GMMResult:
 
 
 def _checked(X, K, what):
-    X = _device_matrix(X, "X")
-    N, Ld = X.shape
-    K = int(K)
-    if L.query("rbvae_gmm_ok", N, Ld, K) != 1:
-        raise ValueError(f"{what}: (N={N}, L={Ld}, K={K}) outside 1 <= L <= 128, 1 <= K <= {MAX_COMPONENTS}, "
-                         f"K <= N <= 1048576, N K <= 67108864")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
-    return X, N, Ld, K
+    return checked_matrix(X, what, "rbvae_gmm_ok", f"1 <= L <= 128, 1 <= K <= {MAX_COMPONENTS}, K <= N <= 1048576, "
+                          f"N K <= 67108864", K=K)
 
 
 def _mean_in_order(v: torch.Tensor) -> float:
@@ -65,6 +59,43 @@ def _mean_in_order(v: torch.Tensor) -> float:
     hist = torch.empty(1, dtype=torch.float64, device=dev)
     L.call("rbvae_gmm_decide", v, v.shape[0], 0.0, 1, lb, hist, state)
     return float(hist[0])
+
+
+def fit_arguments(max_iter, tol, reg_covar):
+    """-> (max_iter, tol, reg_covar) as int, float, float; what gmm and hmm.hmm refuse, they refuse in these words"""
+    max_iter = int(max_iter)
+    if max_iter < 1 or not tol >= 0 or not reg_covar >= 0:
+        raise ValueError(f"max_iter ({max_iter}) must be at least 1, tol ({tol}) and reg_covar ({reg_covar}) non-negative")
+    return max_iter, float(tol), float(reg_covar)
+
+
+def start_labels(X, K, init, seed) -> torch.Tensor:
+    """the labelling a fit starts from -> int64 [N] on X's device: symbols.kmeans' for init "kmeans", else init itself"""
+    N = X.shape[0]
+    if isinstance(init, str):
+        if init != "kmeans":
+            raise ValueError(f"init must be 'kmeans' or a label vector, got {init!r}")
+        return symbols.kmeans(X, K, seed=seed).labels.long()
+    lab = symbols._device_labels(init, "init", X.device)
+    if lab.shape[0] != N or int(lab.min()) < 0 or int(lab.max()) >= K:
+        raise ValueError(f"init must be {N} labels in [0, {K}), got {tuple(lab.shape)}")
+    return lab
+
+
+class MStep:
+    """rbvae_gmm_mstep's outputs and workspace for X [N, L] and K components; run(resp, state) fills them from resp [K, N]"""
+
+    def __init__(self, X, K, reg_covar):
+        N, Ld = X.shape
+        f = lambda *s: torch.empty(s, dtype=torch.float64, device=X.device)     # noqa: E731
+        self.X, self.K, self.reg_covar = X, K, reg_covar
+        self.weights, self.logc, self.means, self.covars, self.prec = f(K), f(K), f(K, Ld), f(K, Ld), f(K, Ld)
+        self.ws = f(L.query("rbvae_gmm_ws_bytes", N, Ld, K) // 8)
+
+    def run(self, resp, state=None):
+        N, Ld = self.X.shape
+        L.call("rbvae_gmm_mstep", self.X, N, Ld, resp, self.K, self.reg_covar, self.weights, self.means, self.covars,
+               self.prec, self.logc, self.ws, state)
 
 
 def gmm(X: torch.Tensor, n_components: int, init: Union[str, torch.Tensor, np.ndarray] = "kmeans", max_iter: int = 100,
@@ -78,42 +109,27 @@ def gmm(X: torch.Tensor, n_components: int, init: Union[str, torch.Tensor, np.nd
     a check after every iteration.  The labels come from one more E-step with the final parameters."""
     X, N, Ld, K = _checked(X, n_components, "gmm")
     dev = X.device
-    max_iter = int(max_iter)
-    if max_iter < 1 or not tol >= 0 or not reg_covar >= 0:
-        raise ValueError(f"max_iter ({max_iter}) must be at least 1, tol ({tol}) and reg_covar ({reg_covar}) non-negative")
-    if isinstance(init, str):
-        if init != "kmeans":
-            raise ValueError(f"init must be 'kmeans' or a label vector, got {init!r}")
-        lab = symbols.kmeans(X, K, seed=seed).labels.long()
-    else:
-        lab = symbols._device_labels(init, "init", dev)
-        if lab.shape[0] != N or int(lab.min()) < 0 or int(lab.max()) >= K:
-            raise ValueError(f"init must be {N} labels in [0, {K}), got {tuple(lab.shape)}")
+    max_iter, tol, reg_covar = fit_arguments(max_iter, tol, reg_covar)
+    lab = start_labels(X, K, init, seed)
     resp = torch.zeros((K, N), dtype=torch.float64, device=dev)
     resp.scatter_(0, lab.view(1, N), 1.0)
-    weights, logc = (torch.empty(K, dtype=torch.float64, device=dev) for _ in range(2))
-    means, covars, prec = (torch.empty((K, Ld), dtype=torch.float64, device=dev) for _ in range(3))
-    ws = torch.empty(L.query("rbvae_gmm_ws_bytes", N, Ld, K) // 8, dtype=torch.float64, device=dev)
+    m = MStep(X, K, reg_covar)
     lognorm = torch.empty(N, dtype=torch.float64, device=dev)
     state = torch.zeros(4, dtype=torch.int32, device=dev)
     lb = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
     history = torch.zeros(max_iter, dtype=torch.float64, device=dev)
-    reg_covar, tol = float(reg_covar), float(tol)
-    L.call("rbvae_gmm_mstep", X, N, Ld, resp, K, reg_covar, weights, means, covars, prec, logc, ws, None)
-    it = 0
-    while True:
-        for _ in range(min(ENQUEUE, max_iter - it)):
-            L.call("rbvae_gmm_estep", X, N, Ld, means, prec, logc, K, resp, lognorm, None, state)
-            L.call("rbvae_gmm_mstep", X, N, Ld, resp, K, reg_covar, weights, means, covars, prec, logc, ws, state)
-            L.call("rbvae_gmm_decide", lognorm, N, tol, max_iter, lb, history, state)
-            it += 1
-        done, n_iter, why, _ = state.cpu().tolist()
-        if done:
-            break
+    m.run(resp)
+
+    def iteration(it):
+        L.call("rbvae_gmm_estep", X, N, Ld, m.means, m.prec, m.logc, K, resp, lognorm, None, state)
+        m.run(resp, state)
+        L.call("rbvae_gmm_decide", lognorm, N, tol, max_iter, lb, history, state)
+
+    n_iter, why, _ = run_until_done(iteration, state, max_iter)
     labels = torch.empty(N, dtype=torch.int32, device=dev)
-    L.call("rbvae_gmm_estep", X, N, Ld, means, prec, logc, K, None, lognorm, labels, None)
+    L.call("rbvae_gmm_estep", X, N, Ld, m.means, m.prec, m.logc, K, None, lognorm, labels, None)
     bounds = history[:n_iter].cpu().numpy()
-    return GMMResult(weights, means, covars, int(n_iter), why == 1, float(bounds[-1]), bounds, labels, prec, logc)
+    return GMMResult(m.weights, m.means, m.covars, int(n_iter), why == 1, float(bounds[-1]), bounds, labels, m.prec, m.logc)
 
 
 def _estep(fit: GMMResult, X, what, want_resp=False, want_label=False):
@@ -154,19 +170,19 @@ def n_parameters(K: int, Ld: int) -> int:
     return 2 * K * Ld + K - 1
 
 
-def _criteria(score: float, N: int, K: int, Ld: int):
-    p = n_parameters(K, Ld)
+def criteria(score: float, N: int, p: int):
+    """(BIC, AIC) = (-2 score N + p log N, -2 score N + 2 p) of a mean log-likelihood over N rows with p free parameters"""
     return -2.0 * score * N + p * math.log(N), -2.0 * score * N + 2.0 * p
 
 
 def gmm_bic(fit: GMMResult, X: torch.Tensor) -> float:
     """bic(X) = -2 score(X) N + p log N"""
-    return _criteria(gmm_score(fit, X), X.shape[0], *fit.means.shape)[0]
+    return criteria(gmm_score(fit, X), X.shape[0], n_parameters(*fit.means.shape))[0]
 
 
 def gmm_aic(fit: GMMResult, X: torch.Tensor) -> float:
     """aic(X) = -2 score(X) N + 2 p"""
-    return _criteria(gmm_score(fit, X), X.shape[0], *fit.means.shape)[1]
+    return criteria(gmm_score(fit, X), X.shape[0], n_parameters(*fit.means.shape))[1]
 
 
 def choose(table, criterion="bic") -> int:
@@ -176,9 +192,10 @@ def choose(table, criterion="bic") -> int:
     return min(range(len(table)), key=lambda j: (table[j][criterion], table[j]["K"]))
 
 
-def gmm_select(X: torch.Tensor, ks: Sequence[int], criterion: str = "bic", seed: int = 42, **fit_kwargs):
-    """One fit per K in ks -> (table: a list of {"K", "n_iter", "converged", "score", "bic", "aic"} in ks' order, the chosen
-    K, its GMMResult).  score is the mean log-likelihood under the final parameters, not lower_bound."""
+def select(X, ks: Sequence[int], criterion: str, fit, score, n_parameters):
+    """One fit(K) per K in ks, scored by score(fit(K)) -> (table: a list of {"K", "n_iter", "converged", "score", "bic",
+    "aic"} in ks' order, the chosen K (choose: the lowest criterion, a tie to the smaller K), its fit).  The criteria are
+    those of X's N rows and n_parameters(K, L) free parameters; fit is what checks X."""
     ks = [int(k) for k in ks]
     if not ks:
         raise ValueError("ks is empty")
@@ -186,13 +203,20 @@ def gmm_select(X: torch.Tensor, ks: Sequence[int], criterion: str = "bic", seed:
         raise ValueError(f"criterion must be 'bic' or 'aic', got {criterion!r}")
     table, fits = [], []
     for K in ks:
-        fit = gmm(X, K, seed=seed, **fit_kwargs)
-        score = gmm_score(fit, X)
-        bic, aic = _criteria(score, X.shape[0], K, X.shape[1])
-        table.append({"K": K, "n_iter": fit.n_iter, "converged": fit.converged, "score": score, "bic": bic, "aic": aic})
-        fits.append(fit)
+        f = fit(K)
+        s = score(f)
+        bic, aic = criteria(s, X.shape[0], n_parameters(K, X.shape[1]))
+        table.append({"K": K, "n_iter": f.n_iter, "converged": f.converged, "score": s, "bic": bic, "aic": aic})
+        fits.append(f)
     j = choose(table, criterion)
     return table, ks[j], fits[j]
+
+
+def gmm_select(X: torch.Tensor, ks: Sequence[int], criterion: str = "bic", seed: int = 42, **fit_kwargs):
+    """One fit per K in ks (select with gmm, gmm_score and n_parameters) -> (table: a list of {"K", "n_iter", "converged",
+    "score", "bic", "aic"} in ks' order, the chosen K, its GMMResult).  score is the mean log-likelihood under the final
+    parameters, not lower_bound."""
+    return select(X, ks, criterion, lambda K: gmm(X, K, seed=seed, **fit_kwargs), lambda fit: gmm_score(fit, X), n_parameters)
 
 
 @torch.no_grad()
@@ -200,37 +224,18 @@ def latent_mixture(model, x: torch.Tensor, frame_indices: Sequence[int], flags: 
                    n_components: Optional[int] = None, ks: Optional[Sequence[int]] = None, criterion: str = "bic",
                    projections: Optional[dict] = None, temperature: float = 0.2, noise_ratio: float = 0.3, u=None,
                    max_iter: int = 100, tol: float = 1e-3, reg_covar: float = 1e-6, seed: int = 42) -> dict:
-    """The mixture of the script's data in one call: x [F, C, H, W] frames (or latents) on the device, encoded exactly as
-    symbols.latent_symbols encodes its soft latents (the uniforms u [F, L]; projections["latents"] is used instead when
-    present); the states are data.assign_label(frame_indices[f], flags) and n_components defaults to their number,
-    len(flags) + 1.
+    """The mixture of the script's data in one call: x [F, C, H, W] frames (or latents) on the device, encoded by
+    _latents.encode_frames' soft pass (the uniforms u [F, L]; projections["latents"] is used instead when present); the
+    states are data.assign_label(frame_indices[f], flags) and n_components defaults to their number, len(flags) + 1.
     -> {"latents", "labels" (the states), "gmm": GMMResult, "agreement": clustering_agreement of the fit's labels against
         the states, "responsibilities" f64 [F, K], "mean_max_responsibility", "log_likelihood" f64 [F] (gmm_score_samples),
         "entropy" f64 [F] (-sum_k r log r in nats, 0 log 0 = 0), and with ks given "selection": gmm_select's
         (table, chosen K, fit)}"""
-    from .data import assign_label
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
-    F = x.shape[0]
-    if len(frame_indices) != F:
-        raise ValueError(f"{len(frame_indices)} frame indices for {F} frames")
-    labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+    labels = frame_labels(frame_indices, flags, frame_count(x))
     S = len(flags) + 1
     K = S if n_components is None else int(n_components)
-    z = projections.get("latents") if projections is not None else None
-    if z is None:
-        if u is None:
-            u = torch.rand((F, model.latent_dim))           # the host draw encode() would make
-        u = u.to(x.device)
-        was_training = model.training
-        model.eval()
-        try:
-            z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio, u=u)[:, 0]
-        finally:
-            model.train(was_training)
-    z = z.float().contiguous()
+    z, _ = encode_frames(model, x, hard=False, latents=projections.get("latents") if projections is not None else None,
+                         temperature=temperature, noise_ratio=noise_ratio, u=u)
     kw = dict(max_iter=max_iter, tol=tol, reg_covar=reg_covar)
     fit = gmm(z, K, seed=seed, **kw)
     resp = gmm_predict_proba(fit, z)

@@ -38,31 +38,19 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._latents import device_matrix as _device_matrix
+from ._latents import encode_frames, finite_device_matrix, frame_count, frame_labels
 
 MAX_COMPONENTS = 8                                  # rbvae_pca_project; rbvae_knn: L <= 128, k <= 128, N <= 16384
 EXPLORATION_ITERS, N_ITER_CHECK = 250, 50           # TSNE._EXPLORATION_MAX_ITER, TSNE._N_ITER_CHECK
 MACHINE_EPSILON = float(np.finfo(np.float64).eps)
 
 
-def _device_matrix(X, name, dtype=torch.float32):
-    if not isinstance(X, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor on the GPU, got {type(X).__name__}")
-    if not X.is_cuda:
-        raise ValueError(f"{name} must be on the GPU (there is no CPU path)")
-    if X.dim() != 2 or X.dtype != dtype:
-        raise ValueError(f"{name} must be a 2-D {dtype} tensor, got {X.dtype} {tuple(X.shape)}")
-    if not X.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return X
-
-
 def knn_graph(X: torch.Tensor, k: int):
     """rbvae_knn: X f32 [N, L] on the device -> (idx int32 [N, k], d2 f64 [N, k]); row i's k nearest other rows by
     squared Euclidean distance in f64, sorted by (d2, index) ascending."""
-    X = _device_matrix(X, "X")
+    X = finite_device_matrix(X)
     N, Ld = X.shape
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
     idx = torch.empty((N, int(k)), dtype=torch.int32, device=X.device)
     d2 = torch.empty((N, int(k)), dtype=torch.float64, device=X.device)
     L.call("rbvae_knn", X, N, Ld, int(k), idx, d2)
@@ -495,30 +483,17 @@ def latent_projections(model, x: torch.Tensor, temperature: float = 0.2, noise_r
                        frame_indices: Optional[Sequence[int]] = None, flags: Optional[Sequence[int]] = None,
                        u=None, umap: Optional[dict] = None, **tsne_kw) -> dict:
     """The script's loop (:209-228) as one batched call: x [F, C, H, W] frames (or latents) on the device, one
-    sequence of length 1 per frame, z = model.encode(x, temperature, hard=False, noise_ratio) (:214, :224), then both
-    projections of the soft latents.  Labels (:228) come from data.assign_label(frame_indices[f], flags) when both are
-    given; u [F, L]: the binarisation uniforms instead of the host draw.  tsne_kw goes to tsne_project.  umap: keyword
+    sequence of length 1 per frame, z = model.encode(x, temperature, hard=False, noise_ratio) (:214, :224) through
+    _latents.encode_frames, then both projections of the soft latents.  Labels (:228) come from
+    data.assign_label(frame_indices[f], flags) when both are given; u [F, L]: the binarisation uniforms instead of the host draw.  tsne_kw goes to tsne_project.  umap: keyword
     arguments of umap_project (the script's: {"n_neighbors": 24, "min_dist": 0.25, "seed": 42}); None leaves UMAP out.
     -> {"latents": f32 [F, L], "pca": PCAResult, "tsne": TSNEResult, "labels": int64 array or None} and, with `umap`,
     "umap": UMAPResult"""
-    from .data import assign_label
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
-    was_training = model.training
-    model.eval()
-    try:
-        z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio,
-                         u=None if u is None else u.to(x.device))[:, 0]
-    finally:
-        model.train(was_training)
-    z = z.float().contiguous()
+    F = frame_count(x)
+    z, _ = encode_frames(model, x, hard=False, temperature=temperature, noise_ratio=noise_ratio, u=u)
     labels = None
     if frame_indices is not None and flags is not None:
-        if len(frame_indices) != x.shape[0]:
-            raise ValueError(f"{len(frame_indices)} frame indices for {x.shape[0]} frames")
-        labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+        labels = frame_labels(frame_indices, flags, F)
     out = {"latents": z, "pca": pca_project(z, 2), "tsne": tsne_project(z, **tsne_kw), "labels": labels}
     if umap is not None:
         out["umap"] = umap_project(z, **umap)

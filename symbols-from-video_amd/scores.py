@@ -22,7 +22,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .projection import _device_matrix, knn_graph
+from ._latents import device_matrix as _device_matrix
+from ._latents import encode_frames, frame_count, frame_labels, require_finite
+from .projection import knn_graph
 
 MAX_STATES = 256                                    # rbvae_label_sums_ok
 
@@ -36,8 +38,7 @@ def neighbour_ranks(X: torch.Tensor, nbr: torch.Tensor):
     N, Ld = X.shape
     if nbr.shape[0] != N:
         raise ValueError(f"nbr has {nbr.shape[0]} rows, X {N}")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
+    require_finite(X)
     k = nbr.shape[1]
     rank = torch.empty((N, k), dtype=torch.int32, device=X.device)
     excess = torch.empty(N, dtype=torch.int32, device=X.device)
@@ -88,8 +89,7 @@ def label_distance_sums(X: torch.Tensor, labels, n_states: Optional[int] = None,
     if metric not in ("euclidean", "hamming"):
         raise ValueError(f"metric must be 'euclidean' or 'hamming', got {metric!r}")
     lab, S = _host_labels(labels, N, n_states)
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
+    require_finite(X)
     order = np.argsort(lab, kind="stable").astype(np.int32)
     seg = np.concatenate([[0], np.cumsum(np.bincount(lab, minlength=S))]).astype(np.int32)
     order_d, seg_d = torch.from_numpy(order).to(X.device), torch.from_numpy(seg).to(X.device)
@@ -156,37 +156,18 @@ def latent_scores(model, x: torch.Tensor, frame_indices: Sequence[int], flags: S
                   projections: Optional[dict] = None, n_neighbors: int = 24, temperature: float = 0.2,
                   noise_ratio: float = 0.3, u=None) -> dict:
     """The scores of the script's data in one call: x [F, C, H, W] frames (or latents) on the device, one sequence of
-    length 1 per frame.  The soft latents are encoded as projection.latent_projections encodes them
+    length 1 per frame.  _latents.encode_frames encodes them: the soft latents
     (model.encode(..., temperature, hard=False, noise_ratio); projections["latents"] is used instead when present), the
-    hard codes from the same uniforms with hard=True (embedding_hamming_distance.py:180), the labels are
+    hard codes from the same uniforms with hard=True (embedding_hamming_distance.py:180); the labels are
     data.assign_label(frame_indices[f], flags).  u [F, L]: the binarisation uniforms instead of the host draw.
     -> {"latents" f32 [F, L], "codes" f32 [F, L], "labels" int64 array, "silhouette" (soft latents, Euclidean),
         "silhouette_hamming" (hard codes), "knn_purity", "knn_accuracy" (soft latents, k = n_neighbors)} and, when
     `projections` (latent_projections' dict) is given, "trustworthiness_pca", "continuity_pca", "trustworthiness_tsne" and
     "continuity_tsne" of its maps at n_neighbors, and "trustworthiness_umap" and "continuity_umap" when it holds "umap"."""
-    from .data import assign_label
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
-    F = x.shape[0]
-    if len(frame_indices) != F:
-        raise ValueError(f"{len(frame_indices)} frame indices for {F} frames")
-    labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+    labels = frame_labels(frame_indices, flags, frame_count(x))
     S = len(flags) + 1
-    if u is None:
-        u = torch.rand((F, model.latent_dim))               # the host draw encode() would make, shared by both encodings
-    u = u.to(x.device)
-    was_training = model.training
-    model.eval()
-    try:
-        z = projections.get("latents") if projections is not None else None
-        if z is None:
-            z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio, u=u)[:, 0]
-        codes = model.encode(x[:, None], temperature=temperature, hard=True, noise_ratio=noise_ratio, u=u)[:, 0]
-    finally:
-        model.train(was_training)
-    z, codes = z.float().contiguous(), codes.float().contiguous()
+    z, codes = encode_frames(model, x, hard=True, latents=projections.get("latents") if projections is not None else None,
+                             temperature=temperature, noise_ratio=noise_ratio, u=u)
     agree = knn_label_agreement(z, labels, n_neighbors, S)
     out = {"latents": z, "codes": codes, "labels": labels,
            "silhouette": silhouette_score(z, labels, S), "silhouette_hamming": silhouette_score(codes, labels, S, "hamming"),

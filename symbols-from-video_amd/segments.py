@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .projection import _device_matrix
+from ._latents import checked_matrix, encode_frames, frame_count, frame_labels
 from .symbols import clustering_agreement
 
 MAX_SEGMENTS = 256                                  # rbvae_segment_ok
@@ -51,15 +51,8 @@ class SegmentResult:
 
 
 def _checked(X, K, min_size, what):
-    X = _device_matrix(X, "X")
-    N, Ld = X.shape
-    K, m = int(K), int(min_size)
-    if L.query("rbvae_segment_ok", N, Ld, K, m) != 1:
-        raise ValueError(f"{what}: (N={N}, L={Ld}, K={K}, min_size={m}) outside 2 <= N <= 65536, 1 <= L <= 128, "
-                         f"1 <= K <= {MAX_SEGMENTS}, min_size >= 1, K min_size <= N")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
-    return X, N, Ld, K, m
+    return checked_matrix(X, what, "rbvae_segment_ok", f"2 <= N <= 65536, 1 <= L <= 128, 1 <= K <= {MAX_SEGMENTS}, "
+                          f"min_size >= 1, K min_size <= N", K=K, min_size=min_size)
 
 
 def _workspace(N, Ld, device):
@@ -204,37 +197,20 @@ def latent_segments(model, x: torch.Tensor, frame_indices: Sequence[int], flags:
                     n_segments: Optional[int] = None, tolerance: int = 2, temperature: float = 0.2, noise_ratio: float = 0.3,
                     u=None, min_size: int = 1) -> dict:
     """The recovered state boundaries of the script's data in one call: x [F, C, H, W] frames (or latents) on the device in
-    frame order, encoded exactly as symbols.latent_symbols encodes them (the same uniforms u [F, L] for the soft and the
-    hard pass); the states are data.assign_label(frame_indices[f], flags) and the true boundaries the positions where the
-    state changes; n_segments defaults to the number of true segments.  The default tolerance of 2 is the reference's
-    grey_out = 1 frame on either side of a flag, plus the flag itself.
+    frame order, encoded by _latents.encode_frames (the same uniforms u [F, L] for the soft and the hard pass); the states
+    are data.assign_label(frame_indices[f], flags) and the true boundaries the positions where the state changes;
+    n_segments defaults to the number of true segments.  The default tolerance of 2 is the reference's grey_out = 1 frame on
+    either side of a flag, plus the flag itself.
     -> {"latents", "codes", "labels" (the states), "true_boundaries", "true_frames", "n_segments", and for each of "soft" and
         "hard" a dict {"segments": SegmentResult, "boundaries" (positions), "frames" (frame_indices[pos]),
         "boundary_agreement" against the true boundaries, "label_agreement": clustering_agreement of the segment labels
         against the states}}"""
-    from .data import assign_label
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
-    F = x.shape[0]
-    frames = np.array([int(f) for f in frame_indices], dtype=np.int64)
-    if len(frames) != F:
-        raise ValueError(f"{len(frames)} frame indices for {F} frames")
-    labels = np.array([assign_label(int(f), flags) for f in frames], dtype=np.int64)
+    F = frame_count(x)
+    frames = np.array([int(f) for f in frame_indices], dtype=np.int64)      # indexed by boundary positions below
+    labels = frame_labels(frames, flags, F)
     true = np.nonzero(labels[1:] != labels[:-1])[0].astype(np.int64) + 1
     K = len(true) + 1 if n_segments is None else int(n_segments)
-    if u is None:
-        u = torch.rand((F, model.latent_dim))               # the host draw encode() would make, shared by both encodings
-    u = u.to(x.device)
-    was_training = model.training
-    model.eval()
-    try:
-        z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio, u=u)[:, 0]
-        codes = model.encode(x[:, None], temperature=temperature, hard=True, noise_ratio=noise_ratio, u=u)[:, 0]
-    finally:
-        model.train(was_training)
-    z, codes = z.float().contiguous(), codes.float().contiguous()
+    z, codes = encode_frames(model, x, hard=True, temperature=temperature, noise_ratio=noise_ratio, u=u)
     out = {"latents": z, "codes": codes, "labels": labels, "true_boundaries": true, "true_frames": frames[true], "n_segments": K}
     S = len(flags) + 1
     for name, rows in (("soft", z), ("hard", codes)):

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._latents import encode_frames, frame_count, frame_labels
 
 MAX_STEPS, MAX_LOCKED, MAX_COLS = 1024, 8, 32       # rbvae_spectral_ok, rbvae_spectral_ritz
 ENQUEUE = 8                                         # steps enqueued between two reads of (alpha, beta, state)
@@ -257,36 +258,23 @@ def latent_spectral(model, x: torch.Tensor, frame_indices: Optional[Sequence[int
                     n_components: int = 2, temperature: float = 0.2, noise_ratio: float = 0.3, u=None, seed: int = 0,
                     **solver_kw) -> dict:
     """The script's data in one call, in the mould of symbols.latent_symbols: x [F, C, H, W] frames (or latents) on the
-    device are encoded as projection.latent_projections encodes them, then knn_graph(z, n_neighbors - 1), fuzzy_graph,
+    device are encoded by _latents.encode_frames (the soft pass), then knn_graph(z, n_neighbors - 1), fuzzy_graph,
     spectral_embedding(n_components) and spectral_clustering(n_clusters; default the number of states, len(flags) + 1).
     -> {"latents", "graph": NormalizedGraph, "embedding", "clustering": KMeansResult, "cluster_embedding", "labels" and
         "agreement": clustering_agreement against the states (None without frame_indices and flags)}"""
-    from .data import assign_label
     from .projection import fuzzy_graph, knn_graph
     from .symbols import clustering_agreement
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
+    F = frame_count(x)
     if n_clusters is None and flags is None:
         raise ValueError("n_clusters or flags must be given")
     K = len(flags) + 1 if n_clusters is None else int(n_clusters)
-    was_training = model.training
-    model.eval()
-    try:
-        z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio,
-                         u=None if u is None else u.to(x.device))[:, 0]
-    finally:
-        model.train(was_training)
-    z = z.float().contiguous()
+    z, _ = encode_frames(model, x, hard=False, temperature=temperature, noise_ratio=noise_ratio, u=u)
     k = int(n_neighbors)
     g = normalized_graph(fuzzy_graph(*knn_graph(z, k - 1), k))
     km, cemb = spectral_clustering(g, K, seed=seed, **solver_kw)
     labels = agreement = None
     if frame_indices is not None and flags is not None:
-        if len(frame_indices) != x.shape[0]:
-            raise ValueError(f"{len(frame_indices)} frame indices for {x.shape[0]} frames")
-        labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+        labels = frame_labels(frame_indices, flags, F)
         agreement = clustering_agreement(labels, km.labels, len(flags) + 1, K)
     return {"latents": z, "graph": g, "embedding": spectral_embedding(g, int(n_components), **solver_kw), "clustering": km,
             "cluster_embedding": cemb, "labels": labels, "agreement": agreement}

@@ -27,10 +27,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .projection import _device_matrix
+from ._latents import ENQUEUE  # noqa: F401  (the batch of run_until_done)
+from ._latents import checked_matrix, encode_frames, frame_count, frame_labels, run_until_done
+from ._latents import device_matrix as _device_matrix
 
 MAX_CLUSTERS = 256                                  # rbvae_kmeans_ok
-ENQUEUE = 8                                         # iterations enqueued between two reads of the state
 WHY = {1: "strict", 2: "tol", 3: "max_iter"}
 
 
@@ -46,14 +47,7 @@ class KMeansResult:
 
 
 def _checked(X, K, what):
-    X = _device_matrix(X, "X")
-    N, Ld = X.shape
-    K = int(K)
-    if L.query("rbvae_kmeans_ok", N, Ld, K) != 1:
-        raise ValueError(f"{what}: (N={N}, L={Ld}, K={K}) outside 1 <= L <= 128, 1 <= K <= {MAX_CLUSTERS}, K <= N <= 1048576")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("X holds NaN or infinite values")
-    return X, N, Ld, K
+    return checked_matrix(X, what, "rbvae_kmeans_ok", f"1 <= L <= 128, 1 <= K <= {MAX_CLUSTERS}, K <= N <= 1048576", K=K)
 
 
 def _workspace(N, Ld, K, device):
@@ -127,16 +121,13 @@ def kmeans(X: torch.Tensor, n_clusters: int, init: Union[str, torch.Tensor, np.n
     count = torch.empty(K, dtype=torch.int32, device=dev)
     shift2, within, spread = (torch.empty(K, dtype=torch.float64, device=dev) for _ in range(3))
     ws = _workspace(N, Ld, K, dev)
-    it = 0
-    while True:
-        for _ in range(min(ENQUEUE, max_iter - it)):
-            L.call("rbvae_kmeans_assign", X, N, Ld, C, K, lab[(it + 1) & 1], None, lab[it & 1], d2, state)
-            L.call("rbvae_kmeans_update", X, N, Ld, lab[it & 1], d2, K, C, count, shift2, within, spread, ws, state)
-            L.call("rbvae_kmeans_decide", shift2, K, tol_abs, max_iter, state)
-            it += 1
-        done, n_iter, why, _ = state.cpu().tolist()
-        if done:
-            break
+
+    def iteration(it):
+        L.call("rbvae_kmeans_assign", X, N, Ld, C, K, lab[(it + 1) & 1], None, lab[it & 1], d2, state)
+        L.call("rbvae_kmeans_update", X, N, Ld, lab[it & 1], d2, K, C, count, shift2, within, spread, ws, state)
+        L.call("rbvae_kmeans_decide", shift2, K, tol_abs, max_iter, state)
+
+    n_iter, why, _ = run_until_done(iteration, state, max_iter)
     # scikit-learn's trailing E-step; after a strict stop the centres did not move and it repeats the last assignment
     labels = torch.empty(N, dtype=torch.int32, device=dev)
     L.call("rbvae_kmeans_assign", X, N, Ld, C, K, None, None, labels, d2, None)
@@ -307,37 +298,18 @@ def latent_symbols(model, x: torch.Tensor, frame_indices: Sequence[int], flags: 
                    n_clusters: Optional[int] = None, projections: Optional[dict] = None, temperature: float = 0.2,
                    noise_ratio: float = 0.3, u=None, max_iter: int = 300, tol: float = 1e-4, seed: int = 42) -> dict:
     """The unsupervised symbols of the script's data in one call: x [F, C, H, W] frames (or latents) on the device, encoded
-    exactly as scores.latent_scores encodes them (the same uniforms u [F, L] for the soft and the hard pass;
-    projections["latents"] is used instead when present); the states are data.assign_label(frame_indices[f], flags) and
+    by _latents.encode_frames (the same uniforms u [F, L] for the soft and the hard pass; projections["latents"] is used
+    instead when present); the states are data.assign_label(frame_indices[f], flags) and
     n_clusters defaults to their number, len(flags) + 1.
     -> {"latents", "codes", "labels" (the states), "kmeans": KMeansResult of the soft latents, "symbols", "codes_unique",
         "symbol_counts": code_symbols of the hard codes, "kmeans_agreement", "symbol_agreement": clustering_agreement of
         either against the states, "davies_bouldin_states", "calinski_harabasz_states", "davies_bouldin_kmeans",
         "calinski_harabasz_kmeans"}"""
-    from .data import assign_label
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be on the GPU (there is no CPU path)")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [F, C, H, W], got {tuple(x.shape)}")
-    F = x.shape[0]
-    if len(frame_indices) != F:
-        raise ValueError(f"{len(frame_indices)} frame indices for {F} frames")
-    labels = np.array([assign_label(int(f), flags) for f in frame_indices], dtype=np.int64)
+    labels = frame_labels(frame_indices, flags, frame_count(x))
     S = len(flags) + 1
     K = S if n_clusters is None else int(n_clusters)
-    if u is None:
-        u = torch.rand((F, model.latent_dim))               # the host draw encode() would make, shared by both encodings
-    u = u.to(x.device)
-    was_training = model.training
-    model.eval()
-    try:
-        z = projections.get("latents") if projections is not None else None
-        if z is None:
-            z = model.encode(x[:, None], temperature=temperature, hard=False, noise_ratio=noise_ratio, u=u)[:, 0]
-        codes = model.encode(x[:, None], temperature=temperature, hard=True, noise_ratio=noise_ratio, u=u)[:, 0]
-    finally:
-        model.train(was_training)
-    z, codes = z.float().contiguous(), codes.float().contiguous()
+    z, codes = encode_frames(model, x, hard=True, latents=projections.get("latents") if projections is not None else None,
+                             temperature=temperature, noise_ratio=noise_ratio, u=u)
     km = kmeans(z, K, max_iter=max_iter, tol=tol, seed=seed)
     symbols, uniq, counts = code_symbols(codes)
     return {"latents": z, "codes": codes, "labels": labels, "kmeans": km, "symbols": symbols, "codes_unique": uniq,
