@@ -116,6 +116,30 @@ class _LDMBlocks(nn.Module):
         if getattr(self, "_seen", None):
             self._seen.clear()
 
+    # ---- trace of the stored activations (the tests' launch-by-launch check) ----------------------------
+    # _trace = None (the default): nothing is kept.  A list: every launch of an eager pass that stores a tensor another
+    # launch reads appends (prefix, op, inputs, output, geometry) -- the tensors themselves (the forward never overwrites
+    # an activation), except the per-image scratch of the unfused attention forms, which is reused and recorded as copies.
+    # A plain attribute: never a buffer, never in state_dict.
+    @property
+    def _trace(self):
+        return self.__dict__.get("_trace_records")
+
+    @_trace.setter
+    def _trace(self, records):
+        if records is not None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the trace records eager launches: it cannot be set while the stream is capturing")
+        self.__dict__["_trace_records"] = records
+
+    def _rec(self, prefix, op, inputs, output, copy=False, **geometry):
+        tr = self._trace
+        if tr is None:
+            return None
+        if copy:
+            output = output.clone()
+        tr.append((prefix, op, inputs, output, geometry))
+        return output
+
     # ---- packed weights ---------------------------------------------------------------------------------
     def _pack_special(self, name, w, pk, pack3, ke):
         """a subclass packs the convolutions whose operands are not plain [co][t][ci] (-> True when it did)"""
@@ -163,6 +187,7 @@ class _LDMBlocks(nn.Module):
         out = torch.empty(N * H * W, cout, dtype=tdt, device=x.device)
         self._gemm(x, pk[f"{name}.weight"], out, self._p(f"{name}.bias"), addend, N, H, W, H, W, 1, H, W, cin, cout,
                    x.shape[1], cout, 9, self._d_conv)
+        self._rec(name, "conv3", (x, addend), out, N=N, H=H, W=W, cin=cin, cout=cout)
         return out
 
     def _conv1(self, name, x, rows, cin, cout, addend=None):
@@ -170,6 +195,7 @@ class _LDMBlocks(nn.Module):
         out = torch.empty(rows, cout, dtype=tdt, device=x.device)
         self._gemm(x, pk[f"{name}.weight"], out, self._p(f"{name}.bias"), addend, rows, 1, 1, 1, 1, 1, 1, 1, cin, cout,
                    x.shape[1], cout, 1, self._d_one)
+        self._rec(name, "conv1", (x, addend), out, rows=rows, cin=cin, cout=cout)
         return out
 
     def _gn(self, name, x, N, HW, C, swish=True):
@@ -179,6 +205,7 @@ class _LDMBlocks(nn.Module):
         ws = torch.empty(nws, dtype=torch.float32, device=x.device)
         L.call("rbvae_groupnorm_swish_ws", dt, x, y, self._p(f"{name}.weight"), self._p(f"{name}.bias"), ws, nws, N, HW, C,
                x.shape[1], y.shape[1], 32, 1e-6, int(swish))
+        self._rec(name, "gn", (x,), y, N=N, HW=HW, C=C, swish=int(swish))
         return y
 
     def _gn_stats(self, x, xst, N, H, W, C):
@@ -204,15 +231,20 @@ class _LDMBlocks(nn.Module):
         fused = cout // 128 <= 2
         sc = sh = None
         st = self._gn_stats(x, xst, N, H, W, cin)
+        if xst is None:
+            self._rec(norm, "gn_stats", (x,), st[1], N=N, HW=H * W, C=cin)
         if fused:
             sc = torch.empty(N, cin, dtype=torch.float32, device=dev)
             sh = torch.empty(N, cin, dtype=torch.float32, device=dev)
             if st[0] == "ms":
                 L.call("rbvae_gn_affine", st[1], st[1][N * 32:], gamma, beta, sc, sh, N, cin, 32)
+                self._rec(norm, "gn_affine", (x, st[1]), (sc, sh), N=N, HW=H * W, C=cin)
             else:
                 L.call("rbvae_gn_finish_tiles", st[1], gamma, beta, sc, sh, None, None, N, H, W, cin, 32, 1e-6, st[2], st[3])
+                self._rec(norm, "gn_finish", (x, st[1]), (sc, sh), N=N, H=H, W=W, C=cin, th=st[2], tw=st[3])
         else:
             if st[0] == "ms":
+                ms = st[1]
                 mean, rstd = st[1], st[1][N * 32:]
             else:
                 ms = torch.empty(2 * N * 32, dtype=torch.float32, device=dev)
@@ -220,13 +252,17 @@ class _LDMBlocks(nn.Module):
                 mean, rstd = ms, ms[N * 32:]
                 L.call("rbvae_gn_finish_tiles", st[1], gamma, beta, sc0[0], sc0[1], mean, rstd, N, H, W, cin, 32, 1e-6, st[2],
                        st[3])
+                self._rec(norm, "gn_finish_ms", (x, st[1]), ms, N=N, H=H, W=W, C=cin, th=st[2], tw=st[3])
             y = torch.empty_like(x)
             L.call("rbvae_groupnorm_apply", dt, x, y, mean, rstd, gamma, beta, N, H * W, cin, x.shape[1], y.shape[1], 32, 1)
+            self._rec(norm, "gn_apply", (x, ms), y, N=N, HW=H * W, C=cin)
             x = y
         out = torch.empty(N * H * W, cout, dtype=tdt, device=dev)
         ost = torch.empty(L.query("rbvae_conv3x3_halo_stats_floats", N, H, W, cout, cout // 32), dtype=torch.float32, device=dev)
         L.call("rbvae_conv3x3_halo", dt, x, pk[f"{conv}.weight"], out, self._p(f"{conv}.bias"), addend, self._zero, sc, sh, 1,
                ost, cout // 32, N, H, W, H, W, 1, 1, cin, cout, x.shape[1], cout)
+        self._rec(conv, "conv3_halo", (x, sc, sh, addend), (out, ost), N=N, H=H, W=W, cin=cin, cout=cout, fused=int(fused),
+                  norm=norm)
         return out, ("tiles", ost, 16, 16)
 
     def _halo_ok(self, N, H, W, cin, cout):
@@ -264,9 +300,11 @@ class _LDMBlocks(nn.Module):
             qkv = torch.empty(N * hw, 3 * C, dtype=tdt, device=x.device)
             self._gemm(h, pk[f"{prefix}.qkv.weight"], qkv, pk[f"{prefix}.qkv.bias"], None, N * hw, 1, 1, 1, 1, 1, 1, 1, C,
                        3 * C, h.shape[1], 3 * C, 1, self._d_one)
+            self._rec(f"{prefix}.qkv", "conv1", (h, None), qkv, rows=N * hw, cin=C, cout=3 * C)
             o = torch.empty(N * hw, C, dtype=tdt, device=x.device)
             L.call("rbvae_attention", dt, qkv, qkv[:, C:], qkv[:, 2 * C:], o, N, hw, C, 3 * C, 3 * C, 3 * C, C,
                    float(int(C) ** (-0.5)))
+            self._rec(prefix, "attention", (qkv,), o, N=N, hw=hw, C=C)
             return self._conv1(f"{prefix}.proj_out", o, N * hw, C, C, addend=x)
         q = self._conv1(f"{prefix}.q", h, N * hw, C, C)
         k = self._conv1(f"{prefix}.k", h, N * hw, C, C)
@@ -278,9 +316,13 @@ class _LDMBlocks(nn.Module):
             qn, kn, vn = q[n * hw:(n + 1) * hw], k[n * hw:(n + 1) * hw], v[n * hw:(n + 1) * hw]
             self._gemm(qn, kn, s, None, None, hw, 1, 1, 1, 1, 1, 1, 1, C, hw, C, hw, 1, self._d_one,
                        scale=float(int(C) ** (-0.5)))
+            s0 = self._rec(prefix, "scores", (q, k), s, copy=True, n=n, hw=hw, C=C, ld=hw)
             L.call("rbvae_softmax_rows", dt, s, s, hw, hw, hw)
+            p0 = self._rec(prefix, "softmax", (s0,), s, copy=True, n=n, hw=hw, ld=hw)
             L.call("rbvae_transpose2d", dt, vn, vt, hw, C, C, hw)
+            vt0 = self._rec(prefix, "transpose", (v,), vt, copy=True, n=n, hw=hw, C=C, ld=hw)
             self._gemm(s, vt, o[n * hw:(n + 1) * hw], None, None, hw, 1, 1, 1, 1, 1, 1, 1, hw, C, hw, C, 1, self._d_one)
+            self._rec(prefix, "pv", (p0, vt0), o[n * hw:(n + 1) * hw], n=n, hw=hw, C=C, ld=hw)
         return self._conv1(f"{prefix}.proj_out", o, N * hw, C, C, addend=x)
 
     def _weights_version(self) -> int:
@@ -370,7 +412,8 @@ class LDMEncoder(_LDMBlocks):
         the current stream before the next call of the same shape."""
         self._check_weights()
         if (not self.use_graph or not x.is_cuda or x.dim() != 4 or x.shape[1] != self.cfg["in_channels"]
-                or x.shape[2] % 8 or x.shape[3] % 8 or torch.cuda.is_current_stream_capturing()):
+                or x.shape[2] % 8 or x.shape[3] % 8 or torch.cuda.is_current_stream_capturing()
+                or self._trace is not None):          # the trace records eager launches
             return self._moments_eager(x)
         key = (tuple(x.shape), x.device)
         g = self._graphs.get(key)
@@ -413,15 +456,18 @@ class LDMEncoder(_LDMBlocks):
                 ost = torch.empty(L.query("rbvae_conv_in_stats_floats", N, H, W, cout, cout // 32), dtype=torch.float32, device=dev)
                 L.call("rbvae_conv_in", dt, x, pk[f"{prefix}.weight"], self._p(f"{prefix}.bias"), self._zero, h, ost, cout // 32,
                        N, C, H, W, cout, cout)
+                self._rec(prefix, "conv_in", (x,), (h, ost), N=N, C=C, H=H, W=W, cout=cout)
                 hst = ("tiles", ost, 8, 16)
                 continue
             if kind == "conv_in":
                 K = pk[f"{prefix}.weight"].shape[1]
                 col = torch.empty(N * H * W, K, dtype=tdt, device=dev)
                 L.call("rbvae_im2col", dt, x, C * H * W, H * W, W, 1, N, C, H, W, H, W, 3, 3, 1, 1, K, col)
+                self._rec(prefix, "im2col", (x,), col, N=N, C=C, H=H, W=W, K=K)
                 h = torch.empty(N * H * W, cout, dtype=tdt, device=dev)
                 self._gemm(col, pk[f"{prefix}.weight"], h, self._p(f"{prefix}.bias"), None, N * H * W, 1, 1, 1, 1, 1,
                            1, 1, K, cout, K, cout, 1, self._d_one)
+                self._rec(prefix, "conv_in_gemm", (col,), h, N=N, C=C, H=H, W=W, K=K, cout=cout)
                 hst = None
             elif kind == "res":
                 h, hst = self._res(prefix, h, hst, N, H, W, cin, cout)
@@ -430,6 +476,7 @@ class LDMEncoder(_LDMBlocks):
                 out = torch.empty(N * (H // 2) * (W // 2), cout, dtype=tdt, device=dev)
                 self._gemm(h, pk[f"{prefix}.weight"], out, self._p(f"{prefix}.bias"), None, N, H, W, H // 2, W // 2, 2,
                            H // 2, W // 2, cin, cout, cin, cout, 9, self._d_down)
+                self._rec(prefix, "down", (h,), out, N=N, H=H, W=W, cin=cin, cout=cout)
                 h, H, W = out, H // 2, W // 2
             elif kind == "attn":
                 h = self._attn(prefix, h, N, H, W, cin)
@@ -440,12 +487,14 @@ class LDMEncoder(_LDMBlocks):
                 out = torch.zeros(N * H * W, K, dtype=tdt, device=dev)     # padded to one K slice for quant_conv
                 self._gemm(h, pk[f"{prefix}.weight"], out, self._p(f"{prefix}.bias"), None, N, H, W, H, W, 1, H, W, cin,
                            cout, cin, K, 9, self._d_conv)
+                self._rec(prefix, "conv3", (h, None), out, N=N, H=H, W=W, cin=cin, cout=cout)
                 h = out
             elif kind == "quant":
                 K = pk["quant_conv.weight"].shape[1]
                 out = torch.empty(N * H * W, cout, dtype=tdt, device=dev)
                 self._gemm(h, pk[f"{prefix}.weight"], out, self._p(f"{prefix}.bias"), None, N * H * W, 1, 1, 1, 1, 1, 1,
                            1, K, cout, K, cout, 1, self._d_one)
+                self._rec(prefix, "conv1", (h, None), out, rows=N * H * W, cin=cin, cout=cout)
                 h = out
             hst = None                # every kind but "res" leaves its statistics to the GroupNorm kernels
         return h
@@ -649,9 +698,13 @@ class LDMDecoder(_LDMBlocks):
             qn, kn, vn = q[n * hw:(n + 1) * hw], k[n * hw:(n + 1) * hw], v[n * hw:(n + 1) * hw]
             self._gemm(qn, kn, s, None, None, hw, 1, 1, 1, 1, 1, 1, 1, C, hw, C, hwp, 1, self._d_one,
                        scale=float(int(C) ** (-0.5)))
+            s0 = self._rec(prefix, "scores", (q, k), s, copy=True, n=n, hw=hw, C=C, ld=hwp)
             L.call("rbvae_softmax_rows", dt, s, s, hw, hw, hwp)
+            p0 = self._rec(prefix, "softmax", (s0,), s, copy=True, n=n, hw=hw, ld=hwp)
             L.call("rbvae_transpose2d", dt, vn, vt, hw, C, C, hwp)
+            vt0 = self._rec(prefix, "transpose", (v,), vt, copy=True, n=n, hw=hw, C=C, ld=hwp)
             self._gemm(s, vt, o[n * hw:(n + 1) * hw], None, None, hw, 1, 1, 1, 1, 1, 1, 1, hwp, C, hwp, C, 1, self._d_one)
+            self._rec(prefix, "pv", (p0, vt0), o[n * hw:(n + 1) * hw], n=n, hw=hw, C=C, ld=hwp)
         return self._conv1(f"{prefix}.proj_out", o, N * hw, C, C, addend=x)
 
     # Which folded form an Upsample takes under upsample_impl="halo": upconv_halo_k only for shapes where it measured faster
@@ -680,20 +733,24 @@ class LDMDecoder(_LDMBlocks):
         if self.upsample_impl == "unfolded":
             up = torch.empty(N * 4 * H * W, C, dtype=tdt, device=dev)
             L.call("rbvae_nearest2x_rows", dt, x, up, N, H, W, C, x.shape[1], C)
+            self._rec(prefix, "nearest2x", (x,), up, N=N, H=H, W=W, C=C)
             wu = pk[f"{prefix}.weight.unfolded"]
             if L.query("rbvae_conv3x3_halo_ok", dt, 2 * H, 2 * W, 2 * H, 2 * W, C, C):
                 L.call("rbvae_conv3x3_halo", dt, up, wu, out, bias, None, self._zero, None, None, 0, None, 0, N, 2 * H, 2 * W,
                        2 * H, 2 * W, 1, 1, C, C, C, C)
             else:
                 self._gemm(up, wu, out, bias, None, N, 2 * H, 2 * W, 2 * H, 2 * W, 1, 2 * H, 2 * W, C, C, C, C, 9, self._d_conv)
+            self._rec(prefix, "up_unfolded", (up,), out, N=N, H=2 * H, W=2 * W, C=C)
             self.upsample_dispatch.append(("unfolded", H, W))
         elif self._upconv_halo_ok(N, H, W, C):
             L.call("rbvae_upconv3x3_halo", dt, x, pk[f"{prefix}.weight"], out, bias, None, self._zero, N, H, W, C, C,
                    x.shape[1], C)
+            self._rec(prefix, "up_halo", (x,), out, N=N, H=H, W=W, C=C)
             self.upsample_dispatch.append(("halo", H, W))
         else:
             L.call("rbvae_gather_gemm", dt, x, pk[f"{prefix}.weight"], out, bias, None, None, None, self._zero, N, H, W, H, W,
                    1, 2 * H, 2 * W, 2, C, C, x.shape[1], C, 16, 4, ctypes.addressof(self._d_up), 0, 0, 0.0, 1.0, 0, None, None)
+            self._rec(prefix, "up_gather", (x,), out, N=N, H=H, W=W, C=C)
             self.upsample_dispatch.append(("gather", H, W))
         return out
 
@@ -703,6 +760,7 @@ class LDMDecoder(_LDMBlocks):
         N, Z, H, W = z.shape
         h = torch.empty(N * H * W, ke, dtype=tdt, device=dev)
         L.call("rbvae_latent_rows", dt, z, h, N, Z, H * W, ke, SCALE_FACTOR)
+        self._rec("latent", "latent_rows", (z,), h, N=N, Z=Z, HW=H * W)
         hst = None
         self.upsample_dispatch = []
         for prefix, kind, cin, cout in self.plan:
@@ -710,11 +768,13 @@ class LDMDecoder(_LDMBlocks):
                 out = torch.zeros(N * H * W, ke, dtype=tdt, device=dev)      # one padded K slice for conv_in
                 self._gemm(h, pk[f"{prefix}.weight"], out, pk[f"{prefix}.bias"], None, N * H * W, 1, 1, 1, 1, 1, 1, 1, ke,
                            pk[f"{prefix}.weight"].shape[0], ke, ke, 1, self._d_one)
+                self._rec(prefix, "conv1", (h, None), out, rows=N * H * W, cin=cin, cout=cout)
                 h = out
             elif kind == "conv_in":
                 out = torch.empty(N * H * W, cout, dtype=tdt, device=dev)
                 self._gemm(h, pk[f"{prefix}.weight"], out, self._p(f"{prefix}.bias"), None, N, H, W, H, W, 1, H, W, ke, cout,
                            ke, cout, 9, self._d_conv)
+                self._rec(prefix, "conv3", (h, None), out, N=N, H=H, W=W, cin=cin, cout=cout)
                 h = out
             elif kind == "res":
                 h, hst = self._res(prefix, h, hst, N, H, W, cin, cout)
@@ -731,6 +791,7 @@ class LDMDecoder(_LDMBlocks):
                 out = torch.empty(N * H * W, co8, dtype=tdt, device=dev)
                 self._gemm(h, pk[f"{prefix}.weight"], out, pk[f"{prefix}.bias"], None, N, H, W, H, W, 1, H, W, cin, co8, cin,
                            co8, 9, self._d_conv)
+                self._rec(prefix, "conv3", (h, None), out, N=N, H=H, W=W, cin=cin, cout=cout)
                 h = out
             hst = None
         return h

@@ -175,10 +175,16 @@ def gn_finish_ref(stored, tile, c, cg, eps):
     mean_out / rstd_out (csrc/conv_halo.hip gn_finish_tiles_k): count-weighted tile means summed over a block of 256
     threads (per-thread strided sums, wave_sum, four wave partials), the tile bounds carried through, rsqrtf 1 ulp."""
     N, (OH, OW, tr, tc, mtiles) = c["N"], ch_geometry(c)[:5]
-    v = stored.double().reshape(N, OH * OW, -1)
+    return gn_finish_bounds(stored, tile, N, OH * OW, tr * tc, cg, eps)
+
+
+def gn_finish_bounds(stored, tile, N, HW, nb, cg, eps):
+    """gn_finish_ref for any tiling: HW pixels per image in nb tiles each (tile: the statistics tile of every stored row)."""
+    mtiles = N * nb
+    v = stored.double().reshape(N, HW, -1)
     Nout = v.shape[-1]
-    G, nb, total = Nout // cg, tr * tc, OH * OW * cg
-    grp = v.reshape(N, OH * OW, G, cg).permute(0, 2, 1, 3).reshape(N, G, -1)
+    G, total = Nout // cg, HW * cg
+    grp = v.reshape(N, HW, G, cg).permute(0, 2, 1, 3).reshape(N, G, -1)
     mean = grp.mean(-1)
     var = ((grp - mean[..., None]) ** 2).sum(-1) / total
     amax = grp.abs().amax(-1)

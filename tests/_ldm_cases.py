@@ -187,10 +187,15 @@ def at_c_pv(hw):
 
 def at_reference(c, d):
     """float64 (ref, bound) [N * hw][C] of the case."""
-    N, hw, C, scale = c["N"], c["hw"], c["C"], d["scale"]
+    return at_bounds(d["q"], d["k"], d["v"], d["scale"])
+
+
+def at_bounds(Q, K, V, scale):
+    """float64 (ref, bound) [N * hw][C] of bf16 operands q, k, v [N][hw][C]."""
+    N, hw, C = Q.shape
     refs, bnds = [], []
     for n in range(N):
-        q, k, v = d["q"][n].double(), d["k"][n].double(), d["v"][n].double()
+        q, k, v = Q[n].double(), K[n].double(), V[n].double()
         s = q @ k.t() * scale
         w = torch.softmax(s, dim=1)
         o = w @ v
@@ -328,12 +333,16 @@ def gn_route(c):
 
 
 def gn_height(c):
-    stats = gn_route(c)[0]
-    cg, n = c["C"] // c["groups"], c["HW"] * (c["C"] // c["groups"])
-    if stats == "gn_stats_k":
+    return gn_height_of(c["dtype"], c["HW"], c["C"], c["groups"], gn_route(c)[0] != "gn_stats_k")
+
+
+def gn_height_of(dtype, HW, C, groups, tiled):
+    """summation height of the statistics kernels of a shape: gn_partial_k + gn_finish_k (tiled) or gn_stats_k"""
+    cg, n = C // groups, HW * (C // groups)
+    if not tiled:
         return cdiv(n, 256) + 12
-    rl_n = 256 // (c["C"] // GN_V[c["dtype"]])
-    return GN_PASSES + rl_n + cg + cdiv(cdiv(c["HW"], gn_rows_per_block(c["dtype"], c["C"])), 64) + 9
+    rl_n = 256 // (C // GN_V[dtype])
+    return GN_PASSES + rl_n + cg + cdiv(cdiv(HW, gn_rows_per_block(dtype, C)), 64) + 9
 
 
 def _gn(id, dtype, C, groups, N, HW, kind, swish=1, padx=0, pady=0, entry="swish_ws", ws="full", misalign=None):
@@ -429,12 +438,23 @@ def gn_data(c):
 
 def gn_reference(c, d):
     """float64 references and bounds: dict(mean, rstd [N * G], y [N * HW][C]) -> (ref, bound) each (what the entry leaves)."""
-    N, HW, C, G, dt = c["N"], c["HW"], c["C"], c["groups"], TDT[c["dtype"]]
+    given = (d["mean"], d["rstd"]) if c["entry"] == "apply" else None
+    out = gn_bounds(d["x"], d["gamma"], d["beta"], c["groups"], TDT[c["dtype"]], c["swish"],
+                    h=None if given else gn_height(c), given=given)
+    if c["entry"] == "stats":
+        out.pop("y")
+    return out
+
+
+def gn_bounds(x, gamma, beta, G, out_dtype, swish, h=None, given=None):
+    """gn_reference for any operands: x [N][HW][C] as stored, the statistics kernels' summation height h, or
+    given = (mean, rstd) [N * G] f32 for the apply pass from given statistics."""
+    N, HW, C = x.shape
     cg, n = C // G, HW * (C // G)
-    xg = d["x"].double().reshape(N, HW, G, cg)
+    xg = x.double().reshape(N, HW, G, cg)
     out = {}
-    if c["entry"] == "apply":
-        mean, rstd = d["mean"].double().reshape(N, G), d["rstd"].double().reshape(N, G)
+    if given is not None:
+        mean, rstd = given[0].double().reshape(N, G), given[1].double().reshape(N, G)
         b_mean = b_rstd = torch.zeros(N, G, dtype=F64)
     else:
         mean = xg.mean((1, 3))
@@ -442,24 +462,22 @@ def gn_reference(c, d):
         var = M2 / n
         v = var + GN_EPS
         rstd = v.rsqrt()
-        b_mean, b_M2, _ = B.tile_stats_bounds(n, cg, xg.abs().sum((1, 3)), xg.abs().amax((1, 3)), M2, h=gn_height(c))
+        b_mean, b_M2, _ = B.tile_stats_bounds(n, cg, xg.abs().sum((1, 3)), xg.abs().amax((1, 3)), M2, h=h)
         b_var = b_M2 / n + U32 * var
         lo = v - b_var
         b_rstd = torch.where(lo > 0, lo.clamp_min(1e-300).rsqrt() - rstd, torch.full_like(v, float("inf"))) + 4 * U32 * rstd
         out["mean"] = (mean.reshape(-1), b_mean.reshape(-1))
         out["rstd"] = (rstd.reshape(-1), b_rstd.reshape(-1))
-    if c["entry"] == "stats":
-        return out
     e = lambda s: s[:, None, :, None]
-    ga, be = d["gamma"].double().reshape(1, 1, G, cg), d["beta"].double().reshape(1, 1, G, cg)
+    ga, be = gamma.double().reshape(1, 1, G, cg), beta.double().reshape(1, 1, G, cg)
     t = (xg - e(mean)) * e(rstd) * ga + be
     b_t = e(rstd) * ga.abs() * e(b_mean) + (xg - e(mean)).abs() * ga.abs() * e(b_rstd) \
         + 4 * U32 * ((xg.abs() + e(mean).abs()) * e(rstd) * ga.abs() + be.abs())
     tmax = float(t.abs().max())
-    c_eval = B.staged_u_in(F32, bool(c["swish"]), tmax)
-    y = t * torch.sigmoid(t) if c["swish"] else t
-    u_out = B.U_OUT[dt]
-    b_y = (1 + u_out) * ((1.1 if c["swish"] else 1.0) * b_t + c_eval * y.abs()) + u_out * y.abs() + TINY
+    c_eval = B.staged_u_in(F32, bool(swish), tmax)
+    y = t * torch.sigmoid(t) if swish else t
+    u_out = B.U_OUT[out_dtype]
+    b_y = (1 + u_out) * ((1.1 if swish else 1.0) * b_t + c_eval * y.abs()) + u_out * y.abs() + TINY
     out["y"] = (y.reshape(N * HW, C), b_y.reshape(N * HW, C))
     return out
 
@@ -591,11 +609,16 @@ def sm_c(n):
 
 
 def sm_reference(c, x):
+    return sm_bounds(x, TDT[c["dtype"]])
+
+
+def sm_bounds(x, out_dtype):
+    """float64 (softmax, bound) of the rows of x [rows][n] as stored"""
     xd = x.double()
     p = torch.softmax(xd, dim=1)
-    u_out = B.U_OUT[TDT[c["dtype"]]]
+    u_out = B.U_OUT[out_dtype]
     dist = (xd - xd.max(1, keepdim=True).values).abs()
-    return p, (1 + u_out) * (sm_c(c["n"]) + dist) * U32 * p + u_out * p + TINY
+    return p, (1 + u_out) * (sm_c(x.shape[1]) + dist) * U32 * p + u_out * p + TINY
 
 
 def sm_forward(c, x, dtype):
