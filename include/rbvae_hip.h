@@ -261,6 +261,9 @@ int rbvae_colsum(int dtype, const void* X, int P, int C, int ld, float* out, flo
  * strides (nslab, slab, accumulate) in type dtype >> 8.  Kind 3 with `inner` set updates the conv weight rows it packs.
  * A table of these jobs is the optimiser step AND the weight repack of a training step in one launch.
  * fast: the logical index consecutive threads walk; inner != 0 (fast == 1, short d2): a thread walks d2 itself.
+ * Kind 3's dtype is exactly RBVAE_F32 or RBVAE_BF16; fields a kind does not name above are not read by it.
+ * The kinds are JOB_PACK .. JOB_ADAM (0 .. 7) in csrc/jobs.hip and symbols-from-video_amd/jobs.py, whose `Col` names the 16
+ * positions in the order above.
  * One launch (grid.y = job) replaces the per-tensor launches of a step. */
 int rbvae_run_jobs(const void* jobs_dev, int njobs, int blocks_per_job, void* stream);
 /* The same table launched with exactly the workgroups its jobs can use (a step's update launch: ~1 400 instead of 49 x 256).

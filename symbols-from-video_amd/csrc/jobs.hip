@@ -1,31 +1,141 @@
 // Batched layout jobs: the dozens of small pack / slab-reduce / row-reduce passes of one
 // training step run as ONE launch each (grid.y = job), driven by a device-resident table.
+// Every branch of run_jobs_k has ONE description of its geometry (what a workgroup index means and how many workgroups
+// the job can use), a __host__ __device__ function below: the branch's loop runs over it, and rbvae_job_block_map sizes
+// the launch from it (a divergence between the two would not give wrong numbers -- every branch is grid-strided -- but
+// silently serialise a job).
 #include "common.h"
+
+#ifndef CPK_CIB
+#define CPK_CIB 64                      // conv_pack_rows: input channels per piece of a wide weight
+#endif
+#ifndef JOBS_TILED_ADAM
+#define JOBS_TILED_ADAM 1               // kind 6: big tensors with permuted copies go through LDS tiles
+#endif
+#define JOBS_HD __host__ __device__ __forceinline__
 
 namespace rbvae {
 
-// 16 x int64 per job
+// the job kinds (what each does: include/rbvae_hip.h, "Batched layout jobs")
+enum JobKind : long { JOB_PACK = 0, JOB_PERMUTE, JOB_ROWS, JOB_CONV_PACK, JOB_CONV_REDUCE, JOB_GATHER, JOB_ADAM_PACK, JOB_ADAM };
+
+// One table row, 16 x int64: the format and the meaning of every field per kind are in include/rbvae_hip.h.  Kind 5 keeps
+// the plan pointer, the counter pointer and the table's rows in s0, s1, s2; kind 6 names its reused fields below.
 struct Job {
-    long type;        // 0 pack3 (f32 -> T, strided scatter), 1 permute_reduce (thread per output), 2 reduce_rows (wave per
-                      // output), 3 conv weight [co][ci][kk] f32 -> both GEMM orders [co][t][ci] (dst) and [ci][t][co] (dst2),
-                      // 4 conv weight-gradient slabs [ks][co][t][ci] -> [co][ci][kk] (d0 = co, d1 = ci, d2 = kk),
-                      // 5 batch gather: dst[r] = src[plan[(*counter % d1) * d0 + r]] (d0 rows of d2 float4; s0 = plan, s1 = counter
-                      //   pointer or 0, s2 = table rows),
-                      // 6 / 7 Adam update of a parameter tensor (+ its packed copies for 6), `inner` = AdamCtx*; kind 3 with
-                      //   `inner` set updates the conv weight rows it packs
+    long type;        // JobKind
     const float* src;
     void* dst;
     long d0, d1, d2;  // logical extents [d0][d1][d2] (the contiguous side is laid out in this order)
     long s0, s1, s2;  // strides on the strided side
-    long nslab, slab; // slabs summed in fixed order (types 1, 2)
-    long dtype;       // destination type of pack3
+    long nslab, slab; // slabs summed in fixed order (kinds 1, 2, 4)
+    long dtype;       // destination type
     long accumulate;
     float scale;
     int fast;         // which logical index consecutive threads walk (the one whose strided-side stride is 1)
-    long inner;       // types 0/1 with fast == 1: a thread walks the whole (short) last index itself
-    void* dst2;       // type 3: the second destination
+    long inner;       // kinds 0/1 with fast == 1: a thread walks the whole (short) last index itself; kinds 3/6/7: AdamCtx*
+    void* dst2;       // kinds 3, 6: the second destination
+    // kind 6: the types of the two copies and the strides of the second one
+    JOBS_HD int type1() const { return (int)(dtype & 255); }
+    JOBS_HD int type2() const { return (int)((dtype >> 8) & 255); }
+    JOBS_HD long c0() const { return nslab; }
+    JOBS_HD long c1() const { return slab; }
+    JOBS_HD long c2() const { return accumulate; }
 };
 static_assert(sizeof(Job) == 16 * 8, "job table stride");
+
+// ---- geometry: one definition per branch, shared by the kernel's loops and the host's block map ---------------------------
+
+// kinds 0, 1, 2 (32-bit indices, as the loops count): a thread per element, or per (i0, i1) row with `inner`; kind 2: four
+// columns (wide rows) or four waves = four outputs per workgroup
+JOBS_HD unsigned job_numel(const Job& j) { return (unsigned)j.d0 * (unsigned)j.d1 * (unsigned)j.d2; }
+JOBS_HD unsigned inner_rows_of(const Job& j) { return (unsigned)j.d0 * (unsigned)j.d1; }
+JOBS_HD unsigned tail_blocks(const Job& j) {             // (n / per + (n % per != 0): no wrap for n close to 2^32)
+    if (j.type == JOB_ROWS) return job_numel(j) / 4 + (job_numel(j) % 4 != 0);
+    const unsigned n = j.inner ? inner_rows_of(j) : job_numel(j);
+    return n / 256 + (n % 256 != 0);
+}
+
+JOBS_HD long gather_rows(const Job& j) { return j.d0; }                 // kind 5: a workgroup per row
+JOBS_HD long adam_numel(const Job& j) { return j.d0 * j.d1 * j.d2; }    // kinds 6 / 7, flat: a thread per master element
+JOBS_HD long adam_flat_blocks(const Job& j) { return (adam_numel(j) + 255) / 256; }
+
+JOBS_HD bool conv_pack_f32(const Job& j) { return j.dtype == RBVAE_F32; }
+
+constexpr int CPK_MAXROW = 2304;                       // 256 ci x 9 taps (or 144 ci x 16 taps)
+constexpr int CPK_LDS_BYTES = 16 * (CPK_MAXROW + 8);  // NCO rows of T, NCO * sizeof(T) = 16; +8 elements of pad per row
+// kind 3: workgroup b owns NCO = 16 / es output channels from co0 and the cn input channels from ci0
+struct ConvPack {
+    unsigned nco, cib, ncb, ngr;
+    bool vec_ok;
+    JOBS_HD unsigned blocks() const { return ngr * ncb; }
+    JOBS_HD unsigned co0(unsigned b) const { return (b / ncb) * nco; }
+    JOBS_HD unsigned ci0(unsigned b) const { return (b % ncb) * cib; }
+};
+JOBS_HD ConvPack conv_pack_geom(const Job& j, unsigned es) {
+    const unsigned NCO = 16 / es, NV = 16 / es;
+    const unsigned Co = (unsigned)j.d0, Ci = (unsigned)j.d1, kk = (unsigned)j.d2;
+    // ci block: a multiple of NV such that cib * kk <= CPK_MAXROW
+    unsigned cib = (CPK_MAXROW / kk) / NV * NV;
+    if (cib > Ci) cib = Ci;
+    // pieces of 64 input channels: 4x the workgroups for a 256-channel weight (128 per weight; with whole rows the
+    // fused optimiser update ran on 32 workgroups per weight and took 35 us longer than the unfused step)
+    if (cib > CPK_CIB && Ci % CPK_CIB == 0) cib = CPK_CIB;
+    const bool vec_ok = (Ci % NV == 0) && (Co % NCO == 0) && ((cib * kk) % 4 == 0) && ((Ci * kk) % 4 == 0);
+    return {NCO, cib, (Ci + cib - 1) / cib, (Co + NCO - 1) / NCO, vec_ok};
+}
+
+constexpr int CRD_CI = 256, CRD_MAXKK = 16, CRD_ACC = CRD_CI * CRD_MAXKK / 4 / 256;      // float4 accumulators per thread
+// kind 4: workgroup b owns output channel co and the block of <= CRD_CI input channels from ci0
+struct ConvReduce {
+    unsigned ncb, nblocks;
+    JOBS_HD unsigned blocks() const { return nblocks; }
+    JOBS_HD unsigned co(unsigned b) const { return b / ncb; }
+    JOBS_HD unsigned ci0(unsigned b) const { return (b % ncb) * CRD_CI; }
+};
+JOBS_HD ConvReduce conv_reduce_geom(const Job& j) {
+    const unsigned ncb = ((unsigned)j.d1 + CRD_CI - 1) / CRD_CI;
+    return {ncb, (unsigned)j.d0 * ncb};
+}
+
+// kind 6, tiled: a big tensor (>= 1 M elements) with a copy whose contiguous index is not i2.  fA / fB = the contiguous
+// index of the first / second copy; tile t is T0 x T1 x T2 elements from (b0, b1, b2).  (A struct of scalars: see the
+// note on indexed local arrays in adam_tiled.)
+struct AdamTiles {
+    bool tiled;
+    int fA, fB;
+    unsigned T0, T1, T2, nt0, nt1, nt2;
+    JOBS_HD unsigned blocks() const { return nt0 * nt1 * nt2; }
+    JOBS_HD unsigned b0(unsigned t) const { return (t / (nt2 * nt1)) * T0; }
+    JOBS_HD unsigned b1(unsigned t) const { return ((t / nt2) % nt1) * T1; }
+    JOBS_HD unsigned b2(unsigned t) const { return (t % nt2) * T2; }
+};
+JOBS_HD AdamTiles adam_tiles(const Job& j) {
+    AdamTiles g = {};
+    if (!(JOBS_TILED_ADAM && j.type == JOB_ADAM_PACK && adam_numel(j) >= (1l << 20))) return g;
+    g.fA = j.s0 == 1 ? 0 : (j.s1 == 1 ? 1 : 2);
+    g.fB = !j.dst2 ? g.fA : (j.c0() == 1 ? 0 : (j.c1() == 1 ? 1 : 2));
+    if (g.fA == 2 && g.fB == 2) return g;
+    g.tiled = true;
+    const unsigned D0 = (unsigned)j.d0, d1 = (unsigned)j.d1, d2 = (unsigned)j.d2;
+    unsigned T0, T1, T2;
+    if (g.fA != 2 && g.fB != 2 && g.fA != g.fB) { T2 = 16; T0 = g.fB == 0 ? 32 : 16; T1 = g.fB == 1 ? 32 : 16; }   // three contiguous indices
+    else { const int f = g.fA != 2 ? g.fA : g.fB; T2 = 32; T0 = f == 0 ? 32 : 8; T1 = f == 1 ? 32 : 8; }
+    g.T0 = T0 < D0 ? T0 : D0; g.T1 = T1 < d1 ? T1 : d1; g.T2 = T2 < d2 ? T2 : d2;
+    g.nt0 = (D0 + g.T0 - 1) / g.T0; g.nt1 = (d1 + g.T1 - 1) / g.T1; g.nt2 = (d2 + g.T2 - 1) / g.T2;
+    return g;
+}
+
+// workgroups a job can use: the loop bound of its branch of run_jobs_k
+JOBS_HD long job_blocks_of(const Job& j) {
+    switch (j.type) {
+    case JOB_CONV_PACK: return conv_pack_geom(j, conv_pack_f32(j) ? 4 : 2).blocks();
+    case JOB_CONV_REDUCE: return conv_reduce_geom(j).blocks();
+    case JOB_GATHER: return gather_rows(j);
+    case JOB_ADAM_PACK:
+    case JOB_ADAM: { const AdamTiles g = adam_tiles(j); return g.tiled ? (long)g.blocks() : adam_flat_blocks(j); }
+    default: return tail_blocks(j);
+    }
+}
 
 // Optimiser context of the fused update jobs (kinds 3 with `inner` set, 6, 7): torch.optim.Adam on the flat buffers, the
 // arithmetic of adam_k (layout.hip) element for element.  w / g / m / v are the BASES of the flat parameter, gradient
@@ -55,35 +165,25 @@ __device__ __forceinline__ float adam_at(const AdamCtx& c, long off, float step_
 // LDS in T, and leave as 16-byte stores on both sides -- [co][t][ci] as whole 16-byte runs of ci, [ci][t][co] as the
 // 16-byte run of the workgroup's NCO channels (the per-element 2-byte stores of the first version moved 30 MB in
 // 15 us).  Weights with more than CPK_MAXROW values per channel take the workgroup's rows in pieces of ci.
-#ifndef CPK_CIB
-#define CPK_CIB 64
-#endif
-constexpr int CPK_MAXROW = 2304;                       // 256 ci x 9 taps (or 144 ci x 16 taps)
-constexpr int CPK_LDS_BYTES = 16 * (CPK_MAXROW + 8);  // NCO rows of T, NCO * sizeof(T) = 16; +8 elements of pad per row
 template <typename T>
 __device__ __forceinline__ void conv_pack_rows(const Job& j, unsigned char* lds_raw, unsigned bidx, unsigned nblk) {
     constexpr unsigned NCO = 16 / sizeof(T), NV = 16 / sizeof(T);
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     T* tile = (T*)lds_raw;
     const unsigned Co = (unsigned)j.d0, Ci = (unsigned)j.d1, kk = (unsigned)j.d2;
-    // ci block: a multiple of NV such that cib * kk <= CPK_MAXROW
-    unsigned cib = (CPK_MAXROW / kk) / NV * NV;
-    if (cib > Ci) cib = Ci;
-    // pieces of 64 input channels: 4x the workgroups for a 256-channel weight (128 per weight; with whole rows the
-    // fused optimiser update ran on 32 workgroups per weight and took 35 us longer than the unfused step)
-    if (cib > CPK_CIB && Ci % CPK_CIB == 0) cib = CPK_CIB;
-    const unsigned ncb = (Ci + cib - 1) / cib, ngr = (Co + NCO - 1) / NCO;
+    const ConvPack g = conv_pack_geom(j, sizeof(T));
+    const unsigned cib = g.cib;
+    const bool vec_ok = g.vec_ok;
     const unsigned pitch = CPK_MAXROW + 8;
     T* wf = (T*)j.dst;
     T* wd = (T*)j.dst2;
-    const bool vec_ok = (Ci % NV == 0) && (Co % NCO == 0) && ((cib * kk) % 4 == 0) && ((Ci * kk) % 4 == 0);
     // fused optimiser update (j.inner = AdamCtx*): the block updates exactly the master rows it packs, so the packed
     // copies are written from the new values without a second pass (and without a launch of their own)
     const AdamCtx* actx = (const AdamCtx*)j.inner;
     float step_size = 0.f, bc2_sqrt = 1.f;
     if (actx) { step_size = actx->hyper[0]; bc2_sqrt = actx->hyper[1]; }
-    for (unsigned b = bidx; b < ngr * ncb; b += nblk) {
-        const unsigned co0 = (b / ncb) * NCO, ci0 = (b % ncb) * cib;
+    for (unsigned b = bidx; b < g.blocks(); b += nblk) {
+        const unsigned co0 = g.co0(b), ci0 = g.ci0(b);
         const unsigned cn = min(cib, Ci - ci0), row = cn * kk;       // this piece: cn input channels
         __syncthreads();
         // ---- in: NCO rows of `row` consecutive floats each
@@ -188,20 +288,19 @@ __device__ __forceinline__ void conv_pack_rows(const Job& j, unsigned char* lds_
 // in slab order into the torch layout [co][ci][t].  A workgroup owns one output channel (and a block of <= CRD_CI input
 // channels): every slab's [t][ci] rows come in by 16-byte loads, all of a thread's loads in flight together, the sums
 // change order through LDS and leave as 16-byte stores of the contiguous [ci][t] row.
-constexpr int CRD_CI = 256, CRD_MAXKK = 16, CRD_ACC = CRD_CI * CRD_MAXKK / 4 / 256;      // float4 accumulators per thread
 __device__ __forceinline__ void conv_reduce_rows(const Job& j, float* tile, unsigned bidx, unsigned nblk) {
 #if defined(JOBS_ABL_ONE_SLAB) && !defined(RBVAE_ABLATION)
 #error "JOBS_ABL_ONE_SLAB gives wrong sums (timing ablation): define RBVAE_ABLATION to confirm"
 #endif
 #ifdef JOBS_ABL_ONE_SLAB
-    const unsigned Co = (unsigned)j.d0, Ci = (unsigned)j.d1, kk = (unsigned)j.d2, ns = 1;      // ablation partner of WG_ABL=5
+    const unsigned Ci = (unsigned)j.d1, kk = (unsigned)j.d2, ns = 1;      // ablation partner of WG_ABL=5
 #else
-    const unsigned Co = (unsigned)j.d0, Ci = (unsigned)j.d1, kk = (unsigned)j.d2, ns = (unsigned)j.nslab;
+    const unsigned Ci = (unsigned)j.d1, kk = (unsigned)j.d2, ns = (unsigned)j.nslab;
 #endif
-    const unsigned ncb = (Ci + CRD_CI - 1) / CRD_CI;
+    const ConvReduce g = conv_reduce_geom(j);
     float* out = (float*)j.dst;
-    for (unsigned b = bidx; b < Co * ncb; b += nblk) {
-        const unsigned co = b / ncb, ci0 = (b % ncb) * CRD_CI;
+    for (unsigned b = bidx; b < g.blocks(); b += nblk) {
+        const unsigned co = g.co(b), ci0 = g.ci0(b);
         const unsigned cn = min((unsigned)CRD_CI, Ci - ci0);       // multiple of 4 (host-checked)
         const unsigned c4 = cn / 4, nch = kk * c4, pitch = cn + 1;
         float4 acc[CRD_ACC];
@@ -283,263 +382,235 @@ __device__ __forceinline__ void conv_reduce_rows(const Job& j, float* tile, unsi
     }
 }
 
-// Launch shapes: grid (blocks per job, jobs) -- every job gets the same number of workgroups, most of which leave at once --
-// or, with a block map (rbvae_run_jobs_sized), a 1-D grid of exactly the workgroups the jobs need: map[b] = (job, index of
-// the workgroup within the job, workgroups of the job).  A step's update launch was 12 544 workgroups of which ~1 400 had work.
-__global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, const int4* __restrict__ map) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[CPK_LDS_BYTES];
-    static_assert(CPK_LDS_BYTES >= (int)sizeof(float) * CRD_MAXKK * (CRD_CI + 1), "the reduce tile fits the pack tile");
-    static_assert(CPK_LDS_BYTES >= 256 * 16, "the wide row reduction's tree fits");
-    unsigned bidx = blockIdx.x, nblk = gridDim.x, jidx = blockIdx.y;
-    if (map) {
-        const int4 m = map[blockIdx.x];
-        jidx = (unsigned)m.x; bidx = (unsigned)m.y; nblk = (unsigned)m.z;
-    }
-    const Job j = jobs[jidx];
-    if (j.type == 3) {
-        if (j.dtype == RBVAE_F32) conv_pack_rows<float>(j, lds_raw, bidx, nblk); else conv_pack_rows<bf16_t>(j, lds_raw, bidx, nblk);
-        return;
-    }
-    if (j.type == 4) {
-        conv_reduce_rows(j, (float*)lds_raw, bidx, nblk);
-        return;
-    }
-    if (j.type == 6 || j.type == 7) {
-        // 6: optimiser update of a parameter tensor [d0][d1][d2] + its packed copies: dst (strides s0, s1, s2, type
-        //    dtype & 255) and optionally dst2 (strides nslab, slab, accumulate; type dtype >> 8); 7: update only.
-        // One thread per master element, consecutive threads on consecutive elements (w, g, m, v move coalesced).
-        const AdamCtx c = *(const AdamCtx*)j.inner;
-        const float step_size = c.hyper[0], bc2_sqrt = c.hyper[1];
-        const unsigned d1 = (unsigned)j.d1, d2 = (unsigned)j.d2;
-        const long n = j.d0 * j.d1 * j.d2, base = j.src - c.w;
-        const int t1 = (int)(j.dtype & 255), t2 = (int)((j.dtype >> 8) & 255);
-#ifndef JOBS_TILED_ADAM
-#define JOBS_TILED_ADAM 1
-#endif
-        if (JOBS_TILED_ADAM && j.type == 6 && n >= (1l << 20)) {
-            // A big tensor (>= 1 M elements = 128 tiles: the 131 072-element fc weight of the bench shape would keep 16 workgroups
-            // busy for 40 us: 0.458 -> 0.49 ms per step) whose packed copies are PERMUTED (the fc weights: 56 320 x 32 in
-            // NHWC-flatten order and transposed): with one thread per master element every 2-byte store of a transposed copy went to its own
-            // 64-byte sector (30-40 us per fc weight).  Tiles of 8192 elements through LDS instead: the master side moves in
-            // runs along i2, each copy in runs along ITS contiguous index; the update arithmetic is adam_at's, element for
-            // element (bit-identical: only the order of the memory operations changes).
-            // (scalars and selects, no indexed local arrays: those are promoted to LDS and cost every job of the launch a
-            // workgroup per CU -- 40 064 instead of 36 992 bytes: +5 us per bench step)
-            const long a0 = j.s0, a1 = j.s1, a2 = j.s2, c0 = j.nslab, c1 = j.slab, c2 = j.accumulate;
-            const int fA = a0 == 1 ? 0 : (a1 == 1 ? 1 : 2);
-            const int fB = !j.dst2 ? fA : (c0 == 1 ? 0 : (c1 == 1 ? 1 : 2));
-            if (fA != 2 || fB != 2) {
-                const unsigned D0 = (unsigned)j.d0;
-                unsigned T0, T1, T2;
-                if (fA != 2 && fB != 2 && fA != fB) { T2 = 16; T0 = fB == 0 ? 32 : 16; T1 = fB == 1 ? 32 : 16; }   // three contiguous indices
-                else { const int f = fA != 2 ? fA : fB; T2 = 32; T0 = f == 0 ? 32 : 8; T1 = f == 1 ? 32 : 8; }
-                T0 = min(T0, D0); T1 = min(T1, d1); T2 = min(T2, d2);
-                const unsigned nt0 = (D0 + T0 - 1) / T0, nt1 = (d1 + T1 - 1) / T1, nt2 = (d2 + T2 - 1) / T2;
-                const unsigned pitch = T2 + 1, tel = T0 * T1 * T2;
-                float* tile = (float*)lds_raw;                                           // [T0 * T1][T2 + 1]
-                for (unsigned t = bidx; t < nt0 * nt1 * nt2; t += nblk) {
-                    const unsigned b2 = (t % nt2) * T2, b1 = ((t / nt2) % nt1) * T1, b0 = (t / (nt2 * nt1)) * T0;
-                    // master order (i2 fastest), four elements per thread and round: their 16 loads are in flight together
-                    // (one element per round was 32 dependent round trips per tile: the stores of one may alias the loads of
-                    // the next as far as the compiler knows)
-                    for (unsigned e0 = threadIdx.x; e0 < tel; e0 += 1024) {
-                        long off[4]; unsigned li[4]; bool ok[4];
-                        float pw[4], pg[4], pm[4], pv[4];
+// Kinds 6 / 7, tiled (adam_tiles): a big tensor (>= 1 M elements = 128 tiles: the 131 072-element fc weight of the bench shape would
+// keep 16 workgroups busy for 40 us: 0.458 -> 0.49 ms per step) whose packed copies are PERMUTED (the fc weights: 56 320 x 32 in
+// NHWC-flatten order and transposed): with one thread per master element every 2-byte store of a transposed copy went to its own
+// 64-byte sector (30-40 us per fc weight).  Tiles of 8192 elements through LDS instead: the master side moves in
+// runs along i2, each copy in runs along ITS contiguous index; the update arithmetic is adam_at's, element for
+// element (bit-identical: only the order of the memory operations changes).
+// (scalars and selects, no indexed local arrays: those are promoted to LDS and cost every job of the launch a
+// workgroup per CU -- 40 064 instead of 36 992 bytes: +5 us per bench step)
+__device__ __forceinline__ void adam_tiled(const Job& j, const AdamCtx& c, const AdamTiles& g, float step_size, float bc2_sqrt,
+                                           float* tile, unsigned bidx, unsigned nblk) {            // tile: [T0 * T1][T2 + 1]
+    const unsigned D0 = (unsigned)j.d0, d1 = (unsigned)j.d1, d2 = (unsigned)j.d2;
+    const unsigned T0 = g.T0, T1 = g.T1, T2 = g.T2;
+    const long base = j.src - c.w;
+    const unsigned pitch = T2 + 1, tel = T0 * T1 * T2;
+    for (unsigned t = bidx; t < g.blocks(); t += nblk) {
+        const unsigned b2 = g.b2(t), b1 = g.b1(t), b0 = g.b0(t);
+        // master order (i2 fastest), four elements per thread and round: their 16 loads are in flight together
+        // (one element per round was 32 dependent round trips per tile: the stores of one may alias the loads of
+        // the next as far as the compiler knows)
+        for (unsigned e0 = threadIdx.x; e0 < tel; e0 += 1024) {
+            long off[4]; unsigned li[4]; bool ok[4];
+            float pw[4], pg[4], pm[4], pv[4];
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const unsigned e = e0 + 256 * u;
-                            const unsigned l2 = e % T2, l1 = (e / T2) % T1, l0 = e / (T2 * T1);
-                            ok[u] = e < tel && b0 + l0 < D0 && b1 + l1 < d1 && b2 + l2 < d2;
-                            off[u] = base + ((long)(b0 + l0) * d1 + (b1 + l1)) * d2 + (b2 + l2);
-                            li[u] = (l0 * T1 + l1) * pitch + l2;
-                            if (ok[u]) { pw[u] = c.w[off[u]]; pg[u] = c.g[off[u]]; pm[u] = c.m[off[u]]; pv[u] = c.v[off[u]]; }
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            if (ok[u]) {
-                                const float w = adam_value(pw[u], pg[u], pm[u], pv[u], c, step_size, bc2_sqrt);
-                                c.m[off[u]] = pm[u]; c.v[off[u]] = pv[u]; c.w[off[u]] = w;
-                                tile[li[u]] = w;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                    for (int copy = 0; copy < (j.dst2 ? 2 : 1); ++copy) {
-                        const int f = copy ? fB : fA;                                    // this copy's contiguous index
-                        const long q0 = copy ? c0 : a0, q1 = copy ? c1 : a1, q2 = copy ? c2 : a2;
-                        void* dst = copy ? j.dst2 : j.dst;
-                        const int ty = copy ? t2 : t1;
-                        // e -> (fastest = index f, then the other two in order)
-                        const unsigned Tf = f == 0 ? T0 : (f == 1 ? T1 : T2);
-                        const unsigned Tm = f == 2 ? T1 : T2;                            // the faster of the other two
-                        for (unsigned e = threadIdx.x; e < tel; e += 256) {
-                            const unsigned lf = e % Tf, lm = (e / Tf) % Tm, ls = e / (Tf * Tm);
-                            const unsigned l0 = f == 0 ? lf : ls, l1 = f == 1 ? lf : (f == 0 ? ls : lm), l2 = f == 2 ? lf : lm;
-                            if (b0 + l0 < D0 && b1 + l1 < d1 && b2 + l2 < d2) {
-                                const float w = tile[(l0 * T1 + l1) * pitch + l2];
-                                const size_t o = (b0 + l0) * (size_t)q0 + (b1 + l1) * (size_t)q1 + (b2 + l2) * (size_t)q2;
-                                if (ty == RBVAE_F32) ((float*)dst)[o] = w; else ((bf16_t*)dst)[o] = f32_to_bf16(w);
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-                return;
+            for (int u = 0; u < 4; ++u) {
+                const unsigned e = e0 + 256 * u;
+                const unsigned l2 = e % T2, l1 = (e / T2) % T1, l0 = e / (T2 * T1);
+                ok[u] = e < tel && b0 + l0 < D0 && b1 + l1 < d1 && b2 + l2 < d2;
+                off[u] = base + ((long)(b0 + l0) * d1 + (b1 + l1)) * d2 + (b2 + l2);
+                li[u] = (l0 * T1 + l1) * pitch + l2;
+                if (ok[u]) { pw[u] = c.w[off[u]]; pg[u] = c.g[off[u]]; pm[u] = c.m[off[u]]; pv[u] = c.v[off[u]]; }
             }
-        }
-        for (long i = (long)bidx * 256 + threadIdx.x; i < n; i += (long)nblk * 256) {
-            const float w = adam_at(c, base + i, step_size, bc2_sqrt);
-            if (j.type == 6) {
-                const unsigned i2 = (unsigned)(i % d2), r = (unsigned)(i / d2), i1 = r % d1, i0 = r / d1;
-                const size_t o1 = i0 * (size_t)j.s0 + i1 * (size_t)j.s1 + i2 * (size_t)j.s2;
-                if (t1 == RBVAE_F32) ((float*)j.dst)[o1] = w; else ((bf16_t*)j.dst)[o1] = f32_to_bf16(w);
-                if (j.dst2) {
-                    const size_t o2 = i0 * (size_t)j.nslab + i1 * (size_t)j.slab + i2 * (size_t)j.accumulate;
-                    if (t2 == RBVAE_F32) ((float*)j.dst2)[o2] = w; else ((bf16_t*)j.dst2)[o2] = f32_to_bf16(w);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (ok[u]) {
+                    const float w = adam_value(pw[u], pg[u], pm[u], pv[u], c, step_size, bc2_sqrt);
+                    c.m[off[u]] = pm[u]; c.v[off[u]] = pv[u]; c.w[off[u]] = w;
+                    tile[li[u]] = w;
                 }
             }
         }
-        return;
-    }
-    if (j.type == 5) {
-        // batch gather from the HBM-resident latent table (rbvae_gather_frames as a job, so that it shares the launch of
-        // the step's weight repack): dst[r] = src[plan[(counter % n_batches) * rows + r]], 16 bytes per lane
-        const long rows = j.d0, nb = j.d1, vec = j.d2, table_rows = j.s2;
-        const long* plan = (const long*)j.s0;
-        const unsigned long long* counter = (const unsigned long long*)j.s1;
-        const long b = counter ? (long)(counter[0] % (unsigned long long)nb) : 0;
-        const float4* table = (const float4*)j.src;
-        float4* out = (float4*)j.dst;
-        for (long r = bidx; r < rows; r += nblk) {
-            long src = plan[b * rows + r];
-            if (src < 0 || src >= table_rows) src = 0;
-            for (long i = threadIdx.x; i < vec; i += 256) out[r * vec + i] = table[src * vec + i];
+        __syncthreads();
+        for (int copy = 0; copy < (j.dst2 ? 2 : 1); ++copy) {
+            const int f = copy ? g.fB : g.fA;                                // this copy's contiguous index
+            const long q0 = copy ? j.c0() : j.s0, q1 = copy ? j.c1() : j.s1, q2 = copy ? j.c2() : j.s2;
+            void* dst = copy ? j.dst2 : j.dst;
+            const int ty = copy ? j.type2() : j.type1();
+            // e -> (fastest = index f, then the other two in order)
+            const unsigned Tf = f == 0 ? T0 : (f == 1 ? T1 : T2);
+            const unsigned Tm = f == 2 ? T1 : T2;                            // the faster of the other two
+            for (unsigned e = threadIdx.x; e < tel; e += 256) {
+                const unsigned lf = e % Tf, lm = (e / Tf) % Tm, ls = e / (Tf * Tm);
+                const unsigned l0 = f == 0 ? lf : ls, l1 = f == 1 ? lf : (f == 0 ? ls : lm), l2 = f == 2 ? lf : lm;
+                if (b0 + l0 < D0 && b1 + l1 < d1 && b2 + l2 < d2) {
+                    const float w = tile[(l0 * T1 + l1) * pitch + l2];
+                    const size_t o = (b0 + l0) * (size_t)q0 + (b1 + l1) * (size_t)q1 + (b2 + l2) * (size_t)q2;
+                    if (ty == RBVAE_F32) ((float*)dst)[o] = w; else ((bf16_t*)dst)[o] = f32_to_bf16(w);
+                }
+            }
         }
+        __syncthreads();
+    }
+}
+
+// Kinds 6 / 7: optimiser update of a parameter tensor [d0][d1][d2] (+ for 6 its one or two packed copies).
+// Flat: one thread per master element, consecutive threads on consecutive elements (w, g, m, v move coalesced).
+__device__ __forceinline__ void adam_rows(const Job& j, unsigned char* lds_raw, unsigned bidx, unsigned nblk) {
+    const AdamCtx c = *(const AdamCtx*)j.inner;
+    const float step_size = c.hyper[0], bc2_sqrt = c.hyper[1];
+    const AdamTiles g = adam_tiles(j);
+    if (g.tiled) {
+        adam_tiled(j, c, g, step_size, bc2_sqrt, (float*)lds_raw, bidx, nblk);
         return;
     }
+    const unsigned d1 = (unsigned)j.d1, d2 = (unsigned)j.d2;
+    const long n = adam_numel(j), base = j.src - c.w;
+    const int t1 = j.type1(), t2 = j.type2();
+    for (long i = (long)bidx * 256 + threadIdx.x; i < n; i += (long)nblk * 256) {
+        const float w = adam_at(c, base + i, step_size, bc2_sqrt);
+        if (j.type == JOB_ADAM_PACK) {
+            const unsigned i2 = (unsigned)(i % d2), r = (unsigned)(i / d2), i1 = r % d1, i0 = r / d1;
+            const size_t o1 = i0 * (size_t)j.s0 + i1 * (size_t)j.s1 + i2 * (size_t)j.s2;
+            if (t1 == RBVAE_F32) ((float*)j.dst)[o1] = w; else ((bf16_t*)j.dst)[o1] = f32_to_bf16(w);
+            if (j.dst2) {
+                const size_t o2 = i0 * (size_t)j.c0() + i1 * (size_t)j.c1() + i2 * (size_t)j.c2();
+                if (t2 == RBVAE_F32) ((float*)j.dst2)[o2] = w; else ((bf16_t*)j.dst2)[o2] = f32_to_bf16(w);
+            }
+        }
+    }
+}
+
+// Kind 5: batch gather from the HBM-resident latent table (rbvae_gather_frames as a job, so that it shares the launch of
+// the step's weight repack): dst[r] = src[plan[(counter % n_batches) * rows + r]], 16 bytes per lane
+__device__ __forceinline__ void gather_rows_job(const Job& j, unsigned bidx, unsigned nblk) {
+    const long rows = gather_rows(j), nb = j.d1, vec = j.d2, table_rows = j.s2;
+    const long* plan = (const long*)j.s0;
+    const unsigned long long* counter = (const unsigned long long*)j.s1;
+    const long b = counter ? (long)(counter[0] % (unsigned long long)nb) : 0;
+    const float4* table = (const float4*)j.src;
+    float4* out = (float4*)j.dst;
+    for (long r = bidx; r < rows; r += nblk) {
+        long src = plan[b * rows + r];
+        if (src < 0 || src >= table_rows) src = 0;
+        for (long i = threadIdx.x; i < vec; i += 256) out[r * vec + i] = table[src * vec + i];
+    }
+}
+
+// Kind 2, thousands of partial rows (the per-tile column sums of a 2 M-pixel layer): a workgroup owns FOUR columns, its
+// 256 threads walk the rows 16 bytes at a time (eight loads in flight each), then a fixed-order tree over the
+// threads -- one wave per column walked 16 384 rows with 64-way uncoalesced dword loads (50 us for 4 MB)
+__device__ __forceinline__ void rows_wide(const Job& j, float4* red, unsigned bidx, unsigned nblk) {
+    const unsigned n = job_numel(j), nsl = (unsigned)j.nslab, slb = (unsigned)j.slab;
+    float* out = (float*)j.dst;
+    for (unsigned cb = bidx; cb < n / 4; cb += nblk) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* col = j.src + 4 * cb;
+        unsigned k = threadIdx.x;
+        for (; k + 7 * 256 < nsl; k += 8 * 256) {
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = *(const float4*)(col + (size_t)(k + u * 256) * slb);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
+        }
+        for (; k < nsl; k += 256) {
+            const float4 v = *(const float4*)(col + (size_t)k * slb);
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+        red[threadIdx.x] = a;
+        __syncthreads();
+        for (unsigned s = 128; s > 0; s >>= 1) {
+            if (threadIdx.x < s) {
+                const float4 o = red[threadIdx.x + s];
+                float4 m = red[threadIdx.x];
+                m.x += o.x; m.y += o.y; m.z += o.z; m.w += o.w;
+                red[threadIdx.x] = m;
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x < 4) {
+            const float* r = (const float*)red;
+            const float t = r[threadIdx.x] * j.scale;
+            out[4 * cb + threadIdx.x] = j.accumulate ? out[4 * cb + threadIdx.x] + t : t;
+        }
+        __syncthreads();
+    }
+}
+
+// Kind 2: out[c] = scale * sum_k src[k*slab + c]; one wave per output, lanes stride the slabs, shuffle-reduce
+__device__ __forceinline__ void rows_wave(const Job& j, unsigned bidx, unsigned nblk) {
+    const unsigned n = job_numel(j);
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = bidx * 4 + (threadIdx.x >> 6), nw = nblk * 4;
+    float* out = (float*)j.dst;
+    const unsigned ns = (unsigned)j.nslab, slab = (unsigned)j.slab;
+    for (unsigned c = wave; c < n; c += nw) {
+        // eight loads in flight per lane (fixed order of additions: reproducible); one per iteration was a
+        // memory round trip each, 64 of them for the 4096 partial rows of a 4-channel bias gradient
+        float a = 0.f;
+        unsigned k = lane;
+        for (; k + 7 * 64 < ns; k += 8 * 64) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = j.src[(size_t)(k + u * 64) * slab + c];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a += v[u];
+        }
+        for (; k < ns; k += 64) a += j.src[(size_t)k * slab + c];
+        a = wave_sum(a) * j.scale;
+        if (lane == 0) out[c] = j.accumulate ? out[c] + a : a;
+    }
+}
+
+// Kinds 0 / 1 with `inner`: fast == 1 with a short last index (conv weights: [co][ci][kk] on the contiguous side, ci-major
+// rows on the strided side): a thread owns (i0, i1) and walks i2 itself, so the strided side is read / written
+// as whole rows of consecutive i1 and the contiguous side as d2-element runs per thread
+__device__ __forceinline__ void inner_rows(const Job& j, unsigned bidx, unsigned nblk) {
+    const unsigned d1 = (unsigned)j.d1, d2 = (unsigned)j.d2;
+    const unsigned ns = (unsigned)j.nslab;
+    for (unsigned i = bidx * 256 + threadIdx.x; i < inner_rows_of(j); i += nblk * 256) {
+        const unsigned i1 = i % d1, i0 = i / d1;
+        const size_t lin0 = (size_t)i * d2;
+        const size_t so0 = i0 * (size_t)j.s0 + i1 * (size_t)j.s1;
+        if (j.type == JOB_PACK) {
+            for (unsigned i2 = 0; i2 < d2; ++i2) {
+                const size_t so = so0 + i2 * (size_t)j.s2;
+                if (j.dtype == RBVAE_F32) ((float*)j.dst)[so] = j.src[lin0 + i2];
+                else ((bf16_t*)j.dst)[so] = f32_to_bf16(j.src[lin0 + i2]);
+            }
+        } else {
+            // slabs in fixed order, four at a time: all 4 * d2 loads of a group are independent and in flight
+            // together (one slab per iteration was a memory round trip per slab: 7 for the 256-channel weights)
+            float a[16];
+#pragma unroll
+            for (int i2 = 0; i2 < 16; ++i2) a[i2] = 0.f;
+            const float* p = j.src + so0;
+            unsigned k = 0;
+            if (d2 <= 9) {
+                for (; k + 4 <= ns; k += 4, p += 4 * j.slab) {
+                    float v[4][9];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int i2 = 0; i2 < 9; ++i2)
+                            v[q][i2] = (unsigned)i2 < d2 ? p[(size_t)q * j.slab + (size_t)i2 * j.s2] : 0.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int i2 = 0; i2 < 9; ++i2) a[i2] += v[q][i2];
+                }
+            }
+            for (; k < ns; ++k, p += j.slab) {
+                float v[16];
+#pragma unroll
+                for (int i2 = 0; i2 < 16; ++i2) v[i2] = (unsigned)i2 < d2 ? p[(size_t)i2 * j.s2] : 0.f;
+#pragma unroll
+                for (int i2 = 0; i2 < 16; ++i2) a[i2] += v[i2];
+            }
+            float* out = (float*)j.dst + lin0;
+#pragma unroll
+            for (int i2 = 0; i2 < 16; ++i2)
+                if ((unsigned)i2 < d2) out[i2] = j.accumulate ? out[i2] + a[i2] * j.scale : a[i2] * j.scale;
+        }
+    }
+}
+
+// Kinds 0 / 1: a thread per element, thread index -> (i0, i1, i2) with index `fast` varying fastest
+__device__ __forceinline__ void elem_rows(const Job& j, unsigned bidx, unsigned nblk) {
     const unsigned d0 = (unsigned)j.d0, d1 = (unsigned)j.d1, d2 = (unsigned)j.d2;
-    const unsigned n = d0 * d1 * d2;
-    // this job may need fewer blocks than the launch provides
-    if (bidx * (j.type == 2 ? 4u : 256u) >= n) return;
-    if (j.type == 2) {
-        const unsigned nsl = (unsigned)j.nslab, slb = (unsigned)j.slab;
-        if (nsl >= 1024 && (n & 3) == 0 && (slb & 3) == 0 && ((size_t)j.src & 15) == 0) {
-            // thousands of partial rows (the per-tile column sums of a 2 M-pixel layer): a workgroup owns FOUR columns, its
-            // 256 threads walk the rows 16 bytes at a time (eight loads in flight each), then a fixed-order tree over the
-            // threads -- one wave per column walked 16 384 rows with 64-way uncoalesced dword loads (50 us for 4 MB)
-            float4* red = (float4*)lds_raw;
-            float* out = (float*)j.dst;
-            for (unsigned cb = bidx; cb < n / 4; cb += nblk) {
-                float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float* col = j.src + 4 * cb;
-                unsigned k = threadIdx.x;
-                for (; k + 7 * 256 < nsl; k += 8 * 256) {
-                    float4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = *(const float4*)(col + (size_t)(k + u * 256) * slb);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
-                }
-                for (; k < nsl; k += 256) {
-                    const float4 v = *(const float4*)(col + (size_t)k * slb);
-                    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-                }
-                red[threadIdx.x] = a;
-                __syncthreads();
-                for (unsigned s = 128; s > 0; s >>= 1) {
-                    if (threadIdx.x < s) {
-                        const float4 o = red[threadIdx.x + s];
-                        float4 m = red[threadIdx.x];
-                        m.x += o.x; m.y += o.y; m.z += o.z; m.w += o.w;
-                        red[threadIdx.x] = m;
-                    }
-                    __syncthreads();
-                }
-                if (threadIdx.x < 4) {
-                    const float* r = (const float*)red;
-                    const float t = r[threadIdx.x] * j.scale;
-                    out[4 * cb + threadIdx.x] = j.accumulate ? out[4 * cb + threadIdx.x] + t : t;
-                }
-                __syncthreads();
-            }
-            return;
-        }
-        // out[c] = scale * sum_k src[k*slab + c]; one wave per output, lanes stride the slabs, shuffle-reduce
-        const int lane = threadIdx.x & 63;
-        const unsigned wave = bidx * 4 + (threadIdx.x >> 6), nw = nblk * 4;
-        float* out = (float*)j.dst;
-        const unsigned ns = (unsigned)j.nslab, slab = (unsigned)j.slab;
-        for (unsigned c = wave; c < n; c += nw) {
-            // eight loads in flight per lane (fixed order of additions: reproducible); one per iteration was a
-            // memory round trip each, 64 of them for the 4096 partial rows of a 4-channel bias gradient
-            float a = 0.f;
-            unsigned k = lane;
-            for (; k + 7 * 64 < ns; k += 8 * 64) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = j.src[(size_t)(k + u * 64) * slab + c];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) a += v[u];
-            }
-            for (; k < ns; k += 64) a += j.src[(size_t)k * slab + c];
-            a = wave_sum(a) * j.scale;
-            if (lane == 0) out[c] = j.accumulate ? out[c] + a : a;
-        }
-        return;
-    }
-    if (j.inner) {
-        // fast == 1 with a short last index (conv weights: [co][ci][kk] on the contiguous side, ci-major rows on
-        // the strided side): a thread owns (i0, i1) and walks i2 itself, so the strided side is read / written
-        // as whole rows of consecutive i1 and the contiguous side as d2-element runs per thread
-        const unsigned ns = (unsigned)j.nslab;
-        for (unsigned i = bidx * 256 + threadIdx.x; i < d0 * d1; i += nblk * 256) {
-            const unsigned i1 = i % d1, i0 = i / d1;
-            const size_t lin0 = (size_t)i * d2;
-            const size_t so0 = i0 * (size_t)j.s0 + i1 * (size_t)j.s1;
-            if (j.type == 0) {
-                for (unsigned i2 = 0; i2 < d2; ++i2) {
-                    const size_t so = so0 + i2 * (size_t)j.s2;
-                    if (j.dtype == RBVAE_F32) ((float*)j.dst)[so] = j.src[lin0 + i2];
-                    else ((bf16_t*)j.dst)[so] = f32_to_bf16(j.src[lin0 + i2]);
-                }
-            } else {
-                // slabs in fixed order, four at a time: all 4 * d2 loads of a group are independent and in flight
-                // together (one slab per iteration was a memory round trip per slab: 7 for the 256-channel weights)
-                float a[16];
-#pragma unroll
-                for (int i2 = 0; i2 < 16; ++i2) a[i2] = 0.f;
-                const float* p = j.src + so0;
-                unsigned k = 0;
-                if (d2 <= 9) {
-                    for (; k + 4 <= ns; k += 4, p += 4 * j.slab) {
-                        float v[4][9];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-#pragma unroll
-                            for (int i2 = 0; i2 < 9; ++i2)
-                                v[q][i2] = (unsigned)i2 < d2 ? p[(size_t)q * j.slab + (size_t)i2 * j.s2] : 0.f;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-#pragma unroll
-                            for (int i2 = 0; i2 < 9; ++i2) a[i2] += v[q][i2];
-                    }
-                }
-                for (; k < ns; ++k, p += j.slab) {
-                    float v[16];
-#pragma unroll
-                    for (int i2 = 0; i2 < 16; ++i2) v[i2] = (unsigned)i2 < d2 ? p[(size_t)i2 * j.s2] : 0.f;
-#pragma unroll
-                    for (int i2 = 0; i2 < 16; ++i2) a[i2] += v[i2];
-                }
-                float* out = (float*)j.dst + lin0;
-#pragma unroll
-                for (int i2 = 0; i2 < 16; ++i2)
-                    if ((unsigned)i2 < d2) out[i2] = j.accumulate ? out[i2] + a[i2] * j.scale : a[i2] * j.scale;
-            }
-        }
-        return;
-    }
-    // thread index -> (i0, i1, i2) with index `fast` varying fastest
+    const unsigned n = job_numel(j);
     const int f = j.fast;
     const unsigned ef = f == 0 ? d0 : (f == 1 ? d1 : d2);       // extent of the fastest index
     const unsigned em = f == 2 ? d1 : d2;                        // extent of the middle one
@@ -551,7 +622,7 @@ __global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, 
         const unsigned i2 = f == 2 ? fv : mid;
         const size_t lin = ((size_t)i0 * d1 + i1) * d2 + i2;
         const size_t so = i0 * (size_t)j.s0 + i1 * (size_t)j.s1 + i2 * (size_t)j.s2;
-        if (j.type == 0) {
+        if (j.type == JOB_PACK) {
             if (j.dtype == RBVAE_F32) ((float*)j.dst)[so] = j.src[lin];
             else ((bf16_t*)j.dst)[so] = f32_to_bf16(j.src[lin]);
         } else {
@@ -579,6 +650,47 @@ __global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, 
     }
 }
 
+// Launch shapes: grid (blocks per job, jobs) -- every job gets the same number of workgroups, most of which leave at once --
+// or, with a block map (rbvae_run_jobs_sized), a 1-D grid of exactly the workgroups the jobs need: map[b] = (job, index of
+// the workgroup within the job, workgroups of the job).  A step's update launch was 12 544 workgroups of which ~1 400 had work.
+__global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, const int4* __restrict__ map) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[CPK_LDS_BYTES];
+    static_assert(CPK_LDS_BYTES >= (int)sizeof(float) * CRD_MAXKK * (CRD_CI + 1), "the reduce tile fits the pack tile");
+    static_assert(CPK_LDS_BYTES >= 256 * 16, "the wide row reduction's tree fits");
+    static_assert(CPK_LDS_BYTES >= (int)sizeof(float) * 32 * 16 * (16 + 1), "the largest Adam tile (adam_tiles) fits");
+    unsigned bidx = blockIdx.x, nblk = gridDim.x, jidx = blockIdx.y;
+    if (map) {
+        const int4 m = map[blockIdx.x];
+        jidx = (unsigned)m.x; bidx = (unsigned)m.y; nblk = (unsigned)m.z;
+    }
+    const Job j = jobs[jidx];
+    if (j.type == JOB_CONV_PACK) {
+        if (conv_pack_f32(j)) conv_pack_rows<float>(j, lds_raw, bidx, nblk); else conv_pack_rows<bf16_t>(j, lds_raw, bidx, nblk);
+        return;
+    }
+    if (j.type == JOB_CONV_REDUCE) {
+        conv_reduce_rows(j, (float*)lds_raw, bidx, nblk);
+        return;
+    }
+    if (j.type == JOB_ADAM_PACK || j.type == JOB_ADAM) {
+        adam_rows(j, lds_raw, bidx, nblk);
+        return;
+    }
+    if (j.type == JOB_GATHER) {
+        gather_rows_job(j, bidx, nblk);
+        return;
+    }
+    if (bidx >= tail_blocks(j)) return;       // this job may need fewer blocks than the launch provides
+    if (j.type == JOB_ROWS) {
+        const bool wide = (unsigned)j.nslab >= 1024 && (job_numel(j) & 3) == 0 && ((unsigned)j.slab & 3) == 0 && ((size_t)j.src & 15) == 0;
+        if (wide) rows_wide(j, (float4*)lds_raw, bidx, nblk); else rows_wave(j, bidx, nblk);
+    } else if (j.inner) {
+        inner_rows(j, bidx, nblk);
+    } else {
+        elem_rows(j, bidx, nblk);
+    }
+}
+
 }  // namespace rbvae
 
 using namespace rbvae;
@@ -592,46 +704,12 @@ extern "C" int rbvae_run_jobs(const void* jobs_dev, int njobs, int blocks_per_jo
     return RBVAE_OK;
 }
 
-// workgroups job `r` (16 x int64, host copy of a table row) can use: the loop bounds of run_jobs_k's branches
-static long job_blocks_of(const long* r) {
-    const long type = r[0], d0 = r[3], d1 = r[4], d2 = r[5], n = d0 * d1 * d2;
-    const long dtype = r[11];
-    if (type == 3) {
-        const long es = (dtype & 255) == RBVAE_F32 ? 4 : 2, nco = 16 / es, nv = 16 / es, kk = d2;
-        long cib = (CPK_MAXROW / kk) / nv * nv;
-        if (cib > d1) cib = d1;
-        if (cib > CPK_CIB && d1 % CPK_CIB == 0) cib = CPK_CIB;
-        return ((d0 + nco - 1) / nco) * ((d1 + cib - 1) / cib);
-    }
-    if (type == 4) return d0 * ((d1 + CRD_CI - 1) / CRD_CI);
-    if (type == 5) return d0;
-    if (type == 6 || type == 7) {
-        if (type == 6 && n >= (1l << 20)) {
-            const long a0 = r[6], a1 = r[7], c0 = r[9], c1 = r[10];
-            const int fA = a0 == 1 ? 0 : (a1 == 1 ? 1 : 2);
-            const int fB = !r[15] ? fA : (c0 == 1 ? 0 : (c1 == 1 ? 1 : 2));
-            if (fA != 2 || fB != 2) {
-                long T0, T1, T2;
-                if (fA != 2 && fB != 2 && fA != fB) { T2 = 16; T0 = fB == 0 ? 32 : 16; T1 = fB == 1 ? 32 : 16; }
-                else { const int f = fA != 2 ? fA : fB; T2 = 32; T0 = f == 0 ? 32 : 8; T1 = f == 1 ? 32 : 8; }
-                if (T0 > d0) T0 = d0;
-                if (T1 > d1) T1 = d1;
-                if (T2 > d2) T2 = d2;
-                return ((d0 + T0 - 1) / T0) * ((d1 + T1 - 1) / T1) * ((d2 + T2 - 1) / T2);
-            }
-        }
-        return (n + 255) / 256;
-    }
-    if (type == 2) return (n + 3) / 4;              // four columns (wide rows) or four waves = four outputs per workgroup
-    if (r[14]) return (d0 * d1 + 255) / 256;        // a thread per (i0, i1) row
-    return (n + 255) / 256;
-}
-
 extern "C" int rbvae_job_block_map(const long* rows_host, int njobs, int max_blocks_per_job, int* map_host, int map_capacity) {
     if (!rows_host || njobs <= 0 || max_blocks_per_job <= 0) return fail(RBVAE_E_INVALID, "job_block_map: bad arguments");
+    const Job* jobs = (const Job*)rows_host;
     long total = 0;
     for (int j = 0; j < njobs; ++j) {
-        long nb = job_blocks_of(rows_host + 16l * j);
+        long nb = job_blocks_of(jobs[j]);
         if (nb < 1) nb = 1;
         if (nb > max_blocks_per_job) nb = max_blocks_per_job;
         if (map_host) {

@@ -19,6 +19,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from .jobs import JOB_CONV_PACK, JOB_PACK, JOB_PERMUTE, JOB_ROWS, Col, JobList, JobTable, adam_context
+from .jobs import job_block_map          # re-exported: tests and tools call engine.job_block_map
 
 F32, BF16 = 0, 1
 
@@ -139,70 +141,6 @@ def dgrad_classes(k: int) -> Tuple[List[int], int]:
 
 ONE_TAP = [1, 0, 0, 0, 0, 0]
 
-JOB_PACK, JOB_PERMUTE, JOB_ROWS, JOB_CONV_PACK, JOB_CONV_REDUCE, JOB_GATHER, JOB_ADAM_PACK, JOB_ADAM = 0, 1, 2, 3, 4, 5, 6, 7
-
-
-class JobList:
-    """Rows of the rbvae_run_jobs table (16 x int64 each), uploaded once and replayed."""
-
-    def __init__(self):
-        self.rows: List[List[int]] = []
-        self.keep = []          # tensors whose addresses the table holds
-
-    def add(self, kind, src, dst, dims, strides, nslab=1, slab=0, dtype=0, accumulate=0, scale=1.0):
-        import struct
-        bits = struct.unpack("<I", struct.pack("<f", float(scale)))[0]
-        # consecutive threads walk the index whose stride on the strided side is 1 (coalesced on that side;
-        # the contiguous side then sees short strides that the caches absorb)
-        fast = 2
-        for ax in (2, 1, 0):
-            if strides[ax] == 1 and dims[ax] > 1:
-                fast = ax
-                break
-        # ... unless that index is the middle one of a long row with a short last index (conv weights): then a
-        # thread walks the last index itself and both sides move in runs
-        inner = int(kind in (JOB_PACK, JOB_PERMUTE) and fast == 1 and dims[2] <= 16 and dims[1] >= 64)
-        self.rows.append([kind, src.data_ptr(), dst.data_ptr(), dims[0], dims[1], dims[2], strides[0], strides[1],
-                          strides[2], nslab, slab, dtype, int(accumulate), bits | (fast << 32), inner, 0])
-        self.keep += [src, dst]
-
-    def add_conv_pack(self, src, wf, wd, co, ci, kk, dtype):
-        """f32 weight [co][ci][kk] -> [co][t][ci] (wf) and [ci][t][co] (wd) in one pass."""
-        if kk > 16:
-            raise ValueError("conv weight pack supports kernels up to 4x4")
-        self.rows.append([JOB_CONV_PACK, src.data_ptr(), wf.data_ptr(), co, ci, kk, 0, 0, 0, 1, 0, dtype, 0, 0, 0,
-                          wd.data_ptr()])
-        self.keep += [src, wf, wd]
-
-    def add_conv_reduce(self, slabs, dst, co, ci, kk, nslab, scale=1.0):
-        """K-slice slabs [nslab][co][kk][ci] of a conv weight gradient -> torch layout [co][ci][kk], coalesced."""
-        import struct
-        bits = struct.unpack("<I", struct.pack("<f", float(scale)))[0]
-        self.rows.append([JOB_CONV_REDUCE, slabs.data_ptr(), dst.data_ptr(), co, ci, kk, 0, 0, 0, nslab, co * kk * ci, 0, 0,
-                          bits, 0, 0])
-        self.keep += [slabs, dst]
-
-    def upload(self, device):
-        return torch.tensor(self.rows, dtype=torch.int64).to(device)
-
-    def signature(self):
-        return tuple(tuple(r) for r in self.rows)
-
-
-def job_block_map(rows, device, cap):
-    """Block map of a job table for rbvae_run_jobs_sized: one workgroup entry (job, index within the job, workgroups of the
-    job) per workgroup the rows can use, at most `cap` per job.  -> (int32 device tensor [n][4], n)."""
-    import numpy as np
-    arr = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(len(rows), 16))
-    total = L.query("rbvae_job_block_map", arr.ctypes.data, len(rows), cap, None, 0)
-    if total <= 0:
-        raise RuntimeError("rbvae_job_block_map: " + L.lib().rbvae_last_error().decode())
-    m = np.empty(4 * total, dtype=np.int32)
-    if L.query("rbvae_job_block_map", arr.ctypes.data, len(rows), cap, m.ctypes.data, total) != total:
-        raise RuntimeError("rbvae_job_block_map: " + L.lib().rbvae_last_error().decode())
-    return torch.from_numpy(m).to(device), total
-
-
 class Saved:
     """Activations one forward call keeps for its backward."""
     __slots__ = ("N", "S", "T", "hw", "train", "tau", "tau_dev", "hard", "col1", "x_in", "fm_in", "a1", "a2", "a3", "e", "hs_enc", "hp_enc",
@@ -248,9 +186,10 @@ class Engine:
         self._desc_cache: Dict[Tuple, object] = {}
         self._idx_cache: Dict[Tuple, torch.Tensor] = {}
         self.seed_dev = None           # optional device step counter (int64 tensor) for graph-replayed steps
-        self._pack_tab: Dict = {}
+        self._pack_tab: Dict = {}      # uploaded JobTables of pack() (keyed by the flat buffer) and update_jobs() (by its arguments)
         self._bufs: Dict = {}          # persistent backward temporaries, keyed by (N, tag)
-        self._bwd_tab: Dict = {}       # uploaded reduce-job tables, keyed by their signature
+        self._bwd_tab: Dict = {}       # uploaded reduce-job JobTables, keyed by their signature
+        self._tables: Dict[int, JobTable] = {}     # every uploaded JobTable by the address of its device rows (which it holds)
         self._jobs: Optional[JobList] = None
         self._wg_cus = 256
         self.last_wgrad_kernel = None  # kernel family the last _wgrad() call launched (bench.py's roofline leg keys its timers by it)
@@ -342,31 +281,32 @@ class Engine:
         self.wT_enc = torch.zeros(nl, 2, Ld, 4 * Ld, dtype=torch.float32, device=self.device)   # [k][gate row]
         self.wT_dec = torch.zeros(nl, 2, Ld, 4 * Ld, dtype=torch.float32, device=self.device)
 
-    def _register_table(self, tab: torch.Tensor, rows):
-        """Remember the block map of an uploaded job table (run_table launches it with exactly the workgroups it can use)."""
-        if not hasattr(self, "_table_maps"):
-            self._table_maps = {}
-        self._table_maps[tab.data_ptr()] = job_block_map(rows, self.device, self._job_blocks) + (tab,)
+    def _upload(self, jl: JobList) -> JobTable:
+        t = JobTable(jl, self.device, self._job_blocks)
+        self._tables[t.rows.data_ptr()] = t
+        return t
+
+    def table_of(self, tab: torch.Tensor) -> Optional[JobTable]:
+        """The uploaded table whose device rows are `tab` (what pack, update_jobs and the backward pass hand out)."""
+        return self._tables.get(tab.data_ptr())
 
     def run_table(self, tab: torch.Tensor, n: int, kind: int = 2):
-        """One batched job launch of an uploaded table: sized (rbvae_run_jobs_sized) when its block map is registered and
-        sized_jobs covers its kind (1 = the optimiser update table, 2 = the pack / reduce tables)."""
-        m = getattr(self, "_table_maps", {}).get(tab.data_ptr())
-        if m is None or self.sized_jobs < kind:
+        """One batched job launch of `tab` (n rows): sized (rbvae_run_jobs_sized, exactly the workgroups it can use) when it
+        is one of the engine's uploaded tables and sized_jobs covers its kind (1 = the optimiser update table, 2 = the
+        pack / reduce tables)."""
+        t = self._tables.get(tab.data_ptr())
+        if t is None or self.sized_jobs < kind:
             L.call("rbvae_run_jobs", tab, n, self._job_blocks)
         else:
-            L.call("rbvae_run_jobs_sized", tab, m[0], m[1])
+            L.call("rbvae_run_jobs_sized", tab, *t.block_map)
 
     def pack(self, flat: torch.Tensor):
         """f32 parameters (reference layouts) -> the packed T copies the GEMMs read (one launch)."""
         key = flat.data_ptr()
-        tab = self._pack_tab.get(key)
-        if tab is None:
-            jl = self._pack_jobs(flat)
-            tab = (jl.upload(self.device), len(jl.rows), jl)
-            self._register_table(tab[0], jl.rows)
-            self._pack_tab[key] = tab
-        self.run_table(tab[0], tab[1])
+        t = self._pack_tab.get(key)
+        if t is None:
+            t = self._pack_tab[key] = self._upload(self._pack_jobs(flat))
+        self.run_table(t.rows, t.n)
 
     def update_jobs(self, flat, gflat, m, v, hyper, betas, eps, gscale, extra_rows=None, part=None):
         """Optimiser step + weight repack of a training step as ONE batched job launch: every parameter tensor is a job
@@ -376,56 +316,42 @@ class Engine:
         part: None = every parameter; "tail" / "head" = the data-parallel trainer's gradient buckets (decoder CNN + both
         LSTM stacks / encoder CNN, cut at decoder_cnn.fc.weight): the tail is updated while the head is still being
         all-reduced.  Returns (device table, n_jobs); cached per buffer set."""
-        import struct
         key = ("update", flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), hyper.data_ptr(), tuple(betas),
                float(eps), float(gscale), tuple(map(tuple, extra_rows)) if extra_rows else None, part)
         tab = self._pack_tab.get(key)
         if tab is not None:
-            return tab[0], tab[1]
+            return tab.rows, tab.n
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("update job table missing during graph capture: run one eager update with the same buffers, "
                                f"hyper-parameters and part ({part!r}) first (FusedTrainer's warm-up steps do)")
-        f2 = lambda a, b: struct.unpack("<q", struct.pack("<ff", float(a), float(b)))[0]
-        b1, b2 = betas
-        ctx = torch.tensor([flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), hyper.data_ptr(),
-                            f2(1.0 - b1, b2), f2(1.0 - b2, eps), f2(gscale, 0.0)], dtype=torch.int64).to(self.device)
-        jl = self._pack_jobs(flat)
+        ctx = adam_context(flat, gflat, m, v, hyper, betas, eps, gscale)
+        packs_jl = self._pack_jobs(flat)
         by_src: Dict[int, List[List[int]]] = {}
-        for row in jl.rows:
-            by_src.setdefault(row[1], []).append(row)
+        for row in packs_jl.rows:
+            by_src.setdefault(row[Col.SRC], []).append(row)
         lay = self.layout
-        rows: List[List[int]] = [list(r) for r in extra_rows] if extra_rows else []
-        cp = ctx.data_ptr()
+        jl = JobList()
+        jl.rows = [list(r) for r in extra_rows] if extra_rows else []
+        jl.keep = [packs_jl.keep]
         o_cut = lay.offsets["decoder_cnn.fc.weight"]
         for name in lay.names:
             src = lay.view(flat, name)
-            n = src.numel()
             packs = by_src.pop(src.data_ptr(), [])
             if part is not None and (lay.offsets[name] >= o_cut) != (part == "tail"):
                 continue
-            if len(packs) == 1 and packs[0][0] == JOB_CONV_PACK:
-                r = list(packs[0])
-                r[14] = cp
-                rows.append(r)
-            elif packs and all(p_[0] == JOB_PACK for p_ in packs) and len(packs) <= 2:
-                a = packs[0]
-                bq = packs[1] if len(packs) == 2 else None
-                if bq is not None and tuple(bq[3:6]) != tuple(a[3:6]):
-                    raise RuntimeError(f"{name}: its two packed copies walk different logical shapes")
-                t2 = bq[11] if bq is not None else 0
-                rows.append([JOB_ADAM_PACK, a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8],
-                             bq[6] if bq is not None else 0, bq[7] if bq is not None else 0, a[11] | (t2 << 8),
-                             bq[8] if bq is not None else 0, 0, cp, bq[2] if bq is not None else 0])
+            kinds = [p_[Col.KIND] for p_ in packs]
+            if kinds == [JOB_CONV_PACK]:
+                jl.add_conv_pack_adam(packs[0], ctx)
+            elif kinds in ([JOB_PACK], [JOB_PACK, JOB_PACK]):
+                jl.add_adam_pack(ctx, *packs, what=name)
             elif not packs:
-                rows.append([JOB_ADAM, src.data_ptr(), 0, n, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, cp, 0])
+                jl.add_adam(src, ctx)
             else:
                 raise RuntimeError(f"{name}: unsupported pack job combination for the fused update")
         if by_src:
             raise RuntimeError("pack jobs whose source is not a parameter tensor")
-        t = torch.tensor(rows, dtype=torch.int64).to(self.device)
-        self._register_table(t, rows)
-        self._pack_tab[key] = (t, len(rows), ctx, jl)
-        return t, len(rows)
+        tab = self._pack_tab[key] = self._upload(jl)
+        return tab.rows, tab.n
 
     def _pack_jobs(self, flat: torch.Tensor) -> JobList:
         lay, dt = self.layout, self.dt
@@ -683,12 +609,10 @@ class Engine:
     def _run_jobs(self):
         jl, self._jobs = self._jobs, None
         sig = jl.signature()
-        tab = self._bwd_tab.get(sig)
-        if tab is None:
-            tab = (jl.upload(self.device), len(jl.rows), jl)
-            self._register_table(tab[0], jl.rows)
-            self._bwd_tab[sig] = tab
-        self.run_table(tab[0], tab[1])
+        t = self._bwd_tab.get(sig)
+        if t is None:
+            t = self._bwd_tab[sig] = self._upload(jl)
+        self.run_table(t.rows, t.n)
 
     def _E(self, *shape, dtype=None):
         return torch.empty(*shape, dtype=dtype or self.tdt, device=self.device)

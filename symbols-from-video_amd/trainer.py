@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from .engine import VARIANTS
+from .jobs import JobList
 
 
 def noise_key(seed: int, rank: int) -> int:
@@ -169,9 +170,7 @@ class FusedTrainer:
 
     def _gather_row(self, x):
         table, plan, _, _ = self._data
-        from .engine import JOB_GATHER
-        return [JOB_GATHER, table.data_ptr(), x.data_ptr(), plan.shape[1], plan.shape[0], table[0].numel() // 4,
-                plan.data_ptr(), self.step_dev.data_ptr(), table.shape[0], 1, 0, 0, 0, 0, 0, 0]
+        return JobList().add_gather(table, x, plan, self.step_dev)
 
     def _update(self, part=None):
         """Adam + weight repack (+ the next batch's gather in set_data mode) as one job launch.

@@ -36,7 +36,7 @@ import torch
 
 import _bounds as B
 from _bounds import TINY, U32
-from _loss_cases import BF16_T, CPK_CIB, CPK_MAXROW, F32_T, TDT, cdiv, conv_pack_path, gen_of, perm_strides, wave_sum32
+from _loss_cases import BF16_T, CPK_CIB, CPK_MAXROW, F32_T, TDT, cdiv, conv_pack_path, gen_of, job_kernel, perm_strides, tile_shape, wave_sum32
 from _lstm_cases import _exact, _worst
 
 U = U32
@@ -180,8 +180,17 @@ def conv_pack_pieces(Co, Ci, kk, dt):
     return vec, cib, cdiv(Ci, cib)
 
 
+def update_job_of(r):
+    """The _loss_cases.job description of a fused-update row (kind 3 with a context, 6, 7), read back from its fields."""
+    kind, dims = r[0], tuple(r[3:6])
+    if kind != 6:
+        return dict(id="row", kind=kind, dims=dims, dtype=r[11], copies=())
+    copies = [(r[11] & 255, tuple(r[6:9]))] + ([((r[11] >> 8) & 255, (r[9], r[10], r[12]))] if r[15] else [])
+    return dict(id="row", kind=6, dims=dims, dtype=0, copies=tuple(copies))
+
+
 def job_blocks_of(r):
-    """Workgroups a row can use: job_blocks_of of csrc/jobs.hip for kinds 0-5 and 7."""
+    """Workgroups a row can use: job_blocks_of of csrc/jobs.hip, every kind (kind 6 from _loss_cases.tile_shape)."""
     kind, d0, d1, d2 = r[0], r[3], r[4], r[5]
     n = d0 * d1 * d2
     if kind == 3:
@@ -191,6 +200,9 @@ def job_blocks_of(r):
         return d0 * cdiv(d1, CRD_CI)
     if kind == 5:
         return d0
+    if kind == 6:
+        ts = tile_shape(update_job_of(r))
+        return cdiv(n, 256) if ts is None else cdiv(d0, ts[0]) * cdiv(d1, ts[1]) * cdiv(d2, ts[2])
     if kind == 7:
         return cdiv(n, 256)
     if kind == 2:
@@ -213,6 +225,8 @@ def job_branch(r):
     """The branch of run_jobs_k a row takes, in the kernel's order of tests."""
     kind, d0, d1, d2 = r[0], r[3], r[4], r[5]
     n = d0 * d1 * d2
+    if kind in (6, 7) or (kind == 3 and r[14]):
+        return job_kernel(update_job_of(r))                 # the fused-update branches, named as in _loss_cases.JOB_BRANCHES
     if kind == 3:
         vec, _, pieces = conv_pack_pieces(d0, d1, d2, r[11])
         return f"run_jobs_k[3,{'vec' if vec else 'elem'},{DTN[r[11]]}{',split' if pieces > 1 else ''}]"

@@ -979,7 +979,7 @@ def test_fused_update_jobs_equal_adam_plus_pack(sfv, variant, in_ch, dtype, Ld, 
                       0.9, 0.999, hyper)
         if fused == "sized":      # the same table launched with exactly the workgroups its jobs can use (rbvae_run_jobs_sized)
             tab, nj = eng.update_jobs(flat, grad, m, v, hyper, (0.9, 0.999), 1e-8, 0.5)
-            bmap, nb = eng._table_maps[tab.data_ptr()][:2]
+            bmap, nb = eng.table_of(tab).block_map
             assert nb < nj * 256 and int(bmap.view(-1, 4)[:, 0].max()) == nj - 1
             eng.run_table(tab, nj)
         elif fused:

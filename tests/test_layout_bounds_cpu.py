@@ -171,6 +171,24 @@ def test_job_blocks_of_literals():
     assert len(m) == 2 + 2 + 2 + 3 + 2 + 2 + 2 + 2 + 3 + 3 + 3
     assert m[6:9] == [[3, 0, 3, 0], [3, 1, 3, 0], [3, 2, 3, 0]]
     assert C.block_map(rows, 65535)[-1] == [10, 3, 4, 0]
+    # kind 6: [6, src, dst, d0, d1, d2, first copy's strides x 3, second copy's strides 0 and 1, t1 | t2 << 8, its stride 2, 0, ctx, dst2]
+    adam = [
+        # tiled (1 802 240 >= 2^20 elements), copies contiguous in i1 (fA = 1) and in i0 (fB = 0): "different", tiles of
+        # T0 x T1 x T2 = 32 x 16 x 16 -> 32/32 x 256/16 x ceil(220/16) = 1 x 16 x 14 = 224
+        [6, 0, 16, 32, 256, 220, 56320, 1, 256, 1, 32, 1, 8192, 0, 64, 32],
+        # tiled (1 106 263 elements), one copy contiguous in i0: 32 x 8 x 32 cut to 32 x 8 x 29 -> ceil(1031/32) x ceil(37/8) x 1
+        # = 33 x 5 x 1 = 165
+        [6, 0, 16, 1031, 37, 29, 1, 1031, 38147, 0, 0, 1, 0, 0, 64, 0],
+        # the same tensor with both copies contiguous in i2 (fA = fB = 2): flat, ceil(1 106 263 / 256) = 4322 (4321 x 256 = 1 106 176)
+        [6, 0, 16, 1031, 37, 29, 1073, 29, 1, 29, 29899, 1 | (0 << 8), 1, 0, 64, 32],
+        # flat, fewer than 2^20 elements whatever the strides: 64 x 9 x 16 = 9216 = 36 x 256
+        [6, 0, 16, 64, 9, 16, 1, 64, 576, 0, 0, 1, 0, 0, 64, 0],
+        [6, 0, 16, 5, 7, 3, 1, 5, 35, 0, 0, 0, 0, 0, 64, 0],                # 105 elements: 1
+    ]
+    assert [C.job_blocks_of(r) for r in adam] == [224, 165, 4322, 36, 1]
+    assert [C.job_branch(r) for r in adam] == ["run_jobs_k[6,tiled,different]", "run_jobs_k[6,tiled,one]", "run_jobs_k[6,flat,2]",
+                                               "run_jobs_k[6,flat,1]", "run_jobs_k[6,flat,1]"]
+    assert [len(C.block_map([r], 256)) for r in adam] == [224, 165, 256, 36, 1]
 
 
 def test_vote_reference_is_the_oracle():

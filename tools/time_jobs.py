@@ -6,6 +6,8 @@ import torch
 import sfv_amd as sfv
 from importlib import import_module
 trainer_mod = import_module("symbols-from-video_amd.trainer")
+jobs_mod = import_module("symbols-from-video_amd.jobs")
+Col = jobs_mod.Col
 L = sfv._lib
 dev = torch.device("cuda", 0)
 torch.manual_seed(1234)
@@ -25,7 +27,7 @@ for _ in range(3):
     tr.step(item, 0.7)
 torch.cuda.synchronize()
 eng = list(model._engines.values())[0]
-names = {0: "pack", 1: "permute_reduce", 2: "reduce_rows", 3: "conv_pack", 4: "conv_reduce"}
+names = ["pack", "permute_reduce", "reduce_rows", "conv_pack", "conv_reduce", "gather", "adam+pack", "adam"]
 def time_tab(label, tab, n, jl):
     """GPU-side duration of the whole table and of every job alone: the launches are queued behind a device-side
     sleep, so the event pairs bracket kernels, not host launch latency."""
@@ -42,8 +44,7 @@ def time_tab(label, tab, n, jl):
     timed([(tab, n)])
     whole = timed([(tab, n)] * 3)
     # the same table with exactly the workgroups its jobs can use (rbvae_run_jobs_sized)
-    from importlib import import_module as _im
-    bmap, nb = _im("symbols-from-video_amd.engine").job_block_map(jl.rows, dev, 256)
+    bmap, nb = jobs_mod.job_block_map(jl.rows, dev, 256)
     def timed_sized(reps):
         torch.cuda.synchronize()
         torch.cuda._sleep(40_000_000)
@@ -59,18 +60,16 @@ def time_tab(label, tab, n, jl):
     each = timed([(tab[i:i + 1].contiguous(), 1) for i in range(n)])
     print(f"{label}: {n} jobs, all together {min(whole):.1f} us (event pair overhead ~4.8 us included)")
     for i, r in enumerate(jl.rows):
-        print(f"  job {i:2d} {names[r[0]]:15s} dims=({r[3]},{r[4]},{r[5]}) strides=({r[6]},{r[7]},{r[8]}) nslab={r[9]} fast={r[13] >> 32} inner={r[14]}: {each[i]:6.1f} us")
+        dims, strides = ",".join(map(str, r[jobs_mod.DIMS])), ",".join(map(str, r[jobs_mod.STRIDES]))
+        print(f"  job {i:2d} {names[r[Col.KIND]]:15s} dims=({dims}) strides=({strides}) nslab={r[Col.NSLAB]} "
+              f"fast={r[Col.SCALE_FAST] >> 32} inner={r[Col.INNER]}: {each[i]:6.1f} us")
 eng.pack(model._flat)
-for key, val in eng._pack_tab.items():
-    if len(val) == 3:
-        time_tab("pack", *val)
-for sig, (tab, n, jl) in eng._bwd_tab.items():
-    time_tab("bwd reduce", tab, n, jl)
+for key, t in list(eng._pack_tab.items()):
+    if not isinstance(key, tuple):                 # pack() tables are keyed by the flat buffer, update tables by a tuple
+        time_tab("pack", t.rows, t.n, t.jl)
+for t in eng._bwd_tab.values():
+    time_tab("bwd reduce", t.rows, t.n, t.jl)
 
 # the fused update launch (Adam + packed copies), whole and job by job
 tab, nj = eng.update_jobs(model._flat, tr.gflat, tr.m, tr.vv, tr.hyper, tr.betas, tr.eps, 1.0)
-rows = tab.cpu().tolist()
-names.update({5: "gather", 6: "adam+pack", 7: "adam"})
-class _JL: pass
-jl = _JL(); jl.rows = rows
-time_tab("fused update", tab, nj, jl)
+time_tab("fused update", tab, nj, eng.table_of(tab).jl)
