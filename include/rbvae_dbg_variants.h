@@ -13,6 +13,11 @@ extern "C" {
  * pixels per K-slice leave room for the index table.  Returns the previous value. */
 int rbvae_dbg_wgrad_gemm_variant(int v);
 
+/* which path rbvae_deconv_last_fwd_bwd_ok (librbvae_hip) offers its callers: 0 (default) the one-launch kernel where it
+ * covers the shape, 1 never (the query answers 0: rbvae_deconv_last_fused + rbvae_deconv_last_dgrad_fused) -- the same
+ * values and sums bit for bit.  Returns the previous value. */
+int rbvae_dbg_deconv_last_variant(int v);
+
 #ifdef __cplusplus
 }
 #endif

@@ -349,6 +349,18 @@ int rbvae_deconv_last_fused_parts(int dtype, int N, int IH, int IW, int C1, int 
 int rbvae_deconv_last_fused(int dtype, const void* D2, const void* V, int NYP, const float* bias, const void* zero_page,
                             int N, int IH, int IW, int C1, int Cout, float* xr, const float* target, int fd1, int fd2,
                             long fs0, long fs1, long fs2, float* ws, float* dpre, float gscale, void* stream);
+/* rbvae_deconv_last_fused followed by rbvae_deconv_last_dgrad_fused as ONE launch (bf16, Cout <= 4, C1 % 64 == 0,
+ * C1 <= 256; target, ws and dpre required): a workgroup stages its 8x16 block of D2 (plus a one-pixel halo all round)
+ * through LDS once, keeps the block's ReLU gate as bits, leaves xr, ws (parts + 4 x parts, as rbvae_deconv_last_fused_parts defines) and dpre exactly as the first call
+ * does, recomputes dpre on the block's low-side rim instead of reading a neighbour's, and from the dpre patch in LDS
+ * leaves dd2 [N*IH*IW][C1] (W [C1][64] the packed weight of the second call, times gs, kept where D2 > 0), the im2col rows
+ * col [N*IH*IW][64] (NULL: not written) and colsum_ws [rbvae_deconv_last_dgrad_blocks][C1] exactly as the second call
+ * does.  Every value and every partial sum is equal bit for bit to the two launches'.  _ok: 1 when the shape is covered. */
+int rbvae_deconv_last_fwd_bwd_ok(int dtype, int N, int IH, int IW, int C1, int Cout);
+int rbvae_deconv_last_fwd_bwd(int dtype, const void* D2, const void* V, int NYP, const void* W, const float* bias,
+                              const void* zero_page, int N, int IH, int IW, int C1, int Cout, float* xr, const float* target,
+                              int fd1, int fd2, long fs0, long fs1, long fs2, float* ws, float* dpre, float gscale, void* col,
+                              void* dd2, float gs, float* colsum_ws, void* stream);
 int rbvae_sigmoid_bwd_nhwc(const float* g_nchw, const float* xr_nchw, float* dpre_nhwc, int N, int C, int H, int W,
                            void* stream);
 /* Linear with few outputs (percep_RBVAE_model.py:61 forward; :74 backward-data):

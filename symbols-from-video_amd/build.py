@@ -60,6 +60,7 @@ ISA_CHECKED = {
     "conv_s2.hip": ("_ZN5rbvae9conv_s2_k", ("ds_read_b128",)),
     "upconv.hip": ("_ZN5rbvae13upconv_halo_k", ("ds_read_b128",)),
     "conv_first.hip": (("_ZN5rbvae13wgrad_first_k", "_ZN5rbvae18wgrad_first_wide_k"), ("ds_read_b64_tr_b16",)),
+    "deconv_last_bwd.hip": ("_ZN5rbvae21deconv_last_fwd_bwd_k", ("ds_read_b128",)),
 }
 
 

@@ -97,3 +97,12 @@ extern "C" int rbvae_dbg_wgrad_gemm_variant(int v) {
     rbvae::wgrad_gemm_variant = v;
     return old;
 }
+
+// whether rbvae_deconv_last_fwd_bwd_ok (librbvae_hip) offers the one-launch kernel: see include/rbvae_dbg_variants.h;
+// returns the previous value
+namespace rbvae { extern int deconv_last_variant; }
+extern "C" int rbvae_dbg_deconv_last_variant(int v) {
+    const int old = rbvae::deconv_last_variant;
+    rbvae::deconv_last_variant = v;
+    return old;
+}

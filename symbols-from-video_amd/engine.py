@@ -145,7 +145,7 @@ class Saved:
     """Activations one forward call keeps for its backward."""
     __slots__ = ("N", "S", "T", "hw", "train", "tau", "tau_dev", "hard", "col1", "x_in", "fm_in", "a1", "a2", "a3", "e", "hs_enc", "hp_enc",
                  "acts_enc", "cs_enc", "y", "z", "hs_dec", "hp_dec", "acts_dec", "cs_dec", "ds_pad", "f", "d1", "d2",
-                 "xr", "gate_scale", "dpre3", "b3_parts")
+                 "xr", "gate_scale", "dpre3", "b3_parts", "dd2_fused")
 
 
 class Engine:
@@ -258,6 +258,9 @@ class Engine:
         self.bin_bwd_fused = wave_ok
         self.deconv_fused = True
         self.conv_first_fused = True
+        # last deconv forward + loss + input gradient as one launch (csrc/deconv_last_bwd.hip) where forward() is told that
+        # backward() will take dpre3 from it; off: rbvae_deconv_last_fused, then rbvae_deconv_last_dgrad_fused in backward()
+        self.deconv_last_bwd_fused = True
         self._alloc_packed()
 
     # ---- packed weights -------------------------------------------------------
@@ -623,8 +626,11 @@ class Engine:
                 seed: int = 0, need_grad: bool = True, encode_only: bool = False,
                 target: Optional[torch.Tensor] = None, recon_gscale: float = 0.0, kl_p: Optional[float] = None,
                 after_hs=None, defer_losses: bool = False,
-                frame_map: Optional[Tuple[int, int, int, int, int]] = None, tau_dev: Optional[torch.Tensor] = None):
+                frame_map: Optional[Tuple[int, int, int, int, int]] = None, tau_dev: Optional[torch.Tensor] = None,
+                bwd_from_dpre: bool = False):
         """x: [S,T,C,H,W] f32 NCHW frames; U: [S*T, L] uniform noise.
+        bwd_from_dpre: the caller will run backward(g_xr=None) on this call's Saved: the last deconv's input gradient may
+        be computed here, in the launch that forms dpre3 (deconv_last_bwd_fused).
         tau_dev: optional device float the kernels read the temperature from instead of `tau` (graph-replayed
         steps under an annealing schedule; backward() reads the same tensor).
         masks: explicit dropout keep-masks (u8, NHWC rows) for the 4 dropout sites, else a counter hash.
@@ -661,6 +667,7 @@ class Engine:
         sv.N, sv.S, sv.T, sv.hw, sv.train, sv.tau, sv.hard = N, S, T, (H, W), train, tau, hard
         sv.tau_dev = tau_dev
         sv.gate_scale = dscale
+        sv.dd2_fused = None
         # encoder CNN
         sv.a1 = self._E(N * h1 * w1, c1)
         m, mk = dm(0)
@@ -796,6 +803,10 @@ class Engine:
         sv.b3_parts = None
         fparts = L.query("rbvae_deconv_last_fused_parts", self.dt, N, h1, w1, c1, self.out_ch) if (
             self.deconv_fused and k == 3 and (target is None or defer_losses)) else 0
+        nb2 = (L.query("rbvae_deconv_last_dgrad_blocks", self.dt, self.out_ch, H, W, c1, N)
+               if (fparts and self.deconv_last_bwd_fused and bwd_from_dpre and target is not None and need_grad
+                   and defer_losses and self.conv_first_fused and self.K3 == 64
+                   and L.query("rbvae_deconv_last_fwd_bwd_ok", self.dt, N, h1, w1, c1, self.out_ch)) else 0)
         if fparts:
             # last deconv + sigmoid + recon loss as one kernel (products on the matrix cores from an LDS-resident pixel
             # block, kept in f32): no product matrix in HBM, no separate col2im pass
@@ -807,9 +818,21 @@ class Engine:
                 if need_grad:
                     sv.dpre3 = self._E(N, H, W, self.out_ch, dtype=torch.float32)
                     sv.b3_parts = (ws, fparts)
-            L.call("rbvae_deconv_last_fused", self.dt, sv.d2, self.V3p, self.NY, P(f"decoder_cnn.deconv.{i2}.bias"),
-                   self.zero, N, h1, w1, c1, self.out_ch, sv.xr, None if target is None else target.contiguous(), *fm, ws,
-                   sv.dpre3, float(recon_gscale))
+            if nb2:
+                # ... and the layer's input gradient from the same resident block: backward()'s buffers, filled here
+                P1 = N * h1 * w1
+                dd2 = self._buf((N, "dd2"), P1 * c1, self.tdt).view(P1, c1)
+                col3 = (None if self._wf_ksplit(N, self.out_ch, H, W, c1)
+                        else self._buf((N, "col3"), P1 * self.K3, self.tdt).view(P1, self.K3))
+                ws2 = self._buf((N, "colsum_dd2f"), nb2 * c1)
+                sv.dd2_fused = (dd2, col3, ws2, nb2)
+                L.call("rbvae_deconv_last_fwd_bwd", self.dt, sv.d2, self.V3p, self.NY, self.V3f,
+                       P(f"decoder_cnn.deconv.{i2}.bias"), self.zero, N, h1, w1, c1, self.out_ch, sv.xr, target.contiguous(),
+                       *fm, ws, sv.dpre3, float(recon_gscale), col3, dd2, float(sv.gate_scale), ws2)
+            else:
+                L.call("rbvae_deconv_last_fused", self.dt, sv.d2, self.V3p, self.NY, P(f"decoder_cnn.deconv.{i2}.bias"),
+                       self.zero, N, h1, w1, c1, self.out_ch, sv.xr, None if target is None else target.contiguous(), *fm, ws,
+                       sv.dpre3, float(recon_gscale))
         else:
             Y = self._E(N * h1 * w1, self.NY)
             self._gemm(sv.d2, self.V3p, Y, None, None, None, N * h1 * w1, 1, 1, 1, 1, 1, 1, 1, 1, c1, self.NY, c1,
@@ -900,8 +923,13 @@ class Engine:
         if nb:
             # im2col + GEMM + gate + bias-gradient partial sums in one kernel (csrc/conv_first.hip, MODE 1)
             ws = self._buf((N, "colsum_dd2f"), nb * c1)
-            L.call("rbvae_deconv_last_dgrad_fused", self.dt, dpre3, self.V3f, self.zero, col3, sv.d2, dd2, N, oc, H, W, c1,
-                   c1, float(gs), ws)
+            if g_xr is None and sv.dd2_fused is not None:
+                # forward() left dd2, col3 and the column sums in these very buffers (rbvae_deconv_last_fwd_bwd)
+                assert sv.dd2_fused[0].data_ptr() == dd2.data_ptr() and sv.dd2_fused[2].data_ptr() == ws.data_ptr()
+                assert (sv.dd2_fused[1] is None) == (col3 is None) and sv.dd2_fused[3] == nb
+            else:
+                L.call("rbvae_deconv_last_dgrad_fused", self.dt, dpre3, self.V3f, self.zero, col3, sv.d2, dd2, N, oc, H, W,
+                       c1, c1, float(gs), ws)
             self._jobs.add(JOB_ROWS, ws, G(f"decoder_cnn.deconv.{i1}.bias"), (1, 1, c1), (0, 0, 1), nslab=nb, slab=c1)
         else:
             L.call("rbvae_im2col", self.dt, dpre3, H * W * oc, 1, W * oc, oc, N, oc, H, W, h1, w1, k, k, 2, 1, self.K3, col3)

@@ -148,7 +148,8 @@ class FusedTrainer:
         out = eng.forward(model._flat, x.view(2 * B, T, *x.shape[3:]), U, tau, False, self.r, bool(model.training), masks,
                           seed=self._noise_key, need_grad=True, target=x, recon_gscale=2.0 / numel, kl_p=self.p,
                           after_hs=pair_term, defer_losses=True,
-                          frame_map=(B * T, T, T * chw, 2 * T * chw, chw), tau_dev=self.tau_dev)
+                          frame_map=(B * T, T, T * chw, 2 * T * chw, chw), tau_dev=self.tau_dev,
+                          bwd_from_dpre=True)       # backward() below takes dpre3 from this call (g_xr=None)
         sse_ws, nparts, inv_n = out["sse"]
         kl_parts, nkl, kl_scale = out["kl"]
         self.last_saved = out["saved"]          # diagnostics (tests read the device's ReLU decisions from it)

@@ -46,10 +46,11 @@ LAUNCHES = [
     mover("decoder fc 32 -> 4096", 2.1 + 0.3, 0, True),
     gemm("deconv1 forward (4 parity classes)", P2, C, K9 / 4, 128, 128, 0, True),
     gemm("deconv2 forward (4 parity classes)", P1, C, K9 / 4, 128, 128, 0, True),
-    mover("deconv3 + sigmoid + MSE (fused)", 33.5 + 4.2 + 4.2 + 4.2, 0, True),
+    # last deconv forward + loss AND its input gradient, one launch (csrc/deconv_last_bwd.hip): d2 in once, target in, xr and
+    # dpre3 out, dd2 out, im2col rows out
+    mover("deconv3 + sigmoid + MSE + input gradient + gate + im2col rows (fused)", 33.5 + 4.2 + 4.2 + 4.2 + 33.5 + 8.4, 0, True),
     mover("pair term (contrast) value + gradient", 0.1, 1, False),
     # ---- backward: data-gradient chain (critical) ...
-    mover("deconv3 input gradient + gate + im2col rows (fused)", 4.2 + 33.5 + 33.5 + 8.4, 0, True),
     gemm("deconv2 input gradient (conv form)", P2, C, K9, 128, 128, 0, True),
     gemm("deconv1 input gradient (conv form)", P3, C, K9, 64, 64, 0, True),
     mover("decoder fc input gradient", 2.1 + 0.3, 0, True),
