@@ -273,6 +273,22 @@ int rbvae_run_jobs(const void* jobs_dev, int njobs, int blocks_per_job, void* st
  * (16-byte aligned), total_blocks = its entries. */
 int rbvae_job_block_map(const long* rows_host, int njobs, int max_blocks_per_job, int* map_host, int map_capacity);
 int rbvae_run_jobs_sized(const void* jobs_dev, const void* block_map_dev, int total_blocks, void* stream);
+/* The sized launch with its LDS taken from the table itself.  rbvae_run_jobs and rbvae_run_jobs_sized give every workgroup
+ * the largest tile any job can need (36 992 bytes).  rbvae_run_jobs_table takes the host copy of the rows (rows_host,
+ * njobs, max_blocks_per_job: what rbvae_job_block_map built block_map_dev from) next to the device rows and map, and works
+ * out from the rows, inside the library, the workgroups (rbvae_job_block_map's count) and the dynamic LDS
+ * (rbvae_job_lds_bytes).  Results are bit for bit those of rbvae_run_jobs_sized.  order_dev: NULL, or
+ * rbvae_job_launch_order's permutation in device memory -- workgroup b then takes map entry order[b], so that the jobs
+ * with the most bytes per workgroup start first and the one-workgroup jobs fill the slots they leave (a step's update
+ * launch: 1 647 workgroups, 1 024 resident at a time).
+ * rbvae_job_lds_bytes (host): the most LDS a job of the table touches, rounded up to 16 bytes; negative = error.
+ * rbvae_job_launch_order (host): order_host[b] = a permutation of the map's entries, the jobs by falling bytes per
+ * workgroup (ties in table order), each job's entries in their own order; a pure function of the rows; returns the
+ * number of entries, negative = error. */
+int rbvae_job_lds_bytes(const long* rows_host, int njobs);
+int rbvae_job_launch_order(const long* rows_host, int njobs, int max_blocks_per_job, int* order_host, int capacity);
+int rbvae_run_jobs_table(const long* rows_host, int njobs, int max_blocks_per_job, const void* jobs_dev,
+                         const void* block_map_dev, const void* order_dev, void* stream);
 
 /* im2col of a strided f32 image (element strides sn,sc,sh,sw) into col[N*OH*OW][Kpad], column
  * (kh*KW+kw)*C + c: the 3/4-channel first Conv2d (percep_RBVAE_model.py:51) and the last

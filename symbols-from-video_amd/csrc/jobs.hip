@@ -5,12 +5,17 @@
 // the launch from it (a divergence between the two would not give wrong numbers -- every branch is grid-strided -- but
 // silently serialise a job).
 #include "common.h"
+#include <algorithm>
+#include <vector>
 
 #ifndef CPK_CIB
 #define CPK_CIB 64                      // conv_pack_rows: input channels per piece of a wide weight
 #endif
 #ifndef JOBS_TILED_ADAM
 #define JOBS_TILED_ADAM 1               // kind 6: big tensors with permuted copies go through LDS tiles
+#endif
+#ifndef JOBS_STAMPS     // -DJOBS_STAMPS=1 (tools/ab_variants.sh, rbvae_dbg_jobs_stamps): per-workgroup start / end stamps; never in the product build
+#define JOBS_STAMPS 0
 #endif
 #define JOBS_HD __host__ __device__ __forceinline__
 
@@ -84,6 +89,16 @@ JOBS_HD ConvPack conv_pack_geom(const Job& j, unsigned es) {
     return {NCO, cib, (Ci + cib - 1) / cib, (Co + NCO - 1) / NCO, vec_ok};
 }
 
+// LDS pitch of a staged row of `row` elements of es bytes: row + 8 with the row rounded up to a whole number of bank rows
+// (256 bytes = 64 banks x 4), so that pitch * es = (CPK_MAXROW + 8) * es (mod 256): every element of every row sits in the
+// bank it had under the fixed pitch CPK_MAXROW + 8, and the conflicts of both output phases (out 1 reads a wave's lanes
+// from two rows r, out 2 reads the NCO rows at one column) are those of the fixed pitch, read for read.  At the largest
+// row (CPK_MAXROW = 18 bank rows of bf16, 36 of f32) it IS the fixed pitch.
+JOBS_HD unsigned conv_pack_pitch(unsigned row, unsigned es) {
+    const unsigned per = 256 / es;
+    return (row + per - 1) / per * per + 8;
+}
+
 constexpr int CRD_CI = 256, CRD_MAXKK = 16, CRD_ACC = CRD_CI * CRD_MAXKK / 4 / 256;      // float4 accumulators per thread
 // kind 4: workgroup b owns output channel co and the block of <= CRD_CI input channels from ci0
 struct ConvReduce {
@@ -123,6 +138,33 @@ JOBS_HD AdamTiles adam_tiles(const Job& j) {
     g.T0 = T0 < D0 ? T0 : D0; g.T1 = T1 < d1 ? T1 : d1; g.T2 = T2 < d2 ? T2 : d2;
     g.nt0 = (D0 + g.T0 - 1) / g.T0; g.nt1 = (d1 + g.T1 - 1) / g.T1; g.nt2 = (d2 + g.T2 - 1) / g.T2;
     return g;
+}
+
+// kind 2: thousands of partial rows go four columns to a workgroup (rows_wide), else a wave per output (rows_wave)
+JOBS_HD bool rows_is_wide(const Job& j) {
+    return (unsigned)j.nslab >= 1024 && (job_numel(j) & 3) == 0 && ((unsigned)j.slab & 3) == 0 && ((size_t)j.src & 15) == 0;
+}
+
+// LDS a workgroup of the job touches: the end of the highest byte its branch of run_jobs_k reads or writes in the tile
+// (0: the branch uses none).  rbvae_run_jobs_table launches a table with the maximum over its rows.
+JOBS_HD long job_lds_bytes(const Job& j) {
+    switch (j.type) {
+    case JOB_CONV_PACK: {           // NCO rows of the largest piece, cib * kk values, at conv_pack_pitch
+        const unsigned es = conv_pack_f32(j) ? 4 : 2, row = conv_pack_geom(j, es).cib * (unsigned)j.d2;
+        return (long)((16 / es - 1) * conv_pack_pitch(row, es) + row) * es;
+    }
+    case JOB_CONV_REDUCE: {         // [kk][cn + 1] floats, cn = the first (largest) block of input channels
+        const unsigned cn = (unsigned)j.d1 < (unsigned)CRD_CI ? (unsigned)j.d1 : (unsigned)CRD_CI;
+        return (long)(((unsigned)j.d2 - 1) * (cn + 1) + cn) * 4;
+    }
+    case JOB_ADAM_PACK:
+    case JOB_ADAM: {                // tiled: [T0 * T1][T2 + 1] floats
+        const AdamTiles g = adam_tiles(j);
+        return g.tiled ? (long)((g.T0 * g.T1 - 1) * (g.T2 + 1) + g.T2) * 4 : 0;
+    }
+    case JOB_ROWS: return rows_is_wide(j) ? 256 * 16 : 0;      // the tree over the workgroup's 256 float4 sums
+    default: return 0;
+    }
 }
 
 // workgroups a job can use: the loop bound of its branch of run_jobs_k
@@ -174,7 +216,7 @@ __device__ __forceinline__ void conv_pack_rows(const Job& j, unsigned char* lds_
     const ConvPack g = conv_pack_geom(j, sizeof(T));
     const unsigned cib = g.cib;
     const bool vec_ok = g.vec_ok;
-    const unsigned pitch = CPK_MAXROW + 8;
+    const unsigned pitch = conv_pack_pitch(cib * kk, sizeof(T));
     T* wf = (T*)j.dst;
     T* wd = (T*)j.dst2;
     // fused optimiser update (j.inner = AdamCtx*): the block updates exactly the master rows it packs, so the packed
@@ -653,14 +695,22 @@ __device__ __forceinline__ void elem_rows(const Job& j, unsigned bidx, unsigned 
 // Launch shapes: grid (blocks per job, jobs) -- every job gets the same number of workgroups, most of which leave at once --
 // or, with a block map (rbvae_run_jobs_sized), a 1-D grid of exactly the workgroups the jobs need: map[b] = (job, index of
 // the workgroup within the job, workgroups of the job).  A step's update launch was 12 544 workgroups of which ~1 400 had work.
-__global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, const int4* __restrict__ map) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[CPK_LDS_BYTES];
+// The tile is dynamic shared memory: job_lds_bytes of the launch's largest job (rbvae_run_jobs_table) or CPK_LDS_BYTES
+// (rbvae_run_jobs, rbvae_run_jobs_sized), which covers every job there is.
+// `order` (optional): workgroup b takes the map entry order[b] (rbvae_job_launch_order: the heaviest jobs' entries first).
+// The kernel needs 116 VGPRs, so 4 workgroups share a CU whatever the tile: a step's update launch (1 647 workgroups) runs
+// in two rounds of 1 024.  In map order the first round held half of the conv pack workgroups (85 % of the launch's bytes)
+// behind the one-workgroup jobs in front of them; heaviest first, all 512 start at once and the light jobs fill the
+// slots they leave: 27.8 -> 22.4 us from the first start to the last end ("Update launch").  A build of this
+// body held to 72 VGPRs (7 workgroups per CU, the launch resident at once) was not faster than that and is not kept.
+__device__ __forceinline__ void run_job(const Job* __restrict__ jobs, const int4* __restrict__ map, const int* __restrict__ order,
+                                        unsigned char* lds_raw) {
     static_assert(CPK_LDS_BYTES >= (int)sizeof(float) * CRD_MAXKK * (CRD_CI + 1), "the reduce tile fits the pack tile");
     static_assert(CPK_LDS_BYTES >= 256 * 16, "the wide row reduction's tree fits");
     static_assert(CPK_LDS_BYTES >= (int)sizeof(float) * 32 * 16 * (16 + 1), "the largest Adam tile (adam_tiles) fits");
     unsigned bidx = blockIdx.x, nblk = gridDim.x, jidx = blockIdx.y;
     if (map) {
-        const int4 m = map[blockIdx.x];
+        const int4 m = map[order ? (unsigned)order[blockIdx.x] : blockIdx.x];
         jidx = (unsigned)m.x; bidx = (unsigned)m.y; nblk = (unsigned)m.z;
     }
     const Job j = jobs[jidx];
@@ -682,8 +732,7 @@ __global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, 
     }
     if (bidx >= tail_blocks(j)) return;       // this job may need fewer blocks than the launch provides
     if (j.type == JOB_ROWS) {
-        const bool wide = (unsigned)j.nslab >= 1024 && (job_numel(j) & 3) == 0 && ((unsigned)j.slab & 3) == 0 && ((size_t)j.src & 15) == 0;
-        if (wide) rows_wide(j, (float4*)lds_raw, bidx, nblk); else rows_wave(j, bidx, nblk);
+        if (rows_is_wide(j)) rows_wide(j, (float4*)lds_raw, bidx, nblk); else rows_wave(j, bidx, nblk);
     } else if (j.inner) {
         inner_rows(j, bidx, nblk);
     } else {
@@ -691,15 +740,63 @@ __global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, 
     }
 }
 
+#if JOBS_STAMPS
+constexpr size_t JOBS_STAMP_CAP = 4096, JOBS_STAMP_SLOTS = 16;     // workgroups stamped per launch (4 x u64 each), launches kept
+#define JOBS_STAMP_PARAM , unsigned long long* stamps
+#define JOBS_STAMP_ARG , jobs_stamp_slot()
+// [workgroup][start, end (its stores acknowledged), map entry, 0], 100 MHz (tools/jobs_stamps.py)
+#define JOBS_STAMP_START const unsigned long long st_t0 = wall_clock64();
+#define JOBS_STAMP_END                                                                                                        \
+    if (stamps) {                                                                                                             \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                      \
+        __syncthreads();                                                                                                      \
+        if (threadIdx.x == 0 && (size_t)blockIdx.y * gridDim.x + blockIdx.x < JOBS_STAMP_CAP) {                               \
+            unsigned long long* o = stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;                               \
+            o[0] = st_t0; o[1] = wall_clock64(); o[3] = 0;                                                                    \
+            o[2] = map ? (order ? (unsigned)order[blockIdx.x] : blockIdx.x) : blockIdx.y;                                     \
+        }                                                                                                                     \
+    }
+#else
+#define JOBS_STAMP_PARAM
+#define JOBS_STAMP_ARG
+#define JOBS_STAMP_START
+#define JOBS_STAMP_END
+#endif
+
+__global__ __launch_bounds__(256) void run_jobs_k(const Job* __restrict__ jobs, const int4* __restrict__ map,
+                                                  const int* __restrict__ order JOBS_STAMP_PARAM) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    JOBS_STAMP_START
+    run_job(jobs, map, order, lds_raw);
+    JOBS_STAMP_END
+}
+
 }  // namespace rbvae
 
 using namespace rbvae;
 
+#if JOBS_STAMPS
+static unsigned long long* g_jobs_stamps = nullptr;
+static unsigned g_jobs_stamp_launch = 0;
+// the k-th job launch after rbvae_dbg_jobs_stamps writes into slot k % JOBS_STAMP_SLOTS of the buffer (a captured launch
+// keeps the slot it was captured with)
+static unsigned long long* jobs_stamp_slot() {
+    return g_jobs_stamps ? g_jobs_stamps + (size_t)(g_jobs_stamp_launch++ % JOBS_STAMP_SLOTS) * JOBS_STAMP_CAP * 4 : nullptr;
+}
+/* stamped builds only (include/rbvae_dbg.h): later job launches write per-workgroup stamps into buf */
+extern "C" int rbvae_dbg_jobs_stamps(unsigned long long* buf, void* stream) {
+    (void)stream;
+    g_jobs_stamps = buf;
+    g_jobs_stamp_launch = 0;
+    return RBVAE_OK;
+}
+#endif
+
 extern "C" int rbvae_run_jobs(const void* jobs_dev, int njobs, int blocks_per_job, void* stream) {
     RBVAE_CHECK_ARG(jobs_dev && njobs > 0 && blocks_per_job > 0, "run_jobs: bad arguments");
     RBVAE_CHECK_ARG(njobs <= 65535, "run_jobs: too many jobs");
-    hipLaunchKernelGGL(run_jobs_k, dim3(blocks_per_job, njobs), dim3(256), 0, (hipStream_t)stream, (const Job*)jobs_dev,
-                       (const int4*)nullptr);
+    hipLaunchKernelGGL(run_jobs_k, dim3(blocks_per_job, njobs), dim3(256), CPK_LDS_BYTES, (hipStream_t)stream, (const Job*)jobs_dev,
+                       (const int4*)nullptr, (const int*)nullptr JOBS_STAMP_ARG);
     RBVAE_CHECK_LAUNCH("run_jobs");
     return RBVAE_OK;
 }
@@ -728,8 +825,88 @@ extern "C" int rbvae_job_block_map(const long* rows_host, int njobs, int max_blo
 extern "C" int rbvae_run_jobs_sized(const void* jobs_dev, const void* block_map_dev, int total_blocks, void* stream) {
     RBVAE_CHECK_ARG(jobs_dev && block_map_dev && total_blocks > 0, "run_jobs_sized: bad arguments");
     RBVAE_CHECK_ARG((uintptr_t)block_map_dev % 16 == 0, "run_jobs_sized: the block map must be 16-byte aligned");
-    hipLaunchKernelGGL(run_jobs_k, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, (const Job*)jobs_dev,
-                       (const int4*)block_map_dev);
+    hipLaunchKernelGGL(run_jobs_k, dim3(total_blocks), dim3(256), CPK_LDS_BYTES, (hipStream_t)stream, (const Job*)jobs_dev,
+                       (const int4*)block_map_dev, (const int*)nullptr JOBS_STAMP_ARG);
     RBVAE_CHECK_LAUNCH("run_jobs_sized");
+    return RBVAE_OK;
+}
+
+// workgroups of the table (job_blocks_of, at most max_blocks_per_job per job: rbvae_job_block_map's count) and the LDS its
+// largest job touches, 16-byte aligned
+static long table_blocks_and_lds(const Job* jobs, int njobs, int max_blocks_per_job, long* lds) {
+    long total = 0, need = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const long nb = job_blocks_of(jobs[j]), l = job_lds_bytes(jobs[j]);
+        total += nb < 1 ? 1 : (nb > max_blocks_per_job ? max_blocks_per_job : nb);
+        if (l > need) need = l;
+    }
+    *lds = (need + 15) / 16 * 16;
+    return total;
+}
+
+extern "C" int rbvae_job_lds_bytes(const long* rows_host, int njobs) {
+    if (!rows_host || njobs <= 0) return fail(RBVAE_E_INVALID, "job_lds_bytes: bad arguments");
+    long lds = 0;
+    table_blocks_and_lds((const Job*)rows_host, njobs, 1, &lds);
+    if (lds > CPK_LDS_BYTES) return fail(RBVAE_E_INVALID, "job_lds_bytes: a job of %ld bytes (at most %d)", lds, CPK_LDS_BYTES);
+    return (int)lds;
+}
+
+// what a workgroup of the job moves, in bytes (an estimate: it only ranks the jobs of a launch)
+static long job_block_weight(const Job& j) {
+    switch (j.type) {
+    case JOB_CONV_PACK: {       // NCO rows of a piece: f32 in, two packed copies out; with the context g, m, v in and w, m, v out too
+        const long es = conv_pack_f32(j) ? 4 : 2, n = (16 / es) * (long)conv_pack_geom(j, (unsigned)es).cib * j.d2;
+        return n * (4 + 2 * es + (j.inner ? 24 : 0));
+    }
+    case JOB_CONV_REDUCE: return (long)((unsigned)j.d1 < (unsigned)CRD_CI ? j.d1 : CRD_CI) * j.d2 * 4 * (j.nslab + 1);
+    case JOB_GATHER: return j.d2 * 32;
+    case JOB_ADAM_PACK:
+    case JOB_ADAM: {
+        const AdamTiles g = adam_tiles(j);
+        const long n = g.tiled ? (long)g.T0 * g.T1 * g.T2 : (adam_numel(j) < 256 ? adam_numel(j) : 256);
+        return n * (j.type == JOB_ADAM ? 28 : 32);
+    }
+    case JOB_ROWS: return 16 * j.nslab;
+    default: return 256 * 4 * (j.nslab + 1) * (j.inner ? j.d2 : 1);
+    }
+}
+
+extern "C" int rbvae_job_launch_order(const long* rows_host, int njobs, int max_blocks_per_job, int* order_host, int capacity) {
+    if (!rows_host || njobs <= 0 || max_blocks_per_job <= 0 || !order_host) return fail(RBVAE_E_INVALID, "job_launch_order: bad arguments");
+    const Job* jobs = (const Job*)rows_host;
+    long lds = 0;
+    const long total = table_blocks_and_lds(jobs, njobs, max_blocks_per_job, &lds);
+    if (total > capacity) return fail(RBVAE_E_INVALID, "job_launch_order: %ld entries do not fit %d", total, capacity);
+    // jobs by falling weight (ties: table order), each job's map entries in their own order
+    std::vector<int> by(njobs);
+    std::vector<long> first(njobs), w(njobs);
+    long at = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const long nb = job_blocks_of(jobs[j]);
+        by[j] = j; first[j] = at; w[j] = job_block_weight(jobs[j]);
+        at += nb < 1 ? 1 : (nb > max_blocks_per_job ? max_blocks_per_job : nb);
+    }
+    std::stable_sort(by.begin(), by.end(), [&](int a, int b) { return w[a] > w[b]; });
+    long o = 0;
+    for (int k = 0; k < njobs; ++k) {
+        const int j = by[k];
+        const long end = j + 1 < njobs ? first[j + 1] : total;
+        for (long b = first[j]; b < end; ++b) order_host[o++] = (int)b;
+    }
+    return (int)total;
+}
+
+extern "C" int rbvae_run_jobs_table(const long* rows_host, int njobs, int max_blocks_per_job, const void* jobs_dev,
+                                    const void* block_map_dev, const void* order_dev, void* stream) {
+    RBVAE_CHECK_ARG(rows_host && njobs > 0 && max_blocks_per_job > 0 && jobs_dev && block_map_dev, "run_jobs_table: bad arguments");
+    RBVAE_CHECK_ARG((uintptr_t)block_map_dev % 16 == 0, "run_jobs_table: the block map must be 16-byte aligned");
+    long lds = 0;
+    const long total = table_blocks_and_lds((const Job*)rows_host, njobs, max_blocks_per_job, &lds);
+    RBVAE_CHECK_ARG(total < (1l << 31), "run_jobs_table: too many workgroups");
+    RBVAE_CHECK_ARG(lds <= CPK_LDS_BYTES, "run_jobs_table: a job of %ld bytes of LDS (at most %d)", lds, CPK_LDS_BYTES);
+    hipLaunchKernelGGL(run_jobs_k, dim3((unsigned)total), dim3(256), (size_t)lds, (hipStream_t)stream, (const Job*)jobs_dev,
+                       (const int4*)block_map_dev, (const int*)order_dev JOBS_STAMP_ARG);
+    RBVAE_CHECK_LAUNCH("run_jobs_table");
     return RBVAE_OK;
 }

@@ -195,6 +195,11 @@ class Engine:
         self.last_wgrad_kernel = None  # kernel family the last _wgrad() call launched (bench.py's roofline leg keys its timers by it)
         self._job_blocks = 256      # workgroups per job of a batched job launch (at most)
         self.sized_jobs = 2         # job tables launched with exactly the workgroups they can use: 0 none, 1 the update table, 2 all
+        self.table_launch = True    # sized launches through rbvae_run_jobs_table (LDS from the rows); False: rbvae_run_jobs_sized
+        # ... their heaviest jobs' workgroups first (rbvae_job_launch_order): 0 none, 1 the update table, 2 all.  The reduce
+        # launches keep the map's order: heaviest first gives them nothing at the bench shape and costs the native step 12 us
+        # ("Update launch")
+        self.jobs_heavy_first = 1
         self._side: Optional[torch.cuda.Stream] = None
         # Side stream (graph capture turns the fork / join into graph edges; `overlap = False`: everything in issue order on
         # one stream -- bench.py's `isolated` leg).  What rides it was settled by same-GPU sweeps in rounds 1-2 (ms/step):
@@ -294,12 +299,14 @@ class Engine:
         return self._tables.get(tab.data_ptr())
 
     def run_table(self, tab: torch.Tensor, n: int, kind: int = 2):
-        """One batched job launch of `tab` (n rows): sized (rbvae_run_jobs_sized, exactly the workgroups it can use) when it
-        is one of the engine's uploaded tables and sized_jobs covers its kind (1 = the optimiser update table, 2 = the
-        pack / reduce tables)."""
+        """One batched job launch of `tab` (n rows): sized (exactly the workgroups it can use, and through
+        rbvae_run_jobs_table the LDS its rows need and the heaviest jobs first) when it is one of the engine's uploaded
+        tables and sized_jobs covers its kind (1 = the optimiser update table, 2 = the pack / reduce tables)."""
         t = self._tables.get(tab.data_ptr())
         if t is None or self.sized_jobs < kind:
             L.call("rbvae_run_jobs", tab, n, self._job_blocks)
+        elif self.table_launch:
+            t.run(self.jobs_heavy_first >= kind)
         else:
             L.call("rbvae_run_jobs_sized", tab, *t.block_map)
 

@@ -127,10 +127,39 @@ def job_block_map(rows, device, cap):
     return torch.from_numpy(m).to(device), total
 
 
+def job_lds_bytes(rows):
+    """LDS of a launch of `rows` (rbvae_job_lds_bytes): the most any of its jobs touches, rounded up to 16 bytes."""
+    arr = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(len(rows), 16))
+    n = L.query("rbvae_job_lds_bytes", arr.ctypes.data, len(rows))
+    if n < 0:
+        raise RuntimeError("rbvae_job_lds_bytes: " + L.lib().rbvae_last_error().decode())
+    return n
+
+
+def job_launch_order(rows, cap):
+    """rbvae_job_launch_order: the permutation of the block map's entries that hands the heaviest jobs' entries out first
+    (int32 numpy array)."""
+    arr = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(len(rows), 16))
+    total = L.query("rbvae_job_block_map", arr.ctypes.data, len(rows), cap, None, 0)
+    order = np.empty(max(total, 1), dtype=np.int32)
+    if total <= 0 or L.query("rbvae_job_launch_order", arr.ctypes.data, len(rows), cap, order.ctypes.data, total) != total:
+        raise RuntimeError("rbvae_job_launch_order: " + L.lib().rbvae_last_error().decode())
+    return order
+
+
 class JobTable:
     """A JobList on the device: `rows` (device tensor) and their count `n`, `block_map` = (map, workgroups) with at most
-    `cap` workgroups per job; `jl` keeps the addressed tensors alive."""
+    `cap` workgroups per job; `jl` keeps the addressed tensors alive.  `host_rows` (the rows as the library reads them on
+    the host), `cap` and `order` (rbvae_job_launch_order's permutation on the device) are what rbvae_run_jobs_table takes."""
 
     def __init__(self, jl: JobList, device, cap):
         self.jl, self.n, self.rows = jl, len(jl.rows), jl.upload(device)
         self.block_map = job_block_map(jl.rows, device, cap)
+        self.cap = cap
+        self.host_rows = np.ascontiguousarray(np.array(jl.rows, dtype=np.int64).reshape(self.n, 16))
+        self.order = torch.from_numpy(job_launch_order(jl.rows, cap)).to(device)
+
+    def run(self, heavy_first=False):
+        """One launch of the table, sized by the library from the rows (rbvae_run_jobs_table)."""
+        L.call("rbvae_run_jobs_table", self.host_rows.ctypes.data, self.n, self.cap, self.rows, self.block_map[0],
+               self.order if heavy_first else None)
