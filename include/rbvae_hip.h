@@ -1041,6 +1041,46 @@ int rbvae_hmm_posterior(const double* alpha, const double* beta, const double* e
 int rbvae_hmm_viterbi(const double* logb, int N, int K, const double* log_pi, const double* log_A, unsigned char* back,
                       int* path, double* score, const int* state, void* stream);
 
+/* ---- Bernoulli models of the hard codes (csrc/bernoulli.hip) -------------------------------------------------
+ * A state is a vector of bit probabilities: theta f64 [K][L], with logt = log theta and logf = log(1 - theta) as the M-step
+ * writes them.  The codes are bit-packed, bits uint32 [N][4] (16-byte aligned): bit l of row i sits in word l / 32 at
+ * position l % 32, bits from L upward are zero.  bernoulli.py drives a mixture with rbvae_bern_estep / _mstep and
+ * rbvae_gmm_decide, and a hidden Markov model with rbvae_bern_emit, rbvae_hmm_forward / _backward / _posterior,
+ * rbvae_bern_mstep on the posterior and rbvae_gmm_decide.  The limits are the mixture's: 1 <= L <= 128, 1 <= K <= 256,
+ * K <= N <= 1048576 and N K <= 2^26 (rbvae_bern_ok = rbvae_gmm_ok; rbvae_bern_pack takes K = 1); rbvae_bern_emit also needs
+ * rbvae_hmm_ok(N, L, K).  Anything else makes every entry return RBVAE_E_UNSUPPORTED without a launch; a NULL pointer or a
+ * prior that is not > 0 (NaN included) RBVAE_E_INVALID.  All arithmetic is f64, never contracted; exp and log are the device
+ * library's.  No floating-point atomics: every sum has one fixed order and two runs agree bit for bit.
+ *
+ * state is the mixture's int32 [4] = {done, n_iter, why, 0} and may be NULL; with done set emit, estep and mstep return
+ * without writing anything.  rbvae_bern_pack takes no state.
+ * rbvae_bern_pack: bit l of row i = codes[i][l] > 0.5 (symbols.code_symbols' rule; NaN gives 0); codes f32 [N][L]; each row is
+ * one 16-byte store.
+ * rbvae_bern_emit: lb_kt = sum_l (bit_tl ? logt_kl : logf_kl) with l ascending from zero, a running sum from zero: selections
+ * and additions only.  logb f64 [K][N] = lb; rowmax f64 [N]: m_t = max_k lb_kt; e f64 [N][K]: e_tk = exp(lb_kt - m_t):
+ * rbvae_hmm_emit's layouts, so the recursions run unchanged.
+ * rbvae_bern_estep: lp_ik = (the sum above) + logw_k, added last; m_i = max_k lp_ik; lognorm_i = m_i + log(sum_k exp(lp_ik -
+ * m_i)) with k ascending from zero; resp_ki = exp(lp_ik - lognorm_i), resp f64 [K][N] (component-major); label_i = the k of the
+ * largest lp_ik (a tie goes to the lower k).  lognorm f64 [N]; resp and label int32 [N] may be NULL.  resp is first used to
+ * hold lp.  In both entries the two log tables pass through LDS rbvae_bern_chunk_components(L) = 2048 / L components at a time.
+ * rbvae_bern_mstep: two stages, blocked as rbvae_gmm_mstep's first pass: min(256, ceil(N / 256)) blocks of ceil(N / blocks)
+ * consecutive rows; each cell's partial is added in ascending row order from zero, the partials then in block order from
+ * zero.  S_kl = sum_i resp_ki over the rows whose bit l is set (no product: the term is added or not); nk_k = sum_i resp_ki;
+ * theta_kl = (S_kl + prior) / (nk_k + 2 prior); logt_kl = log theta_kl; logf_kl = log(((nk_k - S_kl) + prior) / (nk_k + 2 prior));
+ * weights_k = nk'_k / sum_k nk'_k with nk'_k = nk_k + 10 * 2^-52 and k ascending from zero; logw_k = log weights_k.  A component
+ * without mass follows the same formulas: theta = 1 / 2.  ws: rbvae_bern_ws_bytes(N, L, K) = 8 blocks K (L + 1) bytes, the
+ * block partials f64 [blocks][K][L + 1]: cell (k, l) holds the block's part of S_kl and cell (k, L) that of nk_k. */
+int rbvae_bern_ok(int N, int L, int K);
+int rbvae_bern_chunk_components(int L);
+size_t rbvae_bern_ws_bytes(int N, int L, int K);
+int rbvae_bern_pack(const float* codes, int N, int L, uint32_t* bits, void* stream);
+int rbvae_bern_emit(const uint32_t* bits, int N, int L, const double* logt, const double* logf, int K, double* logb,
+                    double* rowmax, double* e, const int* state, void* stream);
+int rbvae_bern_estep(const uint32_t* bits, int N, int L, const double* logt, const double* logf, const double* logw, int K,
+                     double* resp, double* lognorm, int* label, const int* state, void* stream);
+int rbvae_bern_mstep(const uint32_t* bits, int N, int L, const double* resp, int K, double prior, double* weights,
+                     double* logw, double* theta, double* logt, double* logf, double* ws, const int* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

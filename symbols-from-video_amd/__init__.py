@@ -39,6 +39,10 @@ from . import hmm as _hmm_module  # noqa: F401  (the module is sfv.hmm_model: th
 from .hmm import (HMMResult, hmm, hmm_aic, hmm_bic, hmm_forward_backward, hmm_predict, hmm_predict_proba,  # noqa: F401
                   hmm_score, hmm_score_samples, hmm_select, hmm_viterbi, latent_hmm)
 hmm_model = _hmm_module
+from . import bernoulli  # noqa: F401
+from .bernoulli import (BHMMResult, BMMResult, bhmm, bhmm_aic, bhmm_bic, bhmm_predict, bhmm_predict_proba,  # noqa: F401
+                        bhmm_score, bhmm_score_samples, bhmm_select, bmm, bmm_aic, bmm_bic, bmm_predict, bmm_predict_proba,
+                        bmm_score, bmm_score_samples, bmm_select, latent_code_models, pack_codes)
 from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)

@@ -13,7 +13,8 @@ segments.segment's K contiguous runs cannot express, and the posterior is smooth
   latent_hmm            the fit at the number of states of the script's data, scored against the states and the flags
 The start is a labelling (symbols.kmeans' by default, as mixture.gmm takes it): the emissions are its one-hot posterior's
 M-step, A_ij = (n_ij + 1) / (sum_j n_ij + K) from its transition counts and pi = 1 / K.  Full covariances, several
-sequences, Bernoulli emissions for the hard codes, priors on A, a blocked Viterbi and matrix-core products are not built.
+sequences, priors on A, a blocked Viterbi and matrix-core products are not built; Bernoulli emissions for the hard codes are
+bernoulli.bhmm, which runs this module's recursions, posterior and Viterbi on them.
 There is no host path: a matrix on the CPU raises.  The shapes are rbvae_hmm_ok's.
 """
 from __future__ import annotations

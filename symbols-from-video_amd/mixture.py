@@ -12,8 +12,8 @@ responsibilities are soft symbols; its per-frame log-likelihood drops where a fr
 The start is symbols.kmeans' labelling (scikit-learn's own start: KMeans(n_clusters=K, n_init=1) from the same RandomState)
 or any labelling; its one-hot responsibilities go through one M-step (which divides the weights by their sum, where
 scikit-learn's initialisation divides by N: the sums differ by K * 10 * 2^-52).  Full, tied and spherical covariance,
-n_init > 1, the other init_params, warm start and a Bernoulli mixture for the hard codes are not built.  There is no host
-path: a matrix on the CPU raises.  The shapes are rbvae_gmm_ok's, also for prediction: X needs at least K rows.
+n_init > 1, the other init_params and warm start are not built; the Bernoulli mixture for the hard codes is bernoulli.bmm.
+There is no host path: a matrix on the CPU raises.  The shapes are rbvae_gmm_ok's, also for prediction: X needs at least K rows.
 """
 from __future__ import annotations
 
