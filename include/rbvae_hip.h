@@ -1081,6 +1081,51 @@ int rbvae_bern_estep(const uint32_t* bits, int N, int L, const double* logt, con
 int rbvae_bern_mstep(const uint32_t* bits, int N, int L, const double* resp, int K, double prior, double* weights,
                      double* logw, double* theta, double* logt, double* logf, double* ws, const int* state, void* stream);
 
+/* ---- Density clustering on a bit-packed radius graph: DBSCAN (csrc/dbscan.hip) ---------------------------------
+ * scikit-learn 1.7.2's DBSCAN in its order-free form: j is in N(i) iff d(i, j) <= eps (i itself included); row i is core iff
+ * |N(i)| >= min_samples; the clusters are the connected components of the core rows under j in N(i), numbered in ascending
+ * order of their smallest core index; a non-core row with a core neighbour takes the lowest id among its core neighbours'
+ * clusters; every other non-core row is -1.  The graph is a bit matrix adj uint64 [N][W], W = rbvae_dbscan_words(N) =
+ * ceil(N / 64): bit j % 64 of word j / 64 of row i says j in N(i); bits of columns >= N are zero.  The limits are
+ * 2 <= N <= 65536 and 1 <= L <= 128 (rbvae_dbscan_ok; the entries without L take L = 1); anything else makes every entry
+ * return RBVAE_E_UNSUPPORTED without a launch, a NULL pointer, min_samples < 1, eps2 negative or NaN, or max_bits outside
+ * [0, L] RBVAE_E_INVALID.  Distances are f64 from rbvae_knn's device function; everything behind the comparison is integer.
+ * No floating-point atomics; the integer atomicMin of a round gives the same buffer in any order, so two runs agree bit for
+ * bit, the number of rounds included.
+ *
+ * rbvae_dbscan_adj: X f32 [N][L]; the bit is set iff d2(i, j) = sum_l (x_il - x_jl)^2 <= eps2 with l ascending, each
+ * difference exact in f64, each square and each addition rounded once (rbvae_knn's d2, which is symmetric in i and j); a NaN
+ * compares false.  A workgroup owns one word (64 columns, a lane each, held in LDS as f32 [L][65]) and 256 query rows, which
+ * pass through LDS as f64 sixteen at a time; a wave's ballot is the word.  cnt int32 [N]: the row's popcount, from a second
+ * launch over adj.
+ * rbvae_dbscan_adj_bits: bits uint32 [N][4] as rbvae_bern_pack writes them (bits from L upward zero); the bit is set iff
+ * popcount(bits_i xor bits_j) <= max_bits.  cnt as above.
+ * rbvae_dbscan_core: core_mask uint64 [W]: bit i is cnt[i] >= min_samples (bits >= N zero); f int32 [N]: i for a core row,
+ * N for the others.
+ * rbvae_dbscan_round: one synchronous (Jacobi) round of FastSV over the core rows, edges adj[u] & core_mask:
+ *   gf[u] = f_in[f_in[u]]; mn[u] = min of gf[v] over the core v in N(u), v != u (N without one); f_out = f_in; then
+ *   atomicMin(f_out[f_in[u]], mn[u]), atomicMin(f_out[u], mn[u]), atomicMin(f_out[u], gf[u]) for every core u.
+ * Three launches: the copy, the minima, and one workgroup that compares.  state int32 [4] = {done, n_rounds, changed, 0}:
+ * with done set nothing is written; otherwise n_rounds += 1, changed = (any f_out[u] != f_in[u]) and done = !changed.  The
+ * fixed point is f[u] = the smallest core index of u's component.  f_in and f_out are distinct int32 [N]; an entry of f_in
+ * outside [0, N) is read as N and never followed.
+ * rbvae_dbscan_labels: f is the fixed point.  Roots are the core rows with f[i] == i; cid(r) = the number of roots below r,
+ * from the popcounts of a root mask and a scan of its at most 1024 word totals in one workgroup; n_clusters[0] = the number
+ * of roots.  labels int32 [N]: cid(f[i]) for a core row; for the others cid(min f[j] over the core j in N(i)), or -1
+ * without one (cid is monotone in the root, so the smallest root gives the lowest id).  ws: rbvae_dbscan_ws_bytes(N) = 16 W
+ * bytes, 8-byte aligned: the root mask uint64 [W], then the words' exclusive totals int32 [W]. */
+int rbvae_dbscan_ok(int N, int L);
+int rbvae_dbscan_words(int N);
+size_t rbvae_dbscan_ws_bytes(int N);
+int rbvae_dbscan_adj(const float* X, int N, int L, double eps2, unsigned long long* adj, int* cnt, void* stream);
+int rbvae_dbscan_adj_bits(const uint32_t* bits, int N, int L, int max_bits, unsigned long long* adj, int* cnt,
+                          void* stream);
+int rbvae_dbscan_core(const int* cnt, int N, int min_samples, unsigned long long* core_mask, int* f, void* stream);
+int rbvae_dbscan_round(const unsigned long long* adj, const unsigned long long* core_mask, int N, const int* f_in,
+                       int* f_out, int* state, void* stream);
+int rbvae_dbscan_labels(const unsigned long long* adj, const unsigned long long* core_mask, const int* f, int N,
+                        int* labels, int* n_clusters, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

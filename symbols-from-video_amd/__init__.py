@@ -43,6 +43,9 @@ from . import bernoulli  # noqa: F401
 from .bernoulli import (BHMMResult, BMMResult, bhmm, bhmm_aic, bhmm_bic, bhmm_predict, bhmm_predict_proba,  # noqa: F401
                         bhmm_score, bhmm_score_samples, bhmm_select, bmm, bmm_aic, bmm_bic, bmm_predict, bmm_predict_proba,
                         bmm_score, bmm_score_samples, bmm_select, latent_code_models, pack_codes)
+from . import density  # noqa: F401
+from .density import (DBSCANResult, dbscan, dbscan_sweep, k_distances, latent_density, noise_runs,  # noqa: F401
+                      radius_graph, suggest_eps)
 from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)
