@@ -1126,6 +1126,77 @@ int rbvae_dbscan_round(const unsigned long long* adj, const unsigned long long* 
 int rbvae_dbscan_labels(const unsigned long long* adj, const unsigned long long* core_mask, const int* f, int N,
                         int* labels, int* n_clusters, void* ws, void* stream);
 
+/* ---- Density clustering at every radius: HDBSCAN* (csrc/hdbscan.hip) -------------------------------------------
+ * Campello, Moulavi, Zimek and Sander 2015, Algorithm 1 with "edges of equal weight are removed simultaneously", in an
+ * order-free form (DESIGN.md section 7 says why scikit-learn's HDBSCAN cannot be the specification where weights tie).
+ * d2(i, j) is rbvae_knn's; core2[i] is the (m - 1)-th smallest d2(i, j) over j != i, column m - 2 of rbvae_knn(X, k = m - 1),
+ * and 0 for m = 1 (min_samples = m counts the row itself); w2(i, j) = max(core2[i], core2[j], d2(i, j)).  Edges are totally
+ * ordered by the key (w2, lo, hi), lo = min(i, j), hi = max(i, j); under a strict total order the minimum spanning tree is
+ * unique, and that edge set is what the device computes.  The limits are 2 <= N <= 16384 and 1 <= L <= 128 (rbvae_mst_ok;
+ * rbvae_mst_start takes L = 1); anything else makes the two device entries return RBVAE_E_UNSUPPORTED without a launch; a
+ * NULL pointer, a buffer that is not aligned to its element (ws, core2, w2: 8 bytes), or two buffers that overlap (X and core2,
+ * which are only read, excepted) RBVAE_E_INVALID.  A refused call writes nothing.  X and core2 must be finite: the entries do
+ * not look (density.py does).  No floating-point atomics.
+ *
+ * rbvae_mst_ws_bytes(N): the size of ws, 128 N bytes (0 outside the limits); 8-byte aligned; its content between the calls
+ * belongs to the library.
+ * rbvae_mst_start: comp int32 [N] = 0 .. N - 1 (every row its own component), state int32 [4] = {done = 0, n_rounds = 0,
+ * n_components = N, n_edges = 0}, and the per-component minima in ws cleared.
+ * rbvae_mst_round: one Boruvka round, five launches; with done set every kernel returns at once and nothing is written.
+ *   search   for every row i the least (w2(i, j), j) over the rows j with comp[j] != comp[i] -- for a fixed i that is the
+ *            order of the key.  A workgroup owns 32 query rows (f64 in LDS, read as a broadcast) and one of up to 8 slices of
+ *            the columns, which pass through LDS 64 at a time as f32 [L][65]; a lane owns a column of the tile, carries four
+ *            query rows side by side and keeps each row's running minimum in registers; one butterfly per row at the end.
+ *   minima   a thread per row merges the slices in their order, then atomicMin of the bits of w2 (a non-negative f64 orders
+ *            as a uint64) into its component; then, among the rows that hold that minimum, atomicMin of (lo << 32 | hi).
+ *            Both results are the same in whatever order the atomics land.
+ *   hook     component c (c = comp[c]) hooks onto the component t at the other end of its edge, unless t chose the same edge
+ *            and c < t; every component appends its edge at n_edges++, but of two that chose the same edge only the side
+ *            that holds lo does, so that edge is emitted once.  (The keys do not increase along c -> t(c) -> ...; around a cycle
+ *            they are equal, the order is strict, so the cycle is one edge and has two members.)
+ *   merge    one workgroup: pointer jumping to the roots, comp[i] = the smallest row of i's new component, n_rounds += 1,
+ *            n_components, and done = (n_components == 1).
+ * edges int32 [N - 1][2] (lo < hi) and w2 f64 [N - 1] fill up over the rounds, at most ceil(log2 N) of them; their order is
+ * the one in which the counter was handed out.  THE CALLER SORTS them by (w2, lo, hi) (density.mutual_reachability_mst does,
+ * on the device): the key is a strict total order, so the sorted list, like n_rounds, is the same bit for bit in every run. */
+int rbvae_mst_ok(int N, int L);
+size_t rbvae_mst_ws_bytes(int N);
+int rbvae_mst_start(int N, int* comp, int* state, void* ws, void* stream);
+int rbvae_mst_round(const float* X, const double* core2, int N, int L, int* comp, int* edges, double* w2, int* state,
+                    void* ws, void* stream);
+/* The first launch of rbvae_mst_round alone, for timing it (tools/run_hdbscan.py): same arguments and checks; it writes the
+ * slices' minima into ws and nothing else, so it may be repeated before the round proper. */
+int rbvae_mst_search(const float* X, const double* core2, int N, int L, int* comp, int* edges, double* w2, int* state,
+                     void* ws, void* stream);
+/* The host half: HOST pointers, no stream, no GPU call (they run on a machine without one), nothing retained.
+ * edges int32 [N - 1][2] and d f64 [N - 1] = sqrt(w2), sorted by the key.  They must span 0 .. N - 1 as a tree (checked by
+ * union-find) and d must be finite, non-negative and ascending; anything else, min_cluster_size outside [2, N], a method other
+ * than 0 (excess of mass) or 1 (leaves), a negative or NaN cut_distance or a NULL pointer returns RBVAE_E_INVALID, N outside
+ * [2, 16384] RBVAE_E_UNSUPPORTED, and nothing is written.  Iterative throughout (a chain's dendrogram is N deep); O(N log N).
+ *
+ * rbvae_hdbscan_tree.  Levels: the distinct values of d, ascending; lambda = 1 / d, +inf at d = 0.  Dendrogram: all edges of
+ * one level are added at once, and every component that absorbed r >= 2 older ones is one node with r children.  Condensed
+ * tree, top down: the root cluster is born at lambda = 0; at a node visited as part of cluster C at lambda, a child is big
+ * when it has >= min_cluster_size rows; with >= 2 big children C ends and each is a new cluster born at lambda, with exactly
+ * one C continues into it, with none C ends; the rows of the other children leave C at lambda.  stability(C) = the sum over
+ * C's levels, lambda ascending, of (lambda - birth(C)) * n, n the whole number of rows leaving C there (those of the big
+ * children of a split included): one product and one addition per level.  lambda_max(C) is C's last level.  method 0: the
+ * clusters deepest first, the root left out: with children whose stabilities (propagated, added in table order from 0) sum to
+ * MORE than C's, C is dropped and takes that sum; otherwise C is selected and its descendants are dropped.  method 1: the
+ * clusters without children, the root left out.  A row takes the nearest selected cluster from the one it left upwards, else
+ * -1; the selected clusters are numbered by their smallest row, ascending.  prob = 0 for -1; 1 where lambda_max(C) == 0 or
+ * the row's lambda is inf; otherwise min(lambda_row, lambda_max(C)) / lambda_max(C).
+ * The cluster table (every cl_* buffer holds N entries; n_table[0] = the number written, at least 1): the root first, then
+ * (birth, smallest row) ascending, so a parent stands before its children; cl_parent (-1 for the root), cl_birth,
+ * cl_lambda_max, cl_stability (a cluster's own, not the propagated one), cl_size, cl_selected (0 / 1), cl_min_row.
+ * rbvae_hdbscan_cut (DBSCAN* at one radius): the components of the edges with d <= cut_distance; those with fewer than
+ * min_cluster_size rows are -1, the others numbered by their smallest row; n_clusters[0] their number. */
+int rbvae_hdbscan_tree(const int* edges, const double* d, int N, int min_cluster_size, int method, int* labels, double* prob,
+                       int* cl_parent, double* cl_birth, double* cl_lambda_max, double* cl_stability, int* cl_size,
+                       int* cl_selected, int* cl_min_row, int* n_table);
+int rbvae_hdbscan_cut(const int* edges, const double* d, int N, double cut_distance, int min_cluster_size, int* labels,
+                      int* n_clusters);
+
 #ifdef __cplusplus
 }
 #endif

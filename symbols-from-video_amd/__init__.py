@@ -46,6 +46,8 @@ from .bernoulli import (BHMMResult, BMMResult, bhmm, bhmm_aic, bhmm_bic, bhmm_pr
 from . import density  # noqa: F401
 from .density import (DBSCANResult, dbscan, dbscan_sweep, k_distances, latent_density, noise_runs,  # noqa: F401
                       radius_graph, suggest_eps)
+from .density import (HDBSCANResult, MSTResult, core_distances, hdbscan, hdbscan_cut, hdbscan_sweep,  # noqa: F401
+                      latent_hdbscan, mutual_reachability_mst)
 from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)

@@ -12,8 +12,23 @@ sklearn.cluster.DBSCAN's on every row, for Euclidean distance on the soft latent
   noise_runs            the maximal runs of -1
   latent_density        both fits on the script's data, scored against the states and the flags
 The graph is N x N bits (19 MB at N = 12298), so 2 <= N <= 65536; 1 <= L <= 128 (rbvae_dbscan_ok).  Not built: the upper
-triangle alone and its mirror image, an implicit graph for larger N, OPTICS and HDBSCAN, assigning new points to a fit, sample
-weights.  There is no host path: a matrix on the CPU raises.
+triangle alone and its mirror image, an implicit graph for larger N, OPTICS, assigning new points to a fit, sample weights.
+There is no host path: a matrix on the CPU raises.
+
+HDBSCAN* asks the same question at every radius at once (csrc/hdbscan.hip; Campello, Moulavi, Zimek and Sander 2015 in an
+order-free form): a hierarchy of density levels, clusters chosen by how long they persist, a membership
+strength for every frame (a frame on a transition gets a low one, not a hard -1), and any DBSCAN* cut from the one tree.
+  core_distances        the distance to the min_samples-th row, the row itself counted (rbvae_knn)
+  mutual_reachability_mst       the minimum spanning tree under the key (w2, lo, hi) by Boruvka rounds on the device
+                        (rbvae_mst_start / rbvae_mst_round, the stop decided on the device), sorted by the key
+  hdbscan               the tree, then the condensed tree, the selection, labels and probabilities on the host
+                        (rbvae_hdbscan_tree); hdbscan_sweep: one tree, one selection per min_cluster_size
+  hdbscan_cut           DBSCAN* at one radius from a fit or a tree (rbvae_hdbscan_cut)
+  latent_hdbscan        the fit of the script's soft latents, scored as latent_density scores its fits
+2 <= N <= 16384 (rbvae_knn's limit), 1 <= L <= 128, 1 <= min_samples <= min(N, 129), 2 <= min_cluster_size <= N.  Not built:
+Hamming distance on the hard codes (integer distances make every level one massive tie and duplicate codes give lambda = inf
+throughout; dbscan(..., metric="hamming") over bits = 0, 1, 2 ... already is that hierarchy), allow_single_cluster,
+cluster_selection_epsilon, max_cluster_size, GLOSH outlier scores, assigning new points, N > 16384.
 """
 from __future__ import annotations
 
@@ -34,6 +49,10 @@ MAX_ROWS = 65536                                    # rbvae_dbscan_ok
 MAX_KNN_ROWS = 16384                                # rbvae_knn's N, the limit of k_distances and suggest_eps
 METRICS = ("euclidean", "hamming")
 _LIMITS = "2 <= N <= 65536, 1 <= L <= 128"
+MAX_MST_ROWS = 16384                                # rbvae_mst_ok
+MAX_MIN_SAMPLES = 129                               # rbvae_knn's k = min_samples - 1 <= 128
+SELECTION_METHODS = ("eom", "leaf")
+_MST_LIMITS = "2 <= N <= 16384, 1 <= L <= 128"
 
 
 @dataclass
@@ -250,3 +269,196 @@ def latent_density(model, x: torch.Tensor, frame_indices: Sequence[int], flags: 
     hard = dbscan(codes, bits, min_samples, metric="hamming")
     return {"latents": z, "codes": codes, "labels": labels, "eps": eps, "code_bits": bits,
             "soft": _density_scores(soft, labels, S, tolerance), "hard": _density_scores(hard, labels, S, tolerance)}
+
+
+# ---- HDBSCAN* ------------------------------------------------------------------------------------------------------------------
+
+@dataclass
+class MSTResult:
+    edges: torch.Tensor                 # int32 [N - 1, 2] on the device, lo < hi, in ascending order of the key (w2, lo, hi)
+    d: torch.Tensor                     # f64 [N - 1]: sqrt(w2), the mutual reachability distance of every edge
+    w2: torch.Tensor                    # f64 [N - 1]: max(core2_i, core2_j, d2(i, j))
+    core_distances: torch.Tensor        # f64 [N]
+    n_rounds: int                       # the Boruvka rounds that ran
+    min_samples: int
+
+    def __iter__(self):                 # edges, d = mutual_reachability_mst(...)
+        return iter((self.edges, self.d))
+
+
+@dataclass
+class HDBSCANResult:
+    labels: torch.Tensor                # int32 [N] on the device, -1 for noise; clusters numbered by their smallest row
+    probabilities: torch.Tensor         # f64 [N] on the device: the membership strength, 0 for noise
+    n_clusters: int
+    n_noise: int
+    clusters: dict                      # the cluster table on the host, the root first: parent, birth, lambda_max, stability,
+                                        # size, selected, min_row (numpy arrays over the clusters of the condensed tree)
+    mst: MSTResult
+    core_distances: torch.Tensor        # f64 [N] on the device
+    min_cluster_size: int
+    min_samples: int
+    cluster_selection_method: str
+    n_rounds: int
+
+
+def _whole(value, name, lo, hi):
+    if isinstance(value, bool) or int(value) != value or not lo <= int(value) <= hi:
+        raise ValueError(f"{name} ({value!r}) must be a whole number in [{lo}, {hi}]")
+    return int(value)
+
+
+def _core2(X, N, m):
+    from .projection import knn_graph
+    if m == 1:
+        return torch.zeros(N, dtype=torch.float64, device=X.device)
+    return knn_graph(X, m - 1)[1][:, m - 2].contiguous()
+
+
+def core_distances(X: torch.Tensor, min_samples: int) -> torch.Tensor:
+    """f64 [N] on the device, in row order: every row's Euclidean distance to its min_samples-th nearest row, the row itself
+    counted as the first (scikit-learn's np.partition(row, m - 1)[m - 1]): sqrt of column m - 2 of rbvae_knn(X, m - 1), zeros
+    for min_samples = 1.  k_distances(X, k) is this vector sorted."""
+    X, N, _ = checked_matrix(X, "core_distances", "rbvae_mst_ok", _MST_LIMITS)
+    m = _whole(min_samples, "min_samples", 1, min(N, MAX_MIN_SAMPLES))
+    return torch.sqrt(_core2(X, N, m))
+
+
+def mutual_reachability_mst(X: torch.Tensor, min_samples: int) -> MSTResult:
+    """The minimum spanning tree of the mutual reachability graph w2(i, j) = max(core2_i, core2_j, d2(i, j)) under the strict
+    total order (w2, lo, hi) -- so the tree is unique, whatever ties w2 has -- by Boruvka rounds on the device.
+    -> MSTResult, which unpacks as (edges, d); sorted by the key on the device, bit-identical between runs, n_rounds included."""
+    X, N, Ld = checked_matrix(X, "mutual_reachability_mst", "rbvae_mst_ok", _MST_LIMITS)
+    m = _whole(min_samples, "min_samples", 1, min(N, MAX_MIN_SAMPLES))
+    dev = X.device
+    c2 = _core2(X, N, m)
+    comp = torch.empty(N, dtype=torch.int32, device=dev)
+    edges = torch.empty((N - 1, 2), dtype=torch.int32, device=dev)
+    w2 = torch.empty(N - 1, dtype=torch.float64, device=dev)
+    state = torch.empty(4, dtype=torch.int32, device=dev)
+    ws = torch.empty(L.query("rbvae_mst_ws_bytes", N) // 8, dtype=torch.int64, device=dev)
+    L.call("rbvae_mst_start", N, comp, state, ws)
+
+    def one_round(it):
+        L.call("rbvae_mst_round", X, c2, N, Ld, comp, edges, w2, state, ws)
+
+    n_rounds, _, _ = run_until_done(one_round, state, (N - 1).bit_length() + 2)
+    done, _, n_comp, n_edges = state.cpu().tolist()
+    if not done or n_comp != 1 or n_edges != N - 1:
+        raise RuntimeError(f"mutual_reachability_mst: {n_comp} components and {n_edges} edges after {n_rounds} rounds")
+    lohi = edges[:, 0].to(torch.int64) * (1 << 32) + edges[:, 1].to(torch.int64)
+    order = torch.argsort(lohi, stable=True)
+    order = order[torch.argsort(w2[order], stable=True)]
+    edges, w2 = edges[order].contiguous(), w2[order].contiguous()
+    return MSTResult(edges, torch.sqrt(w2), w2, torch.sqrt(c2), int(n_rounds), m)
+
+
+def _host_call(name, *args):
+    """an entry that takes host pointers and no stream"""
+    l = L.lib()
+    rc = getattr(l, name)(*[a.ctypes.data if isinstance(a, np.ndarray) else a for a in args])
+    if rc != 0:
+        msg = l.rbvae_last_error().decode()
+        if rc == L.E_INVALID:
+            raise ValueError(f"{name}: {msg}")
+        raise RuntimeError(f"{name} failed ({rc}): {msg}")
+
+
+_TABLE = (("parent", np.int32), ("birth", np.float64), ("lambda_max", np.float64), ("stability", np.float64),
+          ("size", np.int32), ("selected", np.int32), ("min_row", np.int32))
+
+
+def _host_tree(edges: np.ndarray, d: np.ndarray, N: int, mcs: int, method: str):
+    """rbvae_hdbscan_tree on host arrays -> (labels int32 [N], prob f64 [N], the cluster table)"""
+    edges = np.ascontiguousarray(edges, dtype=np.int32)
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    if edges.shape != (N - 1, 2) or d.shape != (N - 1,):
+        raise ValueError(f"the tree of {N} rows has edges [N - 1, 2] and d [N - 1], got {edges.shape} and {d.shape}")
+    labels, prob, n = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.float64), np.zeros(1, dtype=np.int32)
+    table = {k: np.empty(N, dtype=t) for k, t in _TABLE}
+    _host_call("rbvae_hdbscan_tree", edges, d, N, mcs, SELECTION_METHODS.index(method), labels, prob,
+               *[table[k] for k, _ in _TABLE], n)
+    return labels, prob, {k: v[:int(n[0])].copy() for k, v in table.items()}
+
+
+def _checked_mst(mst, N=None) -> MSTResult:
+    if not isinstance(mst, MSTResult):
+        raise ValueError("mst must be mutual_reachability_mst's result")
+    if N is not None and mst.core_distances.shape[0] != N:
+        raise ValueError(f"mst: built from {mst.core_distances.shape[0]} rows, X has {N}")
+    return mst
+
+
+def _select(mst: MSTResult, tree_host, mcs, method) -> HDBSCANResult:
+    N = mst.core_distances.shape[0]
+    mcs = _whole(mcs, "min_cluster_size", 2, N)
+    if method not in SELECTION_METHODS:
+        raise ValueError(f"cluster_selection_method must be one of {SELECTION_METHODS}, got {method!r}")
+    labels, prob, table = _host_tree(tree_host[0], tree_host[1], N, mcs, method)
+    dev = mst.edges.device
+    return HDBSCANResult(torch.from_numpy(labels).to(dev), torch.from_numpy(prob).to(dev), int(table["selected"].sum()),
+                         int((labels < 0).sum()), table, mst, mst.core_distances, mcs, mst.min_samples, method, mst.n_rounds)
+
+
+def hdbscan(X: torch.Tensor, min_cluster_size: int = 5, min_samples: Optional[int] = None,
+            cluster_selection_method: str = "eom", mst: Optional[MSTResult] = None) -> HDBSCANResult:
+    """HDBSCAN* of the rows of a device matrix, Euclidean distance; min_samples (default: min_cluster_size) counts the row
+    itself.  The answer is the order-free one of the module's docstring: it does not change under a permutation of the rows, and
+    equals sklearn.cluster.HDBSCAN's (1.7.2) wherever that one is well defined -- the tree's weights, every cut, and the fits
+    without ties among the mutual reachabilities (min_samples = 1 as a rule); with ties scikit-learn's answer depends on the
+    order of the rows and the number of clusters is what the two have in common.  mst: mutual_reachability_mst's result for the
+    same X and min_samples, to select again without building it; X may then be None."""
+    if cluster_selection_method not in SELECTION_METHODS:
+        raise ValueError(f"cluster_selection_method must be one of {SELECTION_METHODS}, got {cluster_selection_method!r}")
+    if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[0] >= 2:       # before the tree is built, not after
+        _whole(min_cluster_size, "min_cluster_size", 2, X.shape[0])
+    if mst is None:
+        m = min_cluster_size if min_samples is None else min_samples
+        mst = mutual_reachability_mst(X, m)
+    else:
+        mst = _checked_mst(mst, None if X is None else X.shape[0])
+        if min_samples is not None and int(min_samples) != mst.min_samples:
+            raise ValueError(f"mst was built with min_samples = {mst.min_samples}, not {min_samples}")
+    return _select(mst, (mst.edges.cpu().numpy(), mst.d.cpu().numpy()), min_cluster_size, cluster_selection_method)
+
+
+def hdbscan_sweep(X: torch.Tensor, min_cluster_sizes: Sequence[int], min_samples: int,
+                  cluster_selection_method: str = "eom") -> List[HDBSCANResult]:
+    """One tree, one selection per entry of min_cluster_sizes -> the results in the list's order, each equal to
+    hdbscan(X, mcs, min_samples).  min_samples must be given: the tree depends on it."""
+    if min_samples is None:
+        raise ValueError("hdbscan_sweep: min_samples must be given (the tree depends on it)")
+    mst = mutual_reachability_mst(X, min_samples)
+    host = (mst.edges.cpu().numpy(), mst.d.cpu().numpy())
+    return [_select(mst, host, mcs, cluster_selection_method) for mcs in min_cluster_sizes]
+
+
+def hdbscan_cut(fit_or_mst, cut_distance: float, min_cluster_size: int = 5) -> Tuple[torch.Tensor, int]:
+    """DBSCAN* at one radius from the tree of a fit (or from mutual_reachability_mst's result): the components of the edges
+    with d <= cut_distance; a component with fewer than min_cluster_size rows is -1, the others are numbered by their smallest
+    row (sklearn's HDBSCAN.dbscan_clustering as a partition) -> (labels int32 [N] on the device, n_clusters)."""
+    mst = _checked_mst(fit_or_mst.mst if isinstance(fit_or_mst, HDBSCANResult) else fit_or_mst)
+    N = mst.core_distances.shape[0]
+    mcs = _whole(min_cluster_size, "min_cluster_size", 2, N)
+    cut_distance = float(cut_distance)
+    if not cut_distance >= 0.0:
+        raise ValueError(f"cut_distance ({cut_distance}) must be non-negative")
+    labels, n = np.empty(N, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    _host_call("rbvae_hdbscan_cut", np.ascontiguousarray(mst.edges.cpu().numpy()), np.ascontiguousarray(mst.d.cpu().numpy()), N,
+               cut_distance, mcs, labels, n)
+    return torch.from_numpy(labels).to(mst.edges.device), int(n[0])
+
+
+@torch.no_grad()
+def latent_hdbscan(model, x: torch.Tensor, frame_indices: Sequence[int], flags: Sequence[int], min_cluster_size: int = 5,
+                   min_samples: Optional[int] = None, cluster_selection_method: str = "eom", tolerance: int = 2,
+                   projections: Optional[dict] = None, temperature: float = 0.2, noise_ratio: float = 0.3, u=None) -> dict:
+    """latent_density's counterpart without a radius: x [F, C, H, W] frames (or latents) on the device in time order, encoded
+    by _latents.encode_frames (projections["latents"] serves as the soft latents when present); soft latents only.
+    -> {"latents", "labels" (the states), "fit": HDBSCANResult, "agreement", "noise_fraction", "noise_near_change",
+        "noise_runs", "boundaries"} with the scores of latent_density's two fits."""
+    labels = frame_labels(frame_indices, flags, frame_count(x))
+    z, _ = encode_frames(model, x, hard=False, latents=projections.get("latents") if projections is not None else None,
+                         temperature=temperature, noise_ratio=noise_ratio, u=u)
+    fit = hdbscan(z, min_cluster_size, min_samples, cluster_selection_method)
+    return {"latents": z, "labels": labels, **_density_scores(fit, labels, len(flags) + 1, tolerance)}
