@@ -647,7 +647,9 @@ int rbvae_decoded_to_image(int dtype, const void* rows, int ld, float* img, unsi
  *                 reads, ybox_first .. ybox_last);
  *   vertical = 1: in [N][in_h][W][3] -> out [N][out_h][W][3] (in_w == out_w == W), output row yy reads source rows
  *                 bounds[yy][0] - row0 + t (Pillow's shift of the vertical bounds by ybox_first).
- * Taps outside the source are skipped.  RBVAE_E_UNSUPPORTED when a horizontal pass's two rows exceed 64 KB of LDS. */
+ * Taps outside the source are skipped (a row whose taps all are gives 0), and at most ksize taps are read per row.
+ * RBVAE_E_UNSUPPORTED when a horizontal pass's two rows exceed 64 KB of LDS: ((3 in_w + 7) & ~3) + ((3 out_w + 7) & ~3)
+ * > 65536, e.g. 10921 -> 10921 pixels runs and 10921 -> 10922 does not. */
 int rbvae_resample_u8(const unsigned char* in, unsigned char* out, int N, int in_h, int in_w, int out_h, int out_w,
                       int vertical, int row0, const int* bounds, const int* kk, int ksize, void* stream);
 /* ToTensor -> add_gaussian_noise (kind 1) / add_occlusion (kind 2) -> ToPILImage

@@ -125,9 +125,18 @@ __global__ __launch_bounds__(FR_THREADS) void resample_v_k(const unsigned char* 
     }
     unsigned char* dst = out + ((long)n * out_h + yy) * row_bytes + b;
     if constexpr (VEC == 4) {
+        // Each clipped byte goes through an empty asm before it is packed.  Left to itself the compiler turns
+        // clip8(a) | clip8(b) << 8 into v_ashr_pk_u8_i32, which writes 16 bits of its destination, and then ORs the other
+        // two bytes into that register as if its upper half were zero.  The register is the high word of a 64-bit
+        // multiply-add: small after any tap, never written when every tap of a row is skipped, and then whatever an
+        // earlier wave left there comes out as bytes 2 and 3 of the dword (tests/test_frames_abi_gpu.py, synthetic-W4).
         unsigned w = 0;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) w |= (unsigned)clip8(acc[v]) << (8 * v);
+        for (int v = 0; v < 4; ++v) {
+            unsigned c = clip8(acc[v]);
+            asm volatile("" : "+v"(c));
+            w |= c << (8 * v);
+        }
         *(unsigned*)dst = w;
     } else {
         dst[0] = clip8(acc[0]);

@@ -212,6 +212,39 @@ class GuardedFlat(Guarded):
         assert self.view.data_ptr() % 16 == 0
 
 
+class GuardedBytes:
+    """n bytes starting `offset` bytes past a 256-byte boundary (so .view's address & 3 == offset & 3), inside `guard`
+    bytes of `sentinel` on each side.  A legitimate output byte can equal the sentinel, so a byte-exact test runs twice
+    with two sentinels: both runs equal to the reference and both pairs of bands intact show that every byte of the
+    interior was written and none outside it.  The bands are compared on the device (the buffers of the large cases are
+    not copied to the host)."""
+
+    def __init__(self, n, sentinel=0xA5, offset=0, guard=4096, device="cuda"):
+        self.n, self.sentinel, self.lo = n, sentinel, guard + offset
+        self.buf = torch.full((self.lo + n + guard,), sentinel, dtype=torch.uint8, device=device)
+        self.view = self.buf[self.lo:self.lo + n]
+        assert self.buf.data_ptr() % 256 == 0 and self.view.data_ptr() % 4 == offset % 4
+
+    def fill(self, t):
+        self.view.copy_(t.reshape(-1))
+        return self
+
+
+def assert_byte_bands(g, what=""):
+    """Every byte of g.buf outside the interior still holds the sentinel."""
+    for name, band, base in (("before", g.buf[:g.lo], -g.lo), ("after", g.buf[g.lo + g.n:], g.n)):
+        bad = (band != g.sentinel).nonzero()
+        assert bad.shape[0] == 0, (f"{what}: {bad.shape[0]} bytes {name} the output were written; first at byte "
+                                   f"{int(bad[0, 0]) + base} relative to the interior")
+
+
+def assert_bytes_untouched(g, what=""):
+    """assert_byte_bands and an interior that is still sentinel: a refused call wrote nothing."""
+    assert_byte_bands(g, what)
+    bad = (g.view != g.sentinel).nonzero()
+    assert bad.shape[0] == 0, f"{what}: {bad.shape[0]} output bytes were written by a refused call; first at {int(bad[0, 0])}"
+
+
 def guarded(rows, ld, ncols, dtype, guard_rows=GUARD_ROWS, device="cuda", row_align=16):
     return Guarded(rows, ld, ncols, dtype, guard_rows, device, row_align)
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import sfv_amd as sfv
+from _frames_cases import _boundary_noise
 from _frames_ref import (CASES, add_gaussian_noise, add_occlusion, contrastive_host, frame_image, pil_resize, sd_host,
                          to_pil_array, to_tensor)
 
@@ -57,17 +58,6 @@ def test_reference_chain_and_copy():
         assert np.array_equal(fin[j], pil_resize(m, (1280, 704), "lanczos"))
     same = sfv.resize_u8(x, (1920, 1080), "bilinear")
     assert same.data_ptr() != x.data_ptr() and torch.equal(same, x)
-
-
-def _boundary_noise(a, std, rng):
-    """noise whose sum with x/255 lands within an ulp of a k/255 boundary: the truncation of mul(255).byte() decides"""
-    x = to_tensor(a)
-    k = torch.from_numpy(rng.integers(0, 256, x.shape)).float()
-    target = k / 255
-    n = (target - x) / std
-    ulps = torch.from_numpy(rng.integers(-2, 3, x.shape)).float()
-    n = n + ulps * torch.finfo(torch.float32).eps * n.abs().clamp_min(1e-3)
-    return n
 
 
 def test_perturb_matches_torch():

@@ -10,6 +10,8 @@ CPU restatement pinned to the reference's own Decoder by tests/golden/ldm_decode
                             change no byte
   rbvae_gather_gemm         the same cases through the four-class descriptor, the same bound
   rbvae_latent_rows / rbvae_decoded_to_image   byte for byte against torch float32 on the CPU
+  rbvae_nearest2x_rows      bit-equal to repeat_interleave on NHWC rows, both types, padded ldi / ldo (NaN / sentinel columns),
+                            a second trip of its grid-stride loop, refusals that write nothing (end of this file)
   LDMDecoder                float32, all three upsample forms: both fixture cases within atol = 8 e32, e32 = 3.04e-6 = max
                             |float32 restatement - float64 restatement| over the fixture outputs (test_ldm_decoder_cpu.py
                             measures it; another summation order and the folded weights each cost about one such floor, a
@@ -293,3 +295,78 @@ def test_checkpoint_keys_and_errors(fixture):
         m.decode(torch.zeros(1, 3, 8, 8, device="cuda"))
     with pytest.raises(ValueError):
         m.decode(torch.zeros(4, 8, 8, device="cuda"))
+
+
+# ---- rbvae_nearest2x_rows: the "unfolded" baseline's upsampled rows, on their own ------------------------------------------
+# Measured on one MI355X: all 36 padded cases and the 1 x 1024 x 1025 x 16 second-trip case bit-equal, padding columns and
+# bands untouched, no NaN read; 9 refused calls wrote nothing; each test under 0.2 s.
+
+def _nearest_want(x, N, IH, IW, C):
+    """out[(n, 2r+p, 2c+q)] = in[(n, r, c)] on NHWC rows"""
+    return x.reshape(N, IH, IW, C).repeat_interleave(2, 1).repeat_interleave(2, 2).reshape(N * 4 * IH * IW, C)
+
+
+@pytest.mark.parametrize("pad", [(0, 0), (1, 0), (0, 2)], ids=["ld=C", "ldi+16B", "ldo+32B"])
+@pytest.mark.parametrize("chunks", [1, 3])
+@pytest.mark.parametrize("N,IH,IW", [(1, 1, 1), (2, 3, 5), (1, 7, 4)])
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_nearest2x_rows_bit_equal_padded_and_guarded(lib, dtype, N, IH, IW, chunks, pad):
+    tdt = U.TDT[dtype]
+    per = 16 // torch.empty((), dtype=tdt).element_size()         # elements of one 16-byte chunk: 4 f32, 8 bf16
+    C, ldi, ldo = chunks * per, (chunks + pad[0]) * per, (chunks + pad[1]) * per
+    x = torch.randn(N * IH * IW, C, generator=torch.Generator().manual_seed(N + IH + IW + C)).to(tdt)
+    xin = B.poisoned(x, ldi, tdt)                                  # columns C..ldi and the bands are NaN
+    out = B.guarded(N * 4 * IH * IW, ldo, C, tdt)                  # columns C..ldo and the bands are sentinel
+    lib.call("rbvae_nearest2x_rows", U.DTYPE_ID[dtype], xin.view, out.view, N, IH, IW, C, ldi, ldo)
+    torch.cuda.synchronize()
+    what = f"nearest2x_rows {dtype} {N} x {IH} x {IW} C {C} ldi {ldi} ldo {ldo}"
+    B.assert_guards(out, what)
+    got = out.out.cpu()
+    assert not bool(torch.isnan(got.float()).any())
+    assert torch.equal(bits(got), bits(_nearest_want(x, N, IH, IW, C))), what
+    print(f"\n{what}: {got.numel()} elements bit-equal, padding columns and bands untouched")
+
+
+def test_nearest2x_rows_second_trip_of_the_grid_stride_loop(lib):
+    """1 x 1024 x 1025 x 16 f32: 16 793 600 chunks against 65536 workgroups x 256 threads = 16 777 216; 67 MB in, 268 MB out,
+    compared on the device."""
+    N, IH, IW, C = 1, 1024, 1025, 16
+    assert N * 4 * IH * IW * (C // 4) > 65536 * 256
+    x = torch.randn(N * IH * IW, C, device="cuda", generator=torch.Generator("cuda").manual_seed(13))
+    xin = B.poisoned(x, C, torch.float32)
+    out = B.guarded(N * 4 * IH * IW, C, C, torch.float32)
+    lib.call("rbvae_nearest2x_rows", U.DTYPE_ID["f32"], xin.view, out.view, N, IH, IW, C, C, C)
+    torch.cuda.synchronize()
+    pat = B.SENTINEL[torch.float32][1]
+    raw = out.buf.view(torch.int32)
+    assert bool((raw[:out.g] == pat).all()) and bool((raw[out.g + out.rows:] == pat).all()), "a write outside the output"
+    bad = (out.view.view(torch.int32) != _nearest_want(x, N, IH, IW, C).view(torch.int32)).nonzero()
+    assert bad.shape[0] == 0, f"{bad.shape[0]} elements differ; first at (row {int(bad[0, 0])}, column {int(bad[0, 1])})"
+    print(f"\nnearest2x_rows f32 {N} x {IH} x {IW} C {C}: {out.view.numel()} elements bit-equal on the device, bands untouched")
+
+
+def test_nearest2x_rows_refusals_write_nothing(lib):
+    N, IH, IW = 2, 3, 5
+    x = B.poisoned(torch.randn(N * IH * IW, 8), 8, torch.float32)
+    out = B.guarded(N * 4 * IH * IW, 8, 8, torch.float32)
+    before = out.buf.clone()
+    f32 = U.DTYPE_ID["f32"]
+    assert 7 not in U.DTYPE_ID.values()
+    lib.call("rbvae_nearest2x_rows", f32, x.view, B.guarded(N * 4 * IH * IW, 8, 8, torch.float32).view, N, IH, IW, 8, 8, 8)   # the base is accepted
+    refused = {                                                    # dtype in out N IH IW C ldi ldo
+        "C not a multiple of the chunk": (f32, x.view, out.view, N, IH, IW, 6, 8, 8),
+        "ldi < C": (f32, x.view, out.view, N, IH, IW, 8, 4, 8),
+        "ldo not a multiple of 16 bytes": (f32, x.view, out.view, N, IH, IW, 4, 8, 6),
+        "in offset by 4 bytes": (f32, x.view.view(-1)[1:], out.view, N, IH, IW, 4, 8, 8),
+        "out offset by 4 bytes": (f32, x.view, out.view.view(-1)[1:], N, IH, IW, 4, 8, 8),
+        "dtype 7": (7, x.view, out.view, N, IH, IW, 8, 8, 8),
+        "2^30 pixel rows": (f32, x.view, out.view, 1, 16384, 16384, 8, 8, 8),
+        "in null": (f32, None, out.view, N, IH, IW, 8, 8, 8),
+        "out null": (f32, x.view, None, N, IH, IW, 8, 8, 8),
+    }
+    for what, args in refused.items():
+        with pytest.raises(ValueError):
+            lib.call("rbvae_nearest2x_rows", *args)
+        torch.cuda.synchronize()
+        assert torch.equal(bits(out.buf), bits(before)), what
+    print(f"\nnearest2x_rows: {len(refused)} refused calls raised ValueError and wrote nothing")
