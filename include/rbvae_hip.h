@@ -1199,6 +1199,49 @@ int rbvae_hdbscan_tree(const int* edges, const double* d, int N, int min_cluster
 int rbvae_hdbscan_cut(const int* edges, const double* d, int N, double cut_distance, int min_cluster_size, int* labels,
                       int* n_clusters);
 
+/* ---- Two sequences aligned: dynamic time warping (csrc/dtw.hip) -------------------------------------------------
+ * Sakoe and Chiba 1978 with the symmetric step pattern of unit weights, as dtw-python's "symmetric1" and tslearn's dtw_path
+ * state it; tests/_dtw_ref.py restates every operation.  X has N rows and Y has M rows, both in time order; 1 <= N, M <= 16384,
+ * 1 <= L <= 128, metric in 0 .. 2, window = -1 or |N - M| <= window (and then subsequence = 0), subsequence in {0, 1}
+ * (rbvae_dtw_ok); anything else makes every entry return RBVAE_E_UNSUPPORTED without a launch, a NULL pointer (table
+ * excepted) RBVAE_E_INVALID.  X and Y must be finite: the entries do not look (alignment.py does).
+ *
+ * Cell cost d(i, j).  metric 0 (sqeuclidean), X f32 [N][L] and Y f32 [M][L]: sum_l (x_il - y_jl)^2 in f64 with l ascending,
+ * each difference exact, each square and each addition rounded once, never contracted (rbvae_knn's d2).  metric 1
+ * (euclidean): the correctly rounded f64 square root of that sum.  metric 2 (hamming, rbvae_dtw_fill_bits), uint32 [.][4] as
+ * rbvae_bern_pack writes them: the popcount of the XOR of the two rows, an exact f64; L is only checked.
+ * Table.  D[0][0] = d(0, 0); D[i][j] = d(i, j) + min(D[i-1][j-1], D[i-1][j], D[i][j-1]), a predecessor outside the table
+ * being absent: one f64 addition per cell.  The predecessor is the first of diagonal, up (i - 1, j), left (i, j - 1) whose
+ * value is <= the other two.  dirs uint8 [N][ceil(M / 4)] holds it in 2 bits per cell, cell j in bits 2 (j mod 4) of byte
+ * j / 4 of row i: 0 diagonal, 1 up, 2 left, 3 start / none; the bits of the columns from M on in a row's last byte are 3.
+ * Band.  window = w >= 0: a cell with |i - j| > w holds +inf and direction 3 and is no predecessor; window = -1: no band.
+ * Subsequence (open begin and end on Y).  D[0][j] = d(0, j) with direction 3 for every j; the other rows as above; the end is
+ * the j with the smallest D[N-1][j], the lowest j on a tie; the path runs from there back to row 0.
+ *
+ * rbvae_dtw_tile_rows / _cols: the edges of the tile a workgroup owns (tests place shapes on them).
+ * rbvae_dtw_ws_bytes(N, M): the size of ws, 8-byte aligned (0 outside the limits): a frontier row f64 [M], a frontier column
+ * f64 [N] and one corner per tile.  rbvae_dtw_dirs_bytes(N, M) = N ceil(M / 4).
+ * rbvae_dtw_fill / rbvae_dtw_fill_bits: one launch per anti-diagonal of tiles on the caller's stream -- the launch order is
+ * the only dependency between workgroups, none waits for another -- behind one fill launch where there is a band, whose
+ * tiles wholly outside it are not launched.  They write dirs and last_row f64 [M] = D[N-1][.], and, where table is not NULL,
+ * the whole D f64 [N][M] (tests and small inputs; the product path passes NULL and never stores N M doubles).
+ * rbvae_dtw_trace: one workgroup walks dirs from the end cell (N - 1, M - 1), or (N - 1, end_j) in subsequence mode, to the
+ * cell with direction 3.  path int32 [N + M - 1][2] (8-byte aligned): the pairs (i, j) ascending in rows 0 .. len - 1; the
+ * rows from len on are scratch and hold no meaning afterwards.  state int32 [3] = {len, start_j, end_j}; cost f64 [1] =
+ * last_row[end_j].  dirs that do not lead to row 0 (and column 0 without subsequence) inside N + M - 1 cells give len =
+ * start_j = -1 and no path. */
+int rbvae_dtw_ok(int N, int M, int L, int metric, int window, int subsequence);
+int rbvae_dtw_tile_rows(void);
+int rbvae_dtw_tile_cols(void);
+size_t rbvae_dtw_ws_bytes(int N, int M);
+size_t rbvae_dtw_dirs_bytes(int N, int M);
+int rbvae_dtw_fill(const float* X, int N, const float* Y, int M, int L, int metric, int window, int subsequence,
+                   unsigned char* dirs, double* last_row, double* table, void* ws, void* stream);
+int rbvae_dtw_fill_bits(const uint32_t* xbits, int N, const uint32_t* ybits, int M, int L, int window, int subsequence,
+                        unsigned char* dirs, double* last_row, double* table, void* ws, void* stream);
+int rbvae_dtw_trace(const unsigned char* dirs, const double* last_row, int N, int M, int subsequence, int* path, int* state,
+                    double* cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
