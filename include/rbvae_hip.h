@@ -19,7 +19,11 @@
  *    reductions are always f32;
  *  - activations are NHWC ("pixel rows of C channels"), weights are the packed
  *    layouts written by the rbvae_run_jobs pack jobs (kinds 0 and 3, see that entry
- *    point) from the reference-layout f32 parameters.
+ *    point) from the reference-layout f32 parameters;
+ *  - the keyed dropout of an epilogue (drop_mode 1 of rbvae_gather_gemm, rbvae_conv3x3s2_halo,
+ *    rbvae_deconv3x3s2_halo and rbvae_conv_first_fused) takes 0 <= drop_p < 1: anything else, NaN included, is
+ *    RBVAE_E_INVALID and nothing is launched (the threshold is floor(drop_p * 2^32), a conversion that is undefined from
+ *    1.0 up and wraps below 0).  drop_p is not read in drop_mode 0 and 2.
  * The hardware-map probes and phase-stamp hooks of debug builds are NOT part of this
  * ABI: include/rbvae_dbg.h, librbvae_dbg.so.
  */
@@ -144,7 +148,7 @@ int rbvae_mse_bwd(const float* a, const float* b, long n, float scale, const flo
  *   m -> (n, a, b) over Nimg x TH x TW;  A pixel (a*sa+dh_j, b*sa+dw_j) of an IH x IW grid (zero
  *   outside);  Out pixel (a*so+oh0, b*so+ow0) of an OH x OW grid;  grid.z = parity class.
  *   class_desc is a HOST int array: per class [ntaps, oh0, ow0, ntaps x (widx, dh, dw)].
- *   epilogue: +bias, relu, *scale, dropout (drop_mode 1: counter hash of (seed, element index),
+ *   epilogue: +bias, relu, *scale, dropout (drop_mode 1: counter hash of (seed, element index), 0 <= drop_p < 1;
  *   2: explicit u8 keep-mask [rows][Nout]), + addend (residual, same indexing as Out; LDM ResnetBlock /
  *   AttnBlock skip connections, ldm/modules/diffusionmodules/model.py:141,202), then zero where gate <= 0 (saved activation:
  *   ReLU/dropout backward).  zero_page: >= 128 zero bytes.  Kc % (128/sizeof T) == 0, Nout % 8 == 0.

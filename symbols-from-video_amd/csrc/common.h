@@ -162,7 +162,7 @@ __device__ __forceinline__ unsigned drop_bits(unsigned run, int e) {
 // (drop_bits above: two quarter-rate multiplies) and the state then walks a xorshift32 sequence, 16 bits per
 // element.  A full hash per element cost ~64 cycles per wave-instruction-element, ~8 us of the 23 us conv1
 // forward at 16.7 M activations; this is ~4x cheaper.  Element e of the chunk is dropped iff its 16 bits are
-// below thresh16 = round(p * 65536) (p = 0.2 -> 0.199997).
+// below thresh16 = floor(p * 2^32) >> 16 (p = 0.2 -> 13107 / 65536 = 0.199997; the host wrappers refuse p outside [0, 1)).
 template <int EC>
 __device__ __forceinline__ unsigned drop_chunk_mask(unsigned run, unsigned thresh16) {
     unsigned s = drop_bits(run, 0);

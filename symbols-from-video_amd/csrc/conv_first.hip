@@ -734,6 +734,7 @@ extern "C" int rbvae_conv_first_fused(int dtype, const float* x, int fd1, int fd
                     "(bf16, Cin <= 4, Nout <= 256): Cin=%d %dx%d Nout=%d", Cin, IH, IW, Nout);
     RBVAE_CHECK_ARG(ldo >= Nout && ldo % 8 == 0, "conv_first_fused: ldo=%d", ldo);
     RBVAE_CHECK_ARG(drop_mode == 0 || drop_mode == 1, "conv_first_fused: drop_mode %d (explicit masks: two-kernel path)", drop_mode);
+    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "conv_first_fused: drop_p=%g outside [0, 1)", (double)drop_p);
     RBVAE_CHECK_ARG(((uintptr_t)W | (uintptr_t)zero_page | (uintptr_t)col | (uintptr_t)out) % 16 == 0 &&
                     (!bias || (uintptr_t)bias % 16 == 0), "conv_first_fused: pointers must be 16-byte aligned");
     CfArgs a;

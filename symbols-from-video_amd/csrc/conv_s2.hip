@@ -434,6 +434,7 @@ int rbvae_conv3x3s2_halo(int dtype, const void* A, const void* W, void* Out, con
     RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)gate | (uintptr_t)bias) % 16 == 0,
                     "conv3x3s2_halo: pointers must be 16-byte aligned");
     RBVAE_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 2 || mask), "conv3x3s2_halo: drop_mode/mask");
+    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "conv3x3s2_halo: drop_p=%g outside [0, 1)", (double)drop_p);
     CsArgs a;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
     a.gate = (const unsigned char*)gate; a.mask = (const unsigned char*)mask; a.colsum_ws = colsum_ws; a.seed_dev = seed_dev;

@@ -657,6 +657,7 @@ extern "C" int rbvae_gather_gemm(int dtype, const void* A, const void* W, void* 
     RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)gate) % 16 == 0,
                     "gather_gemm: pointers must be 16-byte aligned");
     RBVAE_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 2 || mask), "gather_gemm: drop_mode/mask");
+    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "gather_gemm: drop_p=%g outside [0, 1)", (double)drop_p);
     GgArgs a;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
     a.gate = (const unsigned char*)gate; a.mask = (const unsigned char*)mask; a.addend = (const unsigned char*)addend;

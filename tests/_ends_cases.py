@@ -70,29 +70,33 @@ def s2_out(IH, IW):
 GOLD = 0x9E3779B97F4A7C15
 
 
-def keyed_keep_mask(M, Nout, seed, p, seed_dev=None, row_stride=None):
+def keyed_keep_mask(M, Nout, seed, p, seed_dev=None, row_stride=None, ec=8, rows=None):
     """Keep-mask [M][Nout] (bool, numpy) of drop_mode 1: the chunk starting at element index row * Nout + chunk is hashed
     once with the key of seed (+ seed_dev * GOLD), then a xorshift32 walk hands out 16 bits per element; an element is
     dropped iff its 16 bits < floor(p * 2^32) >> 16 (p as the f32 the ABI carries).  row_stride: the index's row pitch
-    (the kernels use Nout, never the leading dimension)."""
-    assert Nout % 8 == 0
+    (the kernels use Nout, never the leading dimension).  ec: elements per 16-byte store chunk, 8 (bf16) or 4 (f32: the
+    chunks start at every fourth column and the walk hands out two pairs with one xorshift32 step between them).
+    rows: the M output rows (an int array; default 0 .. M - 1) -- mask row i is that of output row rows[i], so the
+    scattered rows of a parity class come from the same function."""
+    assert ec in (4, 8) and Nout % ec == 0
     u64, u32 = np.uint64, np.uint32
     if seed_dev is not None:
         seed = (seed + seed_dev * GOLD) & 0xFFFFFFFFFFFFFFFF
     stride = Nout if row_stride is None else row_stride
+    rows = np.arange(M, dtype=np.uint64) if rows is None else np.asarray(rows).reshape(-1).astype(np.uint64)
+    assert rows.shape == (M,)
     with np.errstate(over="ignore"):
         x = u64(seed) * u64(GOLD) + u64(0xD6E8FEB86659FD93)
         x ^= x >> u64(32); x *= u64(0xD6E8FEB86659FD93); x ^= x >> u64(32)
         k0, k1 = u32(x & u64(0xFFFFFFFF)), u32(x >> u64(32))
         thresh16 = u32(int(float(np.float32(p)) * 4294967296.0) >> 16)
-        rows, chunks = np.arange(M, dtype=np.uint64)[:, None], np.arange(0, Nout, 8, dtype=np.uint64)[None, :]
-        idx = rows * u64(stride) + chunks                              # first element of every 8-element chunk
+        idx = rows[:, None] * u64(stride) + np.arange(0, Nout, ec, dtype=np.uint64)[None, :]   # first element of every chunk
         s = (idx & u64(0xFFFFFFFF)).astype(u32) + k0 + (idx >> u64(32)).astype(u32) * k1
         s ^= s >> u32(16); s *= u32(0x7feb352d); s ^= s >> u32(15); s *= u32(0x846ca68b); s ^= s >> u32(16)
         keep = np.empty((M, Nout), dtype=bool)
-        for e in range(0, 8, 2):
-            keep[:, e::8] = (s & u32(0xffff)) >= thresh16
-            keep[:, e + 1::8] = (s >> u32(16)) >= thresh16
+        for e in range(0, ec, 2):
+            keep[:, e::ec] = (s & u32(0xffff)) >= thresh16
+            keep[:, e + 1::ec] = (s >> u32(16)) >= thresh16
             s ^= s << u32(13); s ^= s >> u32(17); s ^= s << u32(5)
     return keep
 
