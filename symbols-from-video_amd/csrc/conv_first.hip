@@ -13,7 +13,7 @@
 //
 // They replace rbvae_im2col(_frames) + the single-slice rbvae_gather_gemm (same arithmetic per element: one 64-deep MFMA
 // chain; same dropout key and chunk indices; stored values are bit-identical).
-#include "mma.h"
+#include "epilogue.h"
 #include <stdlib.h>
 
 #ifndef CF_DBG      // timing experiments only: 1 no output stores, 2 no col stores, 3 stop after the staging, 4 no patch loads, 5 no gate reads
@@ -120,7 +120,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
         }
 #pragma unroll
         for (int k8 = 0; k8 < 8; ++k8) koff[k8] = otab.v[(tid & 7) * 8 + k8];
-        if (p.drop_mode == 1) dkey = drop_key(p.seed + (p.seed_dev ? p.seed_dev[0] * 0x9E3779B97F4A7C15ull : 0ull));
+        if (p.drop_mode == 1) dkey = epi_drop_key(p.seed, p.seed_dev);
 #pragma unroll
         for (int it = 0; it < PIT; ++it) {
             const int row = 2 * (w + 8 * it) + (lane >> 5);
@@ -734,7 +734,8 @@ extern "C" int rbvae_conv_first_fused(int dtype, const float* x, int fd1, int fd
                     "(bf16, Cin <= 4, Nout <= 256): Cin=%d %dx%d Nout=%d", Cin, IH, IW, Nout);
     RBVAE_CHECK_ARG(ldo >= Nout && ldo % 8 == 0, "conv_first_fused: ldo=%d", ldo);
     RBVAE_CHECK_ARG(drop_mode == 0 || drop_mode == 1, "conv_first_fused: drop_mode %d (explicit masks: two-kernel path)", drop_mode);
-    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "conv_first_fused: drop_p=%g outside [0, 1)", (double)drop_p);
+    unsigned drop_thresh;
+    if (const int e = epi_drop_args("conv_first_fused", drop_mode, nullptr, drop_p, &drop_thresh)) return e;
     RBVAE_CHECK_ARG(((uintptr_t)W | (uintptr_t)zero_page | (uintptr_t)col | (uintptr_t)out) % 16 == 0 &&
                     (!bias || (uintptr_t)bias % 16 == 0), "conv_first_fused: pointers must be 16-byte aligned");
     CfArgs a;
@@ -743,7 +744,7 @@ extern "C" int rbvae_conv_first_fused(int dtype, const float* x, int fd1, int fd
     a.gate = nullptr; a.colsum_ws = nullptr;
     a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = (IH + 2 - 3) / 2 + 1; a.OW = (IW + 2 - 3) / 2 + 1;
     a.Nout = Nout; a.ldo = ldo; a.relu = relu; a.drop_mode = drop_mode; a.scale = scale;
-    a.drop_thresh = (unsigned)((double)drop_p * 4294967296.0); a.seed = seed; a.seed_dev = seed_dev;
+    a.drop_thresh = drop_thresh; a.seed = seed; a.seed_dev = seed_dev;
     cf_launch<0>(a, (hipStream_t)stream);
     RBVAE_CHECK_LAUNCH("conv_first_fused");
     return RBVAE_OK;

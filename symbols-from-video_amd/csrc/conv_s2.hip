@@ -26,7 +26,7 @@
 // unit are split around the next unit's barrier and fragment reads (gather_gemm.hip's software pipeline).
 // Epilogue = rbvae_gather_gemm's, element for element: +bias, ReLU, *scale, keyed / explicit dropout (same element indices),
 // ReLU gate, 16-byte NHWC stores through an LDS tile, per-tile column sums (bias gradients).
-#include "mma.h"
+#include "epilogue.h"
 #include <type_traits>
 
 #ifndef CS_ABL          // timing ablations (results wrong on purpose; -DRBVAE_ABLATION builds only): 1 no LDS-DMA, 2 no fragment reads / MFMAs
@@ -319,22 +319,15 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
             const int row = (wr * MT + mt) * 16 + fi;
             float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x = acc[mt][nt][r] + bz[r];
-                if (p.relu) x = fmaxf(x, 0.f);
-                v[r] = x * p.scale;
-            }
-            uint2 pk;
-            pk.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-            pk.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-            *(uint2*)(tl + row * PITCH + cb * 2) = pk;
+            for (int r = 0; r < 4; ++r) v[r] = epi_act(acc[mt][nt][r], bz[r], p.relu, p.scale);
+            epi_stage<bf16_t>(tl + row * PITCH + cb * 2, v[0], v[1], v[2], v[3]);
         }
     }
     lds_barrier();
     const int sch = tid % CPR, rl = tid / CPR;
     const int scol = n0 + sch * 8;
     DropKey dkey{0u, 0u};
-    if (p.drop_mode == 1) dkey = drop_key(p.seed + (p.seed_dev ? p.seed_dev[0] * 0x9E3779B97F4A7C15ull : 0ull));
+    if (p.drop_mode == 1) dkey = epi_drop_key(p.seed, p.seed_dev);
     int orow_[ITERS];
     u32x4_t gv[ITERS];
 #pragma unroll
@@ -350,26 +343,11 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
         const int row = it * RL + rl, orow = orow_[it];
         if (orow >= 0) {
             u32x4_t val = *(const u32x4_t*)(tl + row * PITCH + sch * 16);
-            bf16_t* ev = (bf16_t*)&val;
-            if (p.drop_mode == 1) {
-                const unsigned run = drop_run(dkey, (unsigned long long)orow * p.Nout + scol);
-                drop_chunk_zero_b16<8>(run, p.drop_thresh >> 16, (unsigned*)&val);
-            } else if (p.drop_mode == 2) {
-                const unsigned char* mk = p.mask + (size_t)orow * p.Nout + scol;
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (!mk[e]) ev[e] = 0;
-            }
-            if (p.gate) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (!elem_pos<bf16_t>((const unsigned char*)&gv[it], e)) ev[e] = 0;
-            }
+            if (p.drop_mode == 1) val = epi_keyed<bf16_t>(val, dkey, p.drop_thresh >> 16, (unsigned long long)orow * p.Nout + scol);
+            else if (p.drop_mode == 2) val = epi_masked<bf16_t>(val, p.mask + (size_t)orow * p.Nout + scol);
+            if (p.gate) val = epi_gate<bf16_t>(val, gv[it]);
             *(u32x4_t*)(p.Out + ((size_t)orow * p.ldo + scol) * 2) = val;
-            if (p.colsum_ws) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) csum[e] += bf16_to_f32(ev[e]);
-            }
+            if (p.colsum_ws) epi_csum<bf16_t>(val, csum);
         }
     }
     if (p.colsum_ws) {
@@ -433,14 +411,13 @@ int rbvae_conv3x3s2_halo(int dtype, const void* A, const void* W, void* Out, con
     RBVAE_CHECK_ARG((long)Nimg * IH * IW * lda * 2 < (1l << 31), "conv3x3s2_halo: input of 2 GiB or more (32-bit buffer offsets)");
     RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)gate | (uintptr_t)bias) % 16 == 0,
                     "conv3x3s2_halo: pointers must be 16-byte aligned");
-    RBVAE_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 2 || mask), "conv3x3s2_halo: drop_mode/mask");
-    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "conv3x3s2_halo: drop_p=%g outside [0, 1)", (double)drop_p);
     CsArgs a;
+    if (const int e = epi_drop_args("conv3x3s2_halo", drop_mode, mask, drop_p, &a.drop_thresh)) return e;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
     a.gate = (const unsigned char*)gate; a.mask = (const unsigned char*)mask; a.colsum_ws = colsum_ws; a.seed_dev = seed_dev;
     a.seed = seed;
     a.Nimg = Nimg; a.IH = IH; a.IW = IW; a.OH = IH / 2; a.OW = IW / 2; a.Kc = Kc; a.Nout = Nout; a.lda = lda; a.ldo = ldo;
-    a.relu = relu; a.drop_mode = drop_mode; a.scale = scale; a.drop_thresh = (unsigned)((double)drop_p * 4294967296.0);
+    a.relu = relu; a.drop_mode = drop_mode; a.scale = scale;
     a.tiles_r = cdiv(a.OH, CS_TR); a.tiles_c = cdiv(a.OW, CS_TC); a.ntn = Nout / bn;
     const long total = (long)Nimg * a.tiles_r * a.tiles_c * a.ntn;
     RBVAE_CHECK_ARG(total < (1l << 30), "conv3x3s2_halo: too many tiles");

@@ -22,7 +22,7 @@
 // wave behind one barrier.  8 waves as 4 (pixel rows) x 2 (channel halves).  Epilogue class by class through one LDS tile:
 // bias, ReLU, scale, keyed / explicit dropout, ReLU gate of the layer below, per-tile column sums (bias gradients) --
 // element for element the arithmetic of rbvae_gather_gemm's epilogue (same dropout element indices).
-#include "mma.h"
+#include "epilogue.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     const int sch = tid % CPR, rl = tid / CPR;
     const int scol = n0 + sch * EC;
     DropKey dkey{0u, 0u};
-    if (p.drop_mode == 1) dkey = drop_key(p.seed + (p.seed_dev ? p.seed_dev[0] * 0x9E3779B97F4A7C15ull : 0ull));
+    if (p.drop_mode == 1) dkey = epi_drop_key(p.seed, p.seed_dev);
     int obase[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) obase[it] = s_obase[it * RL + rl];
@@ -425,20 +425,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
                     const int row = (wr * MT + mt) * 16 + fi;
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float x = acc[cls][mt][nt][r] + bz[r];
-                        if (p.relu) x = fmaxf(x, 0.f);
-                        v[r] = x * p.scale;
-                    }
-                    unsigned char* dst = tl + row * PITCH + cb * ES;
-                    if constexpr (ES == 4) {
-                        *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-                    } else {
-                        uint2 pk;
-                        pk.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-                        pk.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-                        *(uint2*)dst = pk;
-                    }
+                    for (int r = 0; r < 4; ++r) v[r] = epi_act(acc[cls][mt][nt][r], bz[r], p.relu, p.scale);
+                    epi_stage<T>(tl + row * PITCH + cb * ES, v[0], v[1], v[2], v[3]);
                 }
             }
         });
@@ -470,22 +458,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
                     u32x4_t val = *(const u32x4_t*)(tile + c * DH_BM * PITCH + row * PITCH + sch * 16);
                     T* ev = (T*)&val;
                     if (p.drop_mode == 1) {
+                        // inline: epi_keyed changes all six f32 instances (<float, 16|8|4, 4|8>)
                         const unsigned run = drop_run(dkey, (unsigned long long)orow * p.Nout + scol);
                         if constexpr (sizeof(T) == 2) drop_chunk_zero_b16<EC>(run, p.drop_thresh >> 16, (unsigned*)&val);
                         else drop_chunk_zero_f32<EC>(run, p.drop_thresh >> 16, (float*)&val);
                     } else if (p.drop_mode == 2) {
-                        const unsigned char* mk = p.mask + (size_t)orow * p.Nout + scol;
-#pragma unroll
-                        for (int e = 0; e < EC; ++e)
-                            if (!mk[e]) ev[e] = 0;
+                        val = epi_masked<T>(val, p.mask + (size_t)orow * p.Nout + scol);
                     }
-                    if (p.gate) {
-#pragma unroll
-                        for (int e = 0; e < EC; ++e)
-                            if (!elem_pos<T>((const unsigned char*)&gv[c][it], e)) ev[e] = 0;
-                    }
+                    if (p.gate) val = epi_gate<T>(val, gv[c][it]);
                     *(u32x4_t*)(p.Out + ((size_t)orow * p.ldo + scol) * ES) = val;
-                    if (p.colsum_ws) {
+                    if (p.colsum_ws) {         // inline: epi_csum changes <float, 16, 8> and <float, 8, 8>
 #pragma unroll
                         for (int e = 0; e < EC; ++e) csum[c][e] += Elem<T>::load(ev + e);
                     }
@@ -579,14 +561,13 @@ extern "C" int rbvae_deconv3x3s2_halo(int dtype, const void* A, const void* W, v
     RBVAE_CHECK_ARG((long)Nimg * TH * TW * 4 < (1l << 30), "deconv3x3s2_halo: more than 2^30 output pixel rows");
     RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)gate | (uintptr_t)bias) % 16 == 0,
                     "deconv3x3s2_halo: pointers must be 16-byte aligned");
-    RBVAE_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 2 || mask), "deconv3x3s2_halo: drop_mode/mask");
-    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "deconv3x3s2_halo: drop_p=%g outside [0, 1)", (double)drop_p);
     DhArgs a;
+    if (const int e = epi_drop_args("deconv3x3s2_halo", drop_mode, mask, drop_p, &a.drop_thresh)) return e;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
     a.gate = (const unsigned char*)gate; a.mask = (const unsigned char*)mask; a.zero = (const unsigned char*)zero_page;
     a.colsum_ws = colsum_ws; a.seed_dev = seed_dev; a.seed = seed;
     a.Nimg = Nimg; a.TH = TH; a.TW = TW; a.OH = 2 * TH; a.OW = 2 * TW; a.Kc = Kc; a.Nout = Nout; a.lda = lda; a.ldo = ldo;
-    a.relu = relu; a.drop_mode = drop_mode; a.scale = scale; a.drop_thresh = (unsigned)((double)drop_p * 4294967296.0);
+    a.relu = relu; a.drop_mode = drop_mode; a.scale = scale;
     const int sc = dh_strip_cols(TW);
     a.strips_per_img = TW / sc;
     a.grows = Nimg * a.strips_per_img * TH;

@@ -21,7 +21,7 @@
 // The accumulator is produced transposed (weights as the MFMA row operand) so a
 // lane owns 4 consecutive output channels of one pixel; the tile goes through
 // LDS once more and leaves as whole 16-B chunks of NHWC rows.
-#include "mma.h"
+#include "epilogue.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -445,20 +445,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
             const int row = (wr * MT + mt) * 16 + fi;
             float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x = acc[mt][nt][r] + bz[r];
-                if (p.relu) x = fmaxf(x, 0.f);
-                v[r] = x * p.scale;
-            }
-            unsigned char* dst = tile + row * PITCH + cb * ES;
-            if constexpr (ES == 4) {
-                *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-                uint2 pk;
-                pk.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-                pk.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-                *(uint2*)dst = pk;
-            }
+            for (int r = 0; r < 4; ++r) v[r] = epi_act(acc[mt][nt][r], bz[r], p.relu, p.scale);
+            epi_stage<T>(tile + row * PITCH + cb * ES, v[0], v[1], v[2], v[3]);
         }
     }
     if constexpr (PREFETCH && PF_LATE) {
@@ -475,12 +463,15 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     __syncthreads();
     GG_STAMP(4);
 
-    // ---- store phase: whole 16-B chunks of NHWC rows; dropout / gate zeroing happens here
+    // ---- store phase: whole 16-B chunks of NHWC rows; dropout / gate zeroing happens here.  The steps are epilogue.h's, in
+    // its order and with its index convention, but typed out: each helper changes the listing of some instance here --
+    // epi_keyed <unsigned short, 2, 4, 1, 1, 128>; epi_masked and epi_gate <float, 2, 4, 1, 4, 128> and <float, 4, 8, 2|3|4, 1, 128>;
+    // epi_csum all twelve f32 instances; the residual (this kernel only) has no helper: a value form changed all 24.
     float csum[EC];
 #pragma unroll
     for (int e = 0; e < EC; ++e) csum[e] = 0.f;
     DropKey dkey{0u, 0u};
-    if (p.drop_mode == 1) dkey = drop_key(p.seed + (p.seed_dev ? p.seed_dev[0] * 0x9E3779B97F4A7C15ull : 0ull));
+    if (p.drop_mode == 1) dkey = epi_drop_key(p.seed, p.seed_dev);
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int row = it * RL + rl;
@@ -656,16 +647,14 @@ extern "C" int rbvae_gather_gemm(int dtype, const void* A, const void* W, void* 
                         (long)Nimg * IH * IW < (1l << 30), "gather_gemm: more than 2^30 pixel rows");
     RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)gate) % 16 == 0,
                     "gather_gemm: pointers must be 16-byte aligned");
-    RBVAE_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 2 || mask), "gather_gemm: drop_mode/mask");
-    RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "gather_gemm: drop_p=%g outside [0, 1)", (double)drop_p);
     GgArgs a;
+    if (const int e = epi_drop_args("gather_gemm", drop_mode, mask, drop_p, &a.drop_thresh)) return e;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
     a.gate = (const unsigned char*)gate; a.mask = (const unsigned char*)mask; a.addend = (const unsigned char*)addend;
     a.zero = (const unsigned char*)zero_page;
     a.Nimg = Nimg; a.IH = IH; a.IW = IW; a.TH = TH; a.TW = TW; a.sa = sa; a.OH = OH; a.OW = OW; a.so = so;
     a.Kc = Kc; a.Nout = Nout; a.lda = lda; a.ldo = ldo; a.taps_total = taps_total;
     a.relu = relu; a.drop_mode = drop_mode; a.scale = scale; a.seed = seed; a.seed_dev = seed_dev; a.colsum_ws = colsum_ws;
-    a.drop_thresh = (unsigned)((double)drop_p * 4294967296.0);
     a.nclass = nclass;
     constexpr int dephase = 1;
     a.dephase = dephase;

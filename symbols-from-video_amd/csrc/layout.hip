@@ -2,7 +2,7 @@
 // slab reduction back to torch layouts, im2col for the few-channel ends of the
 // network, the col2im + sigmoid + MSE epilogue of the last ConvTranspose2d, column
 // sums (bias gradients), f32 -> T casts, the skinny Linear (N <= 128) and Adam.
-#include "mma.h"
+#include "epilogue.h"
 #include <stdlib.h>
 
 namespace rbvae {
@@ -171,10 +171,10 @@ __global__ void im2col_k(const float* __restrict__ src, FrameMap fm, long sc, lo
         T* dst = col + pp * Kpad + kg * 8;
         if constexpr (sizeof(T) == 2) {
             uint4 pk;
-            pk.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-            pk.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-            pk.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-            pk.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
+            pk.x = pack_bf16x2(v[0], v[1]);
+            pk.y = pack_bf16x2(v[2], v[3]);
+            pk.z = pack_bf16x2(v[4], v[5]);
+            pk.w = pack_bf16x2(v[6], v[7]);
             *(uint4*)dst = pk;
         } else {
             *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
@@ -217,10 +217,10 @@ __global__ __launch_bounds__(256) void im2col_fast_k(const float* __restrict__ s
     T* dst = col + (size_t)pp * Kpad + kg * 8;
     if constexpr (sizeof(T) == 2) {
         uint4 pk;
-        pk.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-        pk.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-        pk.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-        pk.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
+        pk.x = pack_bf16x2(v[0], v[1]);
+        pk.y = pack_bf16x2(v[2], v[3]);
+        pk.z = pack_bf16x2(v[4], v[5]);
+        pk.w = pack_bf16x2(v[6], v[7]);
         *(uint4*)dst = pk;
     } else {
         *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
@@ -278,10 +278,10 @@ __global__ __launch_bounds__(256) void im2col_lds_k(const float* __restrict__ sr
         T* dst = col + ((size_t)(n * OH + oh) * OW + ow) * Kpad + kg * 8;
         if constexpr (sizeof(T) == 2) {
             uint4 pk;
-            pk.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-            pk.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-            pk.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-            pk.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
+            pk.x = pack_bf16x2(v[0], v[1]);
+            pk.y = pack_bf16x2(v[2], v[3]);
+            pk.z = pack_bf16x2(v[4], v[5]);
+            pk.w = pack_bf16x2(v[6], v[7]);
             *(uint4*)dst = pk;
         } else {
             *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);

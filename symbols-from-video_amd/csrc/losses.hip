@@ -1,6 +1,6 @@
 // Binarise + KL, pairwise-distance losses, MSE: the small f32 reductions of the
 // RBVAE step.  All sums run in a fixed order (bitwise reproducible run to run).
-#include "common.h"
+#include "epilogue.h"
 
 namespace rbvae {
 
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(RED_THREADS) void binarize_kl_fwd_k(
     __shared__ float red[RED_THREADS / 64];
     const int n = rows * L;
     float acc = 0.f;
-    if (seed_dev) seed += seed_dev[0] * 0x9E3779B97F4A7C15ull;
+    if (seed_dev) seed = epi_seed(seed, seed_dev);      // (guarded: without the if the listing changes)
     // batches of UB elements per thread: every global load of a batch is in flight before the first use (the
     // one-element-per-iteration loop paid a memory round trip per element: 8 of them at 256 x 32)
     constexpr int UB = 8;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void binarize_kl_fwd_parts_k(
     const int i = blockIdx.x * 256 + threadIdx.x;
     float acc = 0.f;
     if (i < n) {
-        if (seed_dev) seed += seed_dev[0] * 0x9E3779B97F4A7C15ull;
+        if (seed_dev) seed = epi_seed(seed, seed_dev);
         const float u = U ? U[i] : (float)(hash_u32(seed, (unsigned long long)i) >> 8) * (1.0f / 16777216.0f);
         const float noise = ratio * (logf(u + neps) - logf(1.0f - u + neps));
         const float y = sigmoidf_((h[i] + noise) / tau);
