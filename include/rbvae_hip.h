@@ -1047,6 +1047,62 @@ int rbvae_hmm_posterior(const double* alpha, const double* beta, const double* e
 int rbvae_hmm_viterbi(const double* logb, int N, int K, const double* log_pi, const double* log_A, unsigned char* back,
                       int* path, double* score, const int* state, void* stream);
 
+/* ---- hidden Markov model over several sequences (csrc/hmm.hip) -----------------------------------------------
+ * Several recordings of one task share one model.  The rows of S sequences are stacked in time order, X f32 [N][L] and every
+ * per-row array as above; lengths int32 [S] with every length >= 1 and sum N.  rbvae_hmm_ok(N, L, K) holds for the stacked N
+ * and 1 <= S <= N (rbvae_hmm_seq_ok); a single sequence may be shorter than K, down to one row.  Refusals, state, status (rows
+ * counted from the start of the stack) and the arithmetic are the single-sequence entries': f64, never contracted, no
+ * floating-point atomics, every sum in one fixed order, two runs bit-identical.  rbvae_hmm_emit and rbvae_bern_emit are per
+ * row and serve unchanged.
+ * Blocks restart at every sequence: sequence s, of n_s rows, is cut into ceil(n_s / block_rows) blocks counted from its own
+ * first row (block_rows above N is taken as N), and the three launches of the recurrence treat every sequence as the
+ * single-sequence entries treat theirs.  So on the rows of sequence s alpha, ll, beta, back, path and score[s] are bit-equal
+ * to what rbvae_hmm_forward / _backward / _viterbi write for that sequence alone at the same block_rows (wherever they accept
+ * it: n_s >= max(K, 2)), rows of one sequence never depend on another's values, and with S = 1 every output of every entry
+ * here has the single-sequence entry's bytes.
+ * rbvae_hmm_seq_forward: the first row of every sequence is y = pi e_t (element-wise); otherwise rbvae_hmm_forward's step;
+ * ll_t as there.  rbvae_hmm_seq_backward: the last row of every sequence is beta = 1 / K, and the row before it reads e and
+ * beta of that row only.  Launch (i) runs over the blocks of all sequences, a sequence's own first (backward: last) block
+ * carrying its recursion; launch (ii) is one wave per sequence, walking that sequence's blocks (a sequence of one block has
+ * nothing to pass on, one of two blocks nothing to combine: its second block takes the first's own recursion); launch (iii)
+ * again over all blocks.
+ * rbvae_hmm_seq_posterior: gamma as rbvae_hmm_posterior for every row.  Xi_ij is its two-stage sum over the stacked rows
+ * (xblocks blocks of ceil(N / xblocks) rows, t ascending, the partials in block order) with the terms t that are the last row
+ * of a sequence skipped: not computed, no Z_t, and status counts a bad Z_t only for the terms that exist.  A_new as there.
+ * pi_new_k = (sum_s gamma_k,first(s)) / S: one running sum from zero with s ascending, then one division.
+ * rbvae_hmm_seq_viterbi: rbvae_hmm_viterbi per sequence, one wave each: back of a first row is 0, the last state of sequence
+ * s is the lowest j that attains the maximum of its last row, score f64 [S] holds those maxima.
+ * The plan.  rbvae_hmm_seq_plan checks the host lengths (a length below 1, a sum other than N, a NULL pointer or a plan below
+ * rbvae_hmm_seq_plan_bytes(N, S, block_rows): RBVAE_E_INVALID; S outside [1, N]: RBVAE_E_UNSUPPORTED; nothing is written),
+ * builds the plan on the host and copies it to plan_dev on the stream, which it waits for.  int32, in this order:
+ *   {S, N, block_rows, B}   B = sum_s ceil(n_s / block_rows), the blocks in use
+ *   row [S + 1]             the first row of sequence s; row[S] = N
+ *   end [N]                 1 where row t is the last of its sequence, else 0
+ *   blk [S + 1]             the first block of sequence s; blk[S] = B
+ *   seq [maxb]              the sequence of block b; maxb = min(N, ceil(N / block_rows) + S) >= B is the grid of launches (i), (iii)
+ * rbvae_hmm_seq_plan_bytes = 4 (6 + 2 S + N + maxb).  The entries take the plan made for their N, S and block_rows (posterior
+ * and Viterbi read row and end only, which do not depend on block_rows).  A kernel clamps every row, block and sequence index
+ * it reads from the plan to the arrays' extent before it uses it (rows to [0, N), blocks to [0, maxb), sequences to [0, S)):
+ * a stale or foreign plan gives wrong numbers but no access outside the arrays.
+ * ws: rbvae_hmm_seq_ws_bytes(N, K, S, block_rows) = 8 max(maxb (K K + 2 K), N + xblocks K K) bytes for the block_rows of the
+ * recurrence; every block of the grid has its slot, also those of one-block sequences, which use none (S = 30 000 short
+ * sequences at K = 64 reserve 1 GB: choose block_rows >= the longest sequence there, or fewer states).  The posterior asks for
+ * 8 (N + xblocks K K) bytes only, whatever block_rows. */
+int rbvae_hmm_seq_ok(int N, int L, int K, int S);
+size_t rbvae_hmm_seq_plan_bytes(int N, int S, int block_rows);
+int rbvae_hmm_seq_plan(const int* lengths_host, int S, int N, int block_rows, void* plan_dev, size_t plan_bytes, void* stream);
+size_t rbvae_hmm_seq_ws_bytes(int N, int K, int S, int block_rows);
+int rbvae_hmm_seq_forward(const double* e, const double* rowmax, int N, int K, const double* pi, const double* A,
+                          int block_rows, const void* plan, int S, double* alpha, double* ll, int* status, void* ws,
+                          size_t ws_bytes, const int* state, void* stream);
+int rbvae_hmm_seq_backward(const double* e, int N, int K, const double* A, int block_rows, const void* plan, int S,
+                           double* beta, int* status, void* ws, size_t ws_bytes, const int* state, void* stream);
+int rbvae_hmm_seq_posterior(const double* alpha, const double* beta, const double* e, int N, int K, const void* plan, int S,
+                            const double* A, double* gamma, double* xi, double* A_new, double* pi_new, int* status, void* ws,
+                            size_t ws_bytes, const int* state, void* stream);
+int rbvae_hmm_seq_viterbi(const double* logb, int N, int K, const void* plan, int S, const double* log_pi, const double* log_A,
+                          unsigned char* back, int* path, double* score, const int* state, void* stream);
+
 /* ---- Bernoulli models of the hard codes (csrc/bernoulli.hip) -------------------------------------------------
  * A state is a vector of bit probabilities: theta f64 [K][L], with logt = log theta and logf = log(1 - theta) as the M-step
  * writes them.  The codes are bit-packed, bits uint32 [N][4] (16-byte aligned): bit l of row i sits in word l / 32 at

@@ -37,7 +37,7 @@ from .mixture import (GMMResult, gmm, gmm_aic, gmm_bic, gmm_predict, gmm_predict
                       gmm_score_samples, gmm_select, latent_mixture)
 from . import hmm as _hmm_module  # noqa: F401  (the module is sfv.hmm_model: the name hmm is the fit, as gmm is the mixture's)
 from .hmm import (HMMResult, hmm, hmm_aic, hmm_bic, hmm_forward_backward, hmm_predict, hmm_predict_proba,  # noqa: F401
-                  hmm_score, hmm_score_samples, hmm_select, hmm_viterbi, latent_hmm)
+                  hmm_score, hmm_score_samples, hmm_select, hmm_sequence_scores, hmm_viterbi, latent_hmm, latent_hmm_videos)
 hmm_model = _hmm_module
 from . import bernoulli  # noqa: F401
 from .bernoulli import (BHMMResult, BMMResult, bhmm, bhmm_aic, bhmm_bic, bhmm_predict, bhmm_predict_proba,  # noqa: F401

@@ -16,7 +16,8 @@ codes; the recursions, the posterior, Viterbi and the stop decision are hmm.py's
   latent_code_models    both fits on the script's data, scored against the states and the flags
 The start is a labelling (symbols.kmeans' on the codes by default: Euclidean distance on 0/1 is Hamming distance); its one-hot
 responsibilities go through one M-step.  theta_kl = (S_kl + prior) / (nk_k + 2 prior): prior > 0 keeps every log finite.
-Several sequences, priors on A, tied or per-bit-shared probabilities and a categorical model of bit groups are not built.
+The bhmm family takes lengths=(n_0, n_1, ...) for several sequences stacked in time order, as hmm.hmm's does (the
+rbvae_hmm_seq_ entries).  Priors on A, tied or per-bit-shared probabilities and a categorical model of bit groups are not built.
 There is no host path: a matrix on the CPU raises.  The shapes are rbvae_bern_ok's (bhmm: also rbvae_hmm_ok's).
 """
 from __future__ import annotations
@@ -32,7 +33,7 @@ from . import mixture, symbols
 from ._latents import ENQUEUE  # noqa: F401  (the batch of run_until_done)
 from ._latents import checked_matrix, encode_frames, frame_count, frame_labels, run_until_done
 from .hmm import MAX_STATES  # noqa: F401  (rbvae_hmm_ok; the package's name hmm is the fit, so the module's names come from .hmm)
-from .hmm import _block_rows, _Buffers, _initial_transitions, _viterbi, change_points
+from .hmm import _block_rows, _Buffers, _initial_transitions, _plan, _viterbi, change_points
 
 MAX_COMPONENTS = 256                                # rbvae_bern_ok
 
@@ -66,6 +67,8 @@ class BHMMResult:
     posterior: torch.Tensor             # f64 [N, K]: the smoothed posterior under the final parameters
     path: torch.Tensor                  # int32 [N]: the Viterbi path under the final parameters
     path_score: float                   # its log-probability
+    lengths: Optional[tuple] = None     # the lengths of the sequences the fit saw (None: one sequence)
+    path_scores: Optional[np.ndarray] = None    # f64 [S]: every sequence's path log-probability; path_score is their sum
 
 
 def _checked(codes, K, what, chain=False):
@@ -216,9 +219,11 @@ def _emit(buf, bits, N, Ld, K, logt, logf, state=None):
 
 
 def bhmm(codes: torch.Tensor, n_states: int, init: Union[str, torch.Tensor, np.ndarray] = "kmeans", max_iter: int = 100,
-         tol: float = 1e-3, prior: float = 1.0, seed: int = 42, block_rows: Optional[int] = None) -> BHMMResult:
+         tol: float = 1e-3, prior: float = 1.0, seed: int = 42, block_rows: Optional[int] = None,
+         lengths: Optional[Sequence[int]] = None) -> BHMMResult:
     """Baum-Welch with Bernoulli emissions for an f32 device matrix of hard codes [N, L] whose rows are one sequence in time
-    order.  It is hmm.hmm's iteration -- the emissions, the recursions and the posterior under the current parameters, then pi
+    order, or with lengths several, stacked (hmm.hmm's: no transition across a boundary, pi from every first row).  It is
+    hmm.hmm's iteration -- the emissions, the recursions and the posterior under the current parameters, then pi
     and A (rbvae_hmm_posterior), theta from the posterior (rbvae_bern_mstep; its weights are unused) and the mixture's decision
     on the device -- with the same start (theta from the labelling's one-hot posterior, A_ij = (n_ij + 1) / (sum_j n_ij + K),
     pi = 1 / K), the same "degenerate" ending and the same final pass for the posterior and the Viterbi path."""
@@ -228,7 +233,8 @@ def bhmm(codes: torch.Tensor, n_states: int, init: Union[str, torch.Tensor, np.n
     R = _block_rows(block_rows)
     lab = mixture.start_labels(codes, K, init, seed)
     bits = _pack(codes)
-    buf = _Buffers(N, K, R, dev)
+    plan = _plan(lengths, N, R, dev, "bhmm")
+    buf = _Buffers(N, K, R, dev, plan)
     buf.gamma.zero_()
     buf.gamma.scatter_(0, lab.view(1, N), 1.0)
     m = MStep(bits, N, Ld, K, prior)                        # its weights are unused
@@ -236,7 +242,7 @@ def bhmm(codes: torch.Tensor, n_states: int, init: Union[str, torch.Tensor, np.n
     lb = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
     history = torch.zeros(max_iter, dtype=torch.float64, device=dev)
     m.run(buf.gamma)
-    A = _initial_transitions(lab, K)
+    A = _initial_transitions(lab, K, plan)
     pi = torch.full((K,), 1.0 / K, dtype=torch.float64, device=dev)
 
     def iteration(it):
@@ -251,16 +257,17 @@ def bhmm(codes: torch.Tensor, n_states: int, init: Union[str, torch.Tensor, np.n
     _emit(buf, bits, N, Ld, K, m.logt, m.logf)
     buf.recursions(pi, A)
     buf.posterior(A, scratch_A, scratch_pi)
-    path, score = _viterbi(buf.logb, N, K, pi, A)
+    path, score, *scores = _viterbi(buf.logb, N, K, pi, A, plan)
     lls = history[:max(n_iter, 1)].cpu().numpy()
     reason = "degenerate" if degenerate else ("converged" if why == 1 else "max_iter")
     return BHMMResult(pi, A, m.theta, m.logt, m.logf, int(n_iter), reason == "converged", reason, float(lls[-1]), lls,
-                      buf.gamma.t(), path, score)
+                      buf.gamma.t(), path, score, *((plan.lengths, scores[0]) if plan is not None else ()))
 
 
-def _bhmm_estep(fit: BHMMResult, codes, what, posterior=False):
+def _bhmm_estep(fit: BHMMResult, codes, what, posterior=False, lengths=None):
     codes, N, Ld, K = _same_bits(fit, codes, what, chain=True)
-    buf = _Buffers(N, K, _block_rows(None), codes.device)
+    R = _block_rows(None)
+    buf = _Buffers(N, K, R, codes.device, _plan(lengths, N, R, codes.device, what))
     _emit(buf, _pack(codes), N, Ld, K, fit.log_probs, fit.log_1m_probs)
     if posterior is not None:
         buf.recursions(fit.startprob, fit.transmat)
@@ -269,25 +276,26 @@ def _bhmm_estep(fit: BHMMResult, codes, what, posterior=False):
     return buf
 
 
-def bhmm_score_samples(fit: BHMMResult, codes: torch.Tensor) -> torch.Tensor:
-    """f64 [N] on the device: ll_t = log p(x_t | x_0 .. x_(t-1)); their sum is the sequence's log-likelihood"""
-    return _bhmm_estep(fit, codes, "bhmm_score_samples").ll
+def bhmm_score_samples(fit: BHMMResult, codes: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """f64 [N] on the device: ll_t = log p(x_t | x_0 .. x_(t-1)), the earlier rows of its own sequence; a sequence's sum is its
+    log-likelihood"""
+    return _bhmm_estep(fit, codes, "bhmm_score_samples", lengths=lengths).ll
 
 
-def bhmm_score(fit: BHMMResult, codes: torch.Tensor) -> float:
-    """the mean per-row log-likelihood of the sequence, added on the device in rbvae_gmm_decide's order"""
-    return mixture._mean_in_order(bhmm_score_samples(fit, codes))
+def bhmm_score(fit: BHMMResult, codes: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> float:
+    """the mean per-row log-likelihood of the sequence (or sequences), added on the device in rbvae_gmm_decide's order"""
+    return mixture._mean_in_order(bhmm_score_samples(fit, codes, lengths))
 
 
-def bhmm_predict(fit: BHMMResult, codes: torch.Tensor) -> torch.Tensor:
-    """int32 [N] on the device: the Viterbi path of the sequence"""
-    buf = _bhmm_estep(fit, codes, "bhmm_predict", posterior=None)
-    return _viterbi(buf.logb, buf.N, buf.K, fit.startprob, fit.transmat)[0]
+def bhmm_predict(fit: BHMMResult, codes: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """int32 [N] on the device: the Viterbi path of the sequence (of every sequence)"""
+    buf = _bhmm_estep(fit, codes, "bhmm_predict", posterior=None, lengths=lengths)
+    return _viterbi(buf.logb, buf.N, buf.K, fit.startprob, fit.transmat, buf.plan)[0]
 
 
-def bhmm_predict_proba(fit: BHMMResult, codes: torch.Tensor) -> torch.Tensor:
-    """f64 [N, K] on the device: the smoothed posterior of the sequence"""
-    return _bhmm_estep(fit, codes, "bhmm_predict_proba", posterior=True).gamma.t()
+def bhmm_predict_proba(fit: BHMMResult, codes: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """f64 [N, K] on the device: the smoothed posterior of the sequence (of every sequence)"""
+    return _bhmm_estep(fit, codes, "bhmm_predict_proba", posterior=True, lengths=lengths).gamma.t()
 
 
 def bhmm_n_parameters(K: int, Ld: int) -> int:
@@ -295,20 +303,23 @@ def bhmm_n_parameters(K: int, Ld: int) -> int:
     return (K - 1) + K * (K - 1) + K * Ld
 
 
-def bhmm_bic(fit: BHMMResult, codes: torch.Tensor) -> float:
+def bhmm_bic(fit: BHMMResult, codes: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> float:
     """-2 score(codes) N + p log N"""
-    return mixture.criteria(bhmm_score(fit, codes), codes.shape[0], bhmm_n_parameters(*fit.probs.shape))[0]
+    return mixture.criteria(bhmm_score(fit, codes, lengths), codes.shape[0], bhmm_n_parameters(*fit.probs.shape))[0]
 
 
-def bhmm_aic(fit: BHMMResult, codes: torch.Tensor) -> float:
+def bhmm_aic(fit: BHMMResult, codes: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> float:
     """-2 score(codes) N + 2 p"""
-    return mixture.criteria(bhmm_score(fit, codes), codes.shape[0], bhmm_n_parameters(*fit.probs.shape))[1]
+    return mixture.criteria(bhmm_score(fit, codes, lengths), codes.shape[0], bhmm_n_parameters(*fit.probs.shape))[1]
 
 
-def bhmm_select(codes: torch.Tensor, ks: Sequence[int], criterion: str = "bic", seed: int = 42, **fit_kwargs):
+def bhmm_select(codes: torch.Tensor, ks: Sequence[int], criterion: str = "bic", seed: int = 42,
+                lengths: Optional[Sequence[int]] = None, **fit_kwargs):
     """mixture.select with bhmm, bhmm_score and bhmm_n_parameters -> (table, the chosen K, its BHMMResult)"""
+    if lengths is not None:
+        fit_kwargs["lengths"] = lengths
     return mixture.select(codes, ks, criterion, lambda K: bhmm(codes, K, seed=seed, **fit_kwargs),
-                          lambda fit: bhmm_score(fit, codes), bhmm_n_parameters)
+                          lambda fit: bhmm_score(fit, codes, lengths), bhmm_n_parameters)
 
 
 @torch.no_grad()

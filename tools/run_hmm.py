@@ -3,11 +3,13 @@ iteration (device events, the fastest of three runs after a warm-up), the forwar
 blocked default, Viterbi, the wall time of a whole fit from a perturbed labelling, and -- with --host -- the numpy
 restatement of tests/_hmm_ref.py on the host for the same iterations.
 
-    python tools/run_hmm.py [N L K] [--host] [--host-iters 2] [--launches-only] [--out FILE]
+    python tools/run_hmm.py [N L K] [--host] [--host-iters 2] [--launches-only] [--sequences S [S ...]] [--out FILE]
 
 Default size: 12298 x 50 in 17 states (tools/run_mixture.py's shape).  The states follow a sticky chain (stay 0.98); the start
 is the states' own labelling with every tenth row moved to the next state.  The three launches of a blocked pass are one
 entry point: their split comes from a kernel trace of this tool run with --launches-only (profiles/hmm_times.txt).
+--sequences S cuts the same chain into S pieces of (nearly) equal length and times the rbvae_hmm_seq_ entries on them, next to
+the single-sequence entries of the same run (profiles/hmm_sequences_times.txt); without it the report is unchanged.
 """
 import argparse
 import os
@@ -42,6 +44,8 @@ def main():
     ap.add_argument("--host", action="store_true", help="also run the numpy restatement of tests/_hmm_ref.py on the host")
     ap.add_argument("--host-iters", type=int, default=2, help="iterations of the host run")
     ap.add_argument("--launches-only", action="store_true", help="only the device times of the entries")
+    ap.add_argument("--sequences", type=int, nargs="+", default=[], metavar="S",
+                    help="also time the chain cut into S sequences (the rbvae_hmm_seq_ entries), for every S given")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args()
     N, Ld, K = a.shape
@@ -108,6 +112,35 @@ def main():
     say(f"  decision                                {t_d:9.3f} ms")
     say(f"  an iteration's fourteen launches        {t_e + t_f + t_b + t_p + t_m + t_d:9.3f} ms of device time")
     say(f"  Viterbi (one wave, once per fit)        {t_v:9.3f} ms   {t_v / N * 1e3:.3f} us per row")
+    for S in a.sequences:
+        lengths = [N // S + (1 if s < N % S else 0) for s in range(S)]
+        sb = M._Buffers(N, K, R, X.device, M._Plan(tuple(lengths), N, R, X.device))
+        sb.e, sb.rowmax, sb.logb = buf.e, buf.rowmax, buf.logb
+        p = sb.plan
+        scores = f64(S)
+        t_sf = device_ms(lambda: call("rbvae_hmm_seq_forward", sb.e, sb.rowmax, N, K, pi, A, R, p.dev, S, sb.alpha, sb.ll, sb.status,
+                                      sb.ws, sb.ws_bytes, None))
+        t_sb = device_ms(lambda: call("rbvae_hmm_seq_backward", sb.e, N, K, A, R, p.dev, S, sb.beta, sb.status, sb.ws, sb.ws_bytes, None))
+        t_sp = device_ms(lambda: sb.posterior(A, A2, pi2))
+        t_sv = device_ms(lambda: call("rbvae_hmm_seq_viterbi", sb.logb, N, K, p.dev, S, lpi, lA, back, path, scores, None))
+        blocks = sum(-(-n // R) for n in lengths)
+        say(f"{S} sequences of {min(lengths)} to {max(lengths)} rows: {blocks} blocks, the longest walk {-(-max(lengths) // R)}")
+        say(f"  forward (three launches)                {t_sf:9.3f} ms   one sequence, the existing entry {t_f:9.3f} ms: {t_f / t_sf:.2f} x")
+        say(f"  backward (three launches)               {t_sb:9.3f} ms   one sequence, the existing entry {t_b:9.3f} ms: {t_b / t_sb:.2f} x")
+        say(f"  posterior (three launches)              {t_sp:9.3f} ms   one sequence, the existing entry {t_p:9.3f} ms")
+        say(f"  Viterbi (a wave per sequence)           {t_sv:9.3f} ms   one sequence, the existing entry {t_v:9.3f} ms: {t_v / t_sv:.2f} x")
+        say(f"  forward + backward + Viterbi            {t_sf + t_sb + t_sv:9.3f} ms   one sequence, the existing entries "
+            f"{t_f + t_b + t_v:9.3f} ms")
+        if not a.launches_only:
+            sfv.hmm(X, K, init=start, max_iter=2, lengths=lengths)      # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sfit = sfv.hmm(X, K, init=start, lengths=lengths)
+            torch.cuda.synchronize()
+            t_sfit = time.perf_counter() - t0
+            say(f"  whole fit (wall): {t_sfit:.4f} s, {sfit.n_iter} iterations ({sfit.why}), {t_sfit / sfit.n_iter * 1e3:.3f} ms per "
+                f"iteration, mean log-likelihood {sfit.log_likelihood:.6f}, Viterbi ARI "
+                f"{sfv.clustering_agreement(lab, sfit.path, K, K)['ari']:.4f}")
     if a.launches_only:
         if out:
             out.close()
