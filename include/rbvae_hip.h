@@ -1302,6 +1302,83 @@ int rbvae_dtw_fill_bits(const uint32_t* xbits, int N, const uint32_t* ybits, int
 int rbvae_dtw_trace(const unsigned char* dirs, const double* last_row, int N, int M, int subsequence, int* path, int* state,
                     double* cost, void* stream);
 
+/* ---- Many sequences aligned: batched pairs, path ranges and the DBA update (csrc/dtw.hip; since version 111) ----
+ * Two stacks and a pair list.  X is f32 [sum_a len_x[a]][L] with len_x int32 [Sx], Y f32 [sum_b len_y[b]][L] with len_y
+ * int32 [Sy]: the rows of a sequence are contiguous and in time order, sequence s starts at the row that the lengths before
+ * it add up to.  For metric 2 the stacks are uint32 [.][4] as rbvae_bern_pack writes them.  pairs int32 [P][2] holds
+ * (a, b): sequence a of the X stack (the table's N = len_x[a] rows) against sequence b of the Y stack (its M = len_y[b]
+ * columns).  All pairs of one stack pass the stack twice; self pairs and repeated pairs are allowed.  len_x, len_y and
+ * pairs are HOST arrays everywhere below.  Limits (rbvae_dtw_pairs_ok = 1): Sx, Sy >= 1, 1 <= every length <= 16384, each
+ * stack at most 2^31 - 1 rows, 1 <= L <= 128, 1 <= P <= 65535, metric 0 .. 2, 0 <= a < Sx, 0 <= b < Sy.  There is no
+ * band and no subsequence mode.  Anything outside makes the entries that take the lengths return RBVAE_E_UNSUPPORTED
+ * without a launch and without a write; a NULL pointer RBVAE_E_INVALID.
+ *
+ * The promise.  For every pair, dirs, last_row, path, state and cost are bit for bit what rbvae_dtw_fill(_bits) followed by
+ * rbvae_dtw_trace (window = -1, subsequence = 0, table = NULL) write for that pair alone: the same cell cost, table, tie
+ * order and packing as stated above.  They do not depend on which other pairs are in the batch or on their order; P = 1
+ * gives the single-pair entries' bytes.
+ *
+ * Layout.  Pair p's block of each output has exactly the single-pair entry's layout -- dirs uint8 [N][ceil(M / 4)],
+ * last_row f64 [M], path int32 [N + M - 1][2], ws as rbvae_dtw_ws_bytes(N, M) (frontier row [M], frontier column [N], one
+ * corner per tile: each pair has its own) -- and the blocks follow each other in pair order.  A dirs block starts at a
+ * multiple of 16 bytes: its size is N ceil(M / 4) rounded up to 16, and the padding bytes are never written.
+ * rbvae_dtw_pairs_sizes writes the host arrays int64 [P + 1] dirs_off (bytes), last_off (doubles), ws_off (bytes) and
+ * path_off (rows of two int32): entry p is where pair p's block starts and entry P the total; totals size_t [4] =
+ * {bytes of dirs, doubles of last_row, bytes of ws, rows of path}.  state is int32 [P][3] and cost f64 [P], pair p's at 3 p
+ * and p, each as rbvae_dtw_trace writes it.
+ *
+ * Plan.  rbvae_dtw_pairs_plan checks the lengths and pairs as above, needs plan_bytes >= rbvae_dtw_pairs_plan_bytes(P) =
+ * 8 (4 + 10 P) (0 for P outside its limits; RBVAE_E_INVALID when smaller), builds the plan on the host, copies it to
+ * plan_dev on the stream and waits for the copy.  The plan is int64: {P, rows of the X stack, rows of the Y stack, 0}, then per
+ * pair {first row in X, first row in Y, N, M, tiles down, tiles across, dirs_off, last_off, ws_off / 8, path_off}.  launch
+ * (host int32 [2]) receives what the fill loops over: the number of tile anti-diagonals of the largest pair, max_p (tiles
+ * down + tiles across - 1), and the most tiles any pair has on one anti-diagonal, max_p min(tiles down, tiles across).
+ *
+ * rbvae_dtw_pairs_fill / _fill_bits: X [Nx][L], Y [Ny][L] (or the packed stacks), the plan of these stacks and pairs,
+ * n_diag and max_tiles as the plan returned them, dirs of dirs_bytes bytes, last_row of last_n doubles, ws of ws_bytes
+ * bytes, all at least the totals above.  ONE launch per tile anti-diagonal d = 0 .. n_diag - 1 for all pairs together, grid
+ * (min(d + 1, max_tiles), P): workgroup (x, p) owns the x-th tile of pair p on diagonal d and returns before any work where
+ * the pair has fewer.  The launch order on the stream is the only dependency between workgroups: no flags in memory, no
+ * workgroup waits for another, no cooperative launch, no floating-point atomics.  Nx, Ny < 1, L, metric, P outside the
+ * limits, n_diag outside [1, 511], max_tiles outside [1, 256] or metric 2 given to rbvae_dtw_pairs_fill:
+ * RBVAE_E_UNSUPPORTED.  Every index a kernel reads from the plan is clamped to Nx, Ny, dirs_bytes, last_n, ws_bytes (and
+ * path_rows below), and a pair whose block fits nowhere is skipped: a plan made for other arrays gives wrong numbers and no
+ * access outside the arrays given.
+ * rbvae_dtw_pairs_trace: one workgroup per pair walks its dirs block from (N - 1, M - 1) as rbvae_dtw_trace does and writes
+ * its block of path (path_rows rows in all, 8-byte aligned), state [p] and cost [p].
+ *
+ * rbvae_dtw_path_ranges: from one pair's ascending path (as the trace left it, state its int32 [3] on the device: the length
+ * is read there, not on the host), lo int32 [n] and hi int32 [n]: the first and the last j aligned with row i.  One thread
+ * per path element writes lo[i] where the previous element has another i (or there is none) and hi[i] where the next one
+ * has; every row of a global path has exactly one of each, so no atomics.  state[0] < 1 writes nothing.  (n, m) outside
+ * 1 .. 16384: RBVAE_E_UNSUPPORTED.
+ *
+ * rbvae_dtw_barycenter_update: one step of DTW barycenter averaging (Petitjean, Ketterlin and Gancarski 2011) under squared
+ * Euclidean distance.  The template is the X side of the P pairs of the plan (T rows; the plan's pairs in order are the
+ * sequences s = 0 .. P - 1 whose Y rows are averaged), lo and hi are int32 [P][T] as rbvae_dtw_path_ranges wrote them for
+ * each pair.  For every row i < T and coordinate l < L: acc = 0.0 in f64; for p ascending, for j from lo[p][i] to hi[p][i]
+ * ascending, acc += (double)y_p[j][l], every addition rounded once; cnt_i = sum_p (hi[p][i] - lo[p][i] + 1) (>= P on
+ * global paths); out[i][l] = (float)(acc / (double)cnt_i): one f64 division, then one rounding to f32; count int32 [T] =
+ * cnt_i.  One thread per (i, l), l fastest; no atomics.  lo and hi are clamped to the pair's rows.  Ny < 1, L outside
+ * 1 .. 128, P outside 1 .. 65535, T outside 1 .. 16384: RBVAE_E_UNSUPPORTED. */
+int rbvae_dtw_pairs_ok(const int* len_x, int Sx, const int* len_y, int Sy, const int* pairs, int P, int L, int metric);
+int rbvae_dtw_pairs_sizes(const int* len_x, int Sx, const int* len_y, int Sy, const int* pairs, int P, int64_t* dirs_off,
+                          int64_t* last_off, int64_t* ws_off, int64_t* path_off, size_t* totals);
+size_t rbvae_dtw_pairs_plan_bytes(int P);
+int rbvae_dtw_pairs_plan(const int* len_x, int Sx, const int* len_y, int Sy, const int* pairs, int P, void* plan_dev,
+                         size_t plan_bytes, int* launch, void* stream);
+int rbvae_dtw_pairs_fill(const float* X, int Nx, const float* Y, int Ny, int L, int metric, const void* plan, int P, int n_diag,
+                         int max_tiles, unsigned char* dirs, size_t dirs_bytes, double* last_row, size_t last_n, void* ws,
+                         size_t ws_bytes, void* stream);
+int rbvae_dtw_pairs_fill_bits(const uint32_t* xbits, int Nx, const uint32_t* ybits, int Ny, int L, const void* plan, int P,
+                              int n_diag, int max_tiles, unsigned char* dirs, size_t dirs_bytes, double* last_row,
+                              size_t last_n, void* ws, size_t ws_bytes, void* stream);
+int rbvae_dtw_pairs_trace(const unsigned char* dirs, size_t dirs_bytes, const double* last_row, size_t last_n, const void* plan,
+                          int P, int* path, size_t path_rows, int* state, double* cost, void* stream);
+int rbvae_dtw_path_ranges(const int* path, const int* state, int n, int m, int* lo, int* hi, void* stream);
+int rbvae_dtw_barycenter_update(const float* Y, int Ny, int L, const void* plan, int P, const int* lo, const int* hi, int T,
+                                float* out, int* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,8 +52,9 @@ from . import segments  # noqa: F401
 from .segments import (SegmentResult, SegmentTable, boundary_agreement, latent_segments, segment,  # noqa: F401
                        segment_layer, segment_prefix, segment_table)
 from . import alignment  # noqa: F401
-from .alignment import (DTWResult, DTWTable, dtw, dtw_fill, dtw_trace, latent_alignment, transfer_labels,  # noqa: F401
-                        warp_map)
+from .alignment import (DTWBarycenter, DTWResult, DTWTable, dtw, dtw_barycenter, dtw_distance_matrix,  # noqa: F401
+                        dtw_fill, dtw_medoid, dtw_pairs, dtw_trace, latent_alignment, latent_alignment_videos,
+                        transfer_labels, vote_labels, warp_map)
 from . import spectral  # noqa: F401
 from .spectral import (EigResult, NormalizedGraph, lanczos_eigsh, latent_spectral, normalized_graph,  # noqa: F401
                        spectral_clustering, spectral_embedding, spectral_layout)

@@ -22,10 +22,16 @@
 // (ti-1, tj) fcol[i0-1] one launch earlier, so every full tile leaves its last cell in corner[ti][tj], written once.
 // A frontier value is used only where its cell lies inside the band, +inf otherwise, so a tile that never ran is never read.
 // No floating-point atomics; two runs agree bit for bit.  Contraction is off.
+// Many pairs (two stacks of sequences and a pair list, a device plan with one row per pair): dtw_tile_k<., true> and
+// dtw_trace_k<true> take the pair from blockIdx.y / blockIdx.x and everything about it from its plan row, each pair with its own
+// frontiers and corners, so one launch serves the same tile anti-diagonal of all pairs and every pair's bytes are those of the
+// single-pair kernels.  dtw_ranges_k and dtw_bary_update_k are the two launches of a DBA step.
 #include "common.h"
 #include "pairdist.h"
 
 #include <math.h>
+
+#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -99,13 +105,72 @@ __device__ __forceinline__ void dtw_chain(double* cst, unsigned char* sd, const 
     }
 }
 
-// grid: the tiles ti_lo .. of tile anti-diagonal `diag`, tj = diag - ti.  metric 0 / 1: X, Y f32 [.][L]; BITS: uint32 [.][4]
-template <bool BITS>
+// The device plan of a batch of pairs (rbvae_dtw_pairs_plan): DP_HDR int64 of header {P, the rows of the X stack, of the Y
+// stack, 0}, then DP_ROW int64 per pair.  The offsets count what the header says: rows, bytes of dirs, doubles of last_row
+// and of ws, rows of path.
+constexpr int DP_HDR = 4, DP_ROW = 10;
+enum { DP_X0, DP_Y0, DP_N, DP_M, DP_NTI, DP_NTJ, DP_DIRS, DP_LAST, DP_WS, DP_PATH };
+
+// the extents of the arrays a batched launch was given: every index read from the plan is clamped to them
+struct DtwExt {
+    long x_rows, y_rows, dirs_bytes, last_n, ws_n, path_rows;
+};
+
+struct DtwPair {
+    long x0, y0, dirs, last, ws, path;
+    int n, m, nTi, nTj;
+    bool ok;
+};
+
+__device__ __forceinline__ long clampl(long v, long lo, long hi) { return (v > hi ? hi : v) < lo ? lo : (v > hi ? hi : v); }
+
+// Pair p of the plan with every index inside the extents (an extent of 0 means that the launch does not touch that array).
+// A stale plan gives wrong numbers; a pair whose block fits nowhere is skipped (ok = false).
+__device__ __forceinline__ DtwPair dtw_pair(const long* __restrict__ plan, int p, const DtwExt& e) {
+    const long* r = plan + DP_HDR + (long)p * DP_ROW;
+    DtwPair q;
+    q.n = (int)clampl(r[DP_N], 1, e.x_rows < DTW_MAX_N ? e.x_rows : DTW_MAX_N);
+    q.m = (int)clampl(r[DP_M], 1, e.y_rows < DTW_MAX_N ? e.y_rows : DTW_MAX_N);
+    q.nTi = (q.n + DT_TI - 1) / DT_TI;                      // the tile counts follow the clamped lengths
+    q.nTj = (q.m + DT_TJ - 1) / DT_TJ;
+    const long W4 = (q.m + 3) >> 2, wsn = (long)q.n + q.m + (long)q.nTi * q.nTj, cap = (long)q.n + q.m - 1;
+    q.x0 = clampl(r[DP_X0], 0, e.x_rows - q.n);
+    q.y0 = clampl(r[DP_Y0], 0, e.y_rows - q.m);
+    q.dirs = clampl(r[DP_DIRS], 0, e.dirs_bytes - q.n * W4);
+    q.last = clampl(r[DP_LAST], 0, e.last_n - q.m);
+    q.ws = clampl(r[DP_WS], 0, e.ws_n - wsn);
+    q.path = clampl(r[DP_PATH], 0, e.path_rows - cap);
+    q.ok = e.x_rows >= 1 && e.y_rows >= 1 && (e.dirs_bytes == 0 || e.dirs_bytes >= q.n * W4) &&
+           (e.last_n == 0 || e.last_n >= q.m) && (e.ws_n == 0 || e.ws_n >= wsn) && (e.path_rows == 0 || e.path_rows >= cap);
+    return q;
+}
+
+// grid: the tiles ti_lo .. of tile anti-diagonal `diag`, tj = diag - ti.  metric 0 / 1: X, Y f32 [.][L]; BITS: uint32 [.][4].
+// PAIRS: grid (the most tiles one pair has on this diagonal, P): the pair is blockIdx.y, whose plan row gives the rows of X
+// and Y, N, M, nTj, its own frow / fcol / corner inside ws and its blocks of dirs and last_row; blockIdx.x counts the pair's
+// tiles on the diagonal from its own first one, and a workgroup beyond its last one returns before any work.  No band, no
+// open ends, no table.  Everything after that is the single pair's code.
+template <bool BITS, bool PAIRS>
 __global__ __launch_bounds__(DT_THREADS) void dtw_tile_k(const void* __restrict__ Xv, const void* __restrict__ Yv, int N, int M,
                                                          int L, int root, int window, int sub, int diag, int ti_lo, int nTj,
                                                          double* __restrict__ frow, double* __restrict__ fcol,
                                                          double* __restrict__ corner, unsigned char* __restrict__ dirs,
-                                                         double* __restrict__ last_row, double* __restrict__ table) {
+                                                         double* __restrict__ last_row, double* __restrict__ table,
+                                                         const long* __restrict__ plan, DtwExt ext) {
+    if constexpr (PAIRS) {
+        const DtwPair q = dtw_pair(plan, blockIdx.y, ext);
+        ti_lo = diag - (q.nTj - 1) > 0 ? diag - (q.nTj - 1) : 0;
+        const int ti_hi = diag < q.nTi - 1 ? diag : q.nTi - 1;
+        if (!q.ok || ti_lo + (int)blockIdx.x > ti_hi) return;   // this pair has no such tile on this diagonal
+        Xv = static_cast<const char*>(Xv) + q.x0 * (BITS ? 16 : 4 * (long)L);
+        Yv = static_cast<const char*>(Yv) + q.y0 * (BITS ? 16 : 4 * (long)L);
+        N = q.n, M = q.m, nTj = q.nTj, window = -1, sub = 0, table = nullptr;
+        frow += q.ws;                                       // the single pair's workspace layout, the pair's own
+        fcol = frow + M;
+        corner = fcol + N;
+        dirs += q.dirs;
+        last_row += q.last;
+    }
     __shared__ __attribute__((aligned(16))) double cst[DT_TI * DT_TJ];      // the costs, then D
     __shared__ __attribute__((aligned(16))) double px[DT_LC * DT_LD];
     __shared__ __attribute__((aligned(16))) double py[DT_LC * DT_LD];
@@ -248,11 +313,23 @@ __global__ __launch_bounds__(DT_THREADS) void dtw_tile_k(const void* __restrict_
         }
 }
 
-// state int32 [3] = {len, start_j, end_j}; len = -1 where dirs holds no walk from the end cell to row 0
+// state int32 [3] = {len, start_j, end_j}; len = -1 where dirs holds no walk from the end cell to row 0.  PAIRS: blockIdx.x is
+// the pair, whose blocks of dirs, last_row and path come from its plan row, state + 3 p and cost + p; the same walk.
+template <bool PAIRS>
 __global__ __launch_bounds__(DT_THREADS) void dtw_trace_k(const unsigned char* __restrict__ dirs,
                                                           const double* __restrict__ last_row, int N, int M, int sub,
                                                           int* __restrict__ path, int* __restrict__ state,
-                                                          double* __restrict__ cost) {
+                                                          double* __restrict__ cost, const long* __restrict__ plan, DtwExt ext) {
+    if constexpr (PAIRS) {
+        const DtwPair q = dtw_pair(plan, blockIdx.x, ext);
+        if (!q.ok) return;
+        N = q.n, M = q.m, sub = 0;
+        dirs += q.dirs;
+        last_row += q.last;
+        path += 2 * q.path;
+        state += 3 * (long)blockIdx.x;
+        cost += blockIdx.x;
+    }
     __shared__ unsigned char td[DT_TI * (DT_TJ / 4)];
     __shared__ double rv[DT_THREADS];
     __shared__ int rj[DT_THREADS];
@@ -390,11 +467,131 @@ static int dtw_fill(const char* name, bool bits, const void* X, int N, const voi
         if ((d + q) / 2 < hi) hi = (d + q) / 2;
         if (lo > hi) continue;
         if (bits)
-            hipLaunchKernelGGL(dtw_tile_k<true>, dim3(hi - lo + 1), dim3(DT_THREADS), 0, st, X, Y, N, M, L, root, window, sub, d,
-                               lo, nTj, frow, fcol, corner, dirs, last_row, table);
+            hipLaunchKernelGGL((dtw_tile_k<true, false>), dim3(hi - lo + 1), dim3(DT_THREADS), 0, st, X, Y, N, M, L, root, window, sub,
+                               d, lo, nTj, frow, fcol, corner, dirs, last_row, table, (const long*)nullptr, DtwExt{});
         else
-            hipLaunchKernelGGL(dtw_tile_k<false>, dim3(hi - lo + 1), dim3(DT_THREADS), 0, st, X, Y, N, M, L, root, window, sub,
-                               d, lo, nTj, frow, fcol, corner, dirs, last_row, table);
+            hipLaunchKernelGGL((dtw_tile_k<false, false>), dim3(hi - lo + 1), dim3(DT_THREADS), 0, st, X, Y, N, M, L, root, window, sub,
+                               d, lo, nTj, frow, fcol, corner, dirs, last_row, table, (const long*)nullptr, DtwExt{});
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(RBVAE_E_LAUNCH, "%s (tile anti-diagonal %d): %s", name, d, hipGetErrorString(e));
+    }
+    return RBVAE_OK;
+}
+
+// ---- many pairs ----------------------------------------------------------------------------------------------------------------
+
+// One thread per path element k < len = state[0]: lo[i] where element k - 1 has another i, hi[i] where element k + 1 has.
+// Every row has one first and one last element, so every lo[i] and hi[i] has one writer.  len < 1: nothing is written.
+__global__ __launch_bounds__(DT_THREADS) void dtw_ranges_k(const int* __restrict__ path, const int* __restrict__ state, int n,
+                                                           int m, int* __restrict__ lo, int* __restrict__ hi) {
+    const int len = min(state[0], n + m - 1);
+    const int k = blockIdx.x * DT_THREADS + threadIdx.x;
+    if (k >= len) return;
+    const int i = path[2 * (long)k], j = min(max(path[2 * (long)k + 1], 0), m - 1);
+    if ((unsigned)i >= (unsigned)n) return;                 // not a path of this table
+    if (k == 0 || path[2 * (long)(k - 1)] != i) lo[i] = j;
+    if (k == len - 1 || path[2 * (long)(k + 1)] != i) hi[i] = j;
+}
+
+// One thread per (i, l), l fastest: acc in f64 over the pairs p ascending and the rows lo[p][i] .. hi[p][i] of pair p's Y
+// sequence ascending, then one f64 division by the number of rows added and one rounding to f32.
+__global__ __launch_bounds__(DT_THREADS) void dtw_bary_update_k(const float* __restrict__ Y, const long* __restrict__ plan,
+                                                                DtwExt ext, int P, int L, int T, const int* __restrict__ lo,
+                                                                const int* __restrict__ hi, float* __restrict__ out,
+                                                                int* __restrict__ count) {
+    const long g = (long)blockIdx.x * DT_THREADS + threadIdx.x;
+    if (g >= (long)T * L) return;
+    const int i = (int)(g / L), l = (int)(g - (long)i * L);
+    double acc = 0.0;
+    int cnt = 0;
+    for (int p = 0; p < P; ++p) {
+        const DtwPair q = dtw_pair(plan, p, ext);
+        if (!q.ok) continue;
+        const int a = min(max(lo[(long)p * T + i], 0), q.m - 1), b = min(max(hi[(long)p * T + i], 0), q.m - 1);
+        const float* y = Y + (q.y0 + a) * L + l;
+        for (int j = a; j <= b; ++j, y += L) acc += (double)*y;
+        cnt += b >= a ? b - a + 1 : 0;
+    }
+    out[g] = (float)(acc / (double)cnt);
+    if (l == 0) count[i] = cnt;
+}
+
+constexpr int DTW_MAX_P = 65535;                            // gridDim.y
+
+static size_t dirs_block(long n, long m) { return ((size_t)n * ((m + 3) >> 2) + 15) & ~(size_t)15; }
+
+// the host lengths and pairs against the limits -> NULL, or what is wrong
+static const char* dtw_pairs_why(const int* len_x, long Sx, const int* len_y, long Sy, const int* pairs, long P, long L,
+                                 int metric) {
+    static thread_local char b[256];
+    auto say = [&](const char* fmt, long a, long c) {
+        snprintf(b, 256, fmt, a, c);
+        return (const char*)b;
+    };
+    if (Sx < 1 || Sy < 1) return say("(Sx=%ld, Sy=%ld): every stack needs a sequence", Sx, Sy);
+    if (P < 1 || P > DTW_MAX_P) return say("P=%ld outside 1 <= P <= %ld", P, DTW_MAX_P);
+    if (L < 1 || L > DTW_MAX_L) return say("L=%ld outside 1 <= L <= %ld", L, DTW_MAX_L);
+    if (metric < 0 || metric > 2) return say("metric=%ld outside 0 .. %ld", metric, 2);
+    long tx = 0, ty = 0;
+    for (long s = 0; s < Sx; ++s) {
+        if (len_x[s] < 1 || len_x[s] > DTW_MAX_N) return say("len_x[%ld]=%ld outside 1 .. 16384", s, len_x[s]);
+        tx += len_x[s];
+    }
+    for (long s = 0; s < Sy; ++s) {
+        if (len_y[s] < 1 || len_y[s] > DTW_MAX_N) return say("len_y[%ld]=%ld outside 1 .. 16384", s, len_y[s]);
+        ty += len_y[s];
+    }
+    if (tx > INT32_MAX || ty > INT32_MAX) return say("the stacks hold %ld and %ld rows, more than an int counts", tx, ty);
+    for (long p = 0; p < P; ++p) {
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= Sx) return say("pairs[%ld][0]=%ld names no sequence of the X stack", p, pairs[2 * p]);
+        if (pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= Sy)
+            return say("pairs[%ld][1]=%ld names no sequence of the Y stack", p, pairs[2 * p + 1]);
+    }
+    return nullptr;
+}
+
+// the offsets of every pair's blocks, pair order, as the header states them; any of the outputs may be NULL
+static void dtw_pairs_offsets(const int* len_x, const int* len_y, const int* pairs, int P, int64_t* dirs_off, int64_t* last_off,
+                              int64_t* ws_off, int64_t* path_off) {
+    int64_t d = 0, l = 0, w = 0, r = 0;
+    for (int p = 0; p <= P; ++p) {
+        if (dirs_off) dirs_off[p] = d;
+        if (last_off) last_off[p] = l;
+        if (ws_off) ws_off[p] = w;
+        if (path_off) path_off[p] = r;
+        if (p == P) break;
+        const long n = len_x[pairs[2 * p]], m = len_y[pairs[2 * p + 1]];
+        d += (int64_t)dirs_block(n, m);
+        l += m;
+        w += (int64_t)sizeof(double) * (n + m + (long)cdiv(n, DT_TI) * cdiv(m, DT_TJ));
+        r += n + m - 1;
+    }
+}
+
+static int dtw_pairs_fill(const char* name, bool bits, const void* X, int Nx, const void* Y, int Ny, int L, int metric,
+                          const void* plan, int P, int n_diag, int max_tiles, unsigned char* dirs, size_t dirs_bytes,
+                          double* last_row, size_t last_n, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int max_t = cdiv(DTW_MAX_N, DT_TI);
+    if (Nx < 1 || Ny < 1 || L < 1 || L > DTW_MAX_L || metric < 0 || metric > 2 || P < 1 || P > DTW_MAX_P || n_diag < 1 ||
+        n_diag > 2 * max_t - 1 || max_tiles < 1 || max_tiles > max_t)
+        return fail(RBVAE_E_UNSUPPORTED,
+                    "%s: (Nx=%d, Ny=%d, L=%d, metric=%d, P=%d, n_diag=%d, max_tiles=%d) outside 1 <= Nx, Ny, 1 <= L <= %d, "
+                    "metric 0..2, 1 <= P <= %d, 1 <= n_diag <= %d, 1 <= max_tiles <= %d",
+                    name, Nx, Ny, L, metric, P, n_diag, max_tiles, DTW_MAX_L, DTW_MAX_P, 2 * max_t - 1, max_t);
+    if (!bits && metric == 2)
+        return fail(RBVAE_E_UNSUPPORTED, "%s: metric=2 (hamming) takes packed codes: rbvae_dtw_pairs_fill_bits", name);
+    RBVAE_CHECK_ARG(X && Y && plan && dirs && last_row && ws, "%s: null pointer", name);
+    RBVAE_CHECK_ARG(dirs_bytes >= 1 && last_n >= 1 && ws_bytes >= sizeof(double), "%s: an output of no bytes", name);
+    const DtwExt ext{Nx, Ny, (long)dirs_bytes, (long)last_n, (long)(ws_bytes / sizeof(double)), 0};
+    double* w = (double*)ws;
+    for (int d = 0; d < n_diag; ++d) {
+        const dim3 grid(d + 1 < max_tiles ? d + 1 : max_tiles, P);      // no pair has more tiles on diagonal d
+        if (bits)
+            hipLaunchKernelGGL((dtw_tile_k<true, true>), grid, dim3(DT_THREADS), 0, st, X, Y, 0, 0, L, 0, -1, 0, d, 0, 0, w,
+                               (double*)nullptr, (double*)nullptr, dirs, last_row, (double*)nullptr, (const long*)plan, ext);
+        else
+            hipLaunchKernelGGL((dtw_tile_k<false, true>), grid, dim3(DT_THREADS), 0, st, X, Y, 0, 0, L, metric == 1, -1, 0, d, 0,
+                               0, w, (double*)nullptr, (double*)nullptr, dirs, last_row, (double*)nullptr, (const long*)plan, ext);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(RBVAE_E_LAUNCH, "%s (tile anti-diagonal %d): %s", name, d, hipGetErrorString(e));
     }
@@ -448,8 +645,121 @@ extern "C" int rbvae_dtw_trace(const unsigned char* dirs, const double* last_row
     DTW_CHECK_SHAPE("dtw_trace");
     RBVAE_CHECK_ARG(dirs && last_row && path && state && cost, "dtw_trace: null pointer");
     RBVAE_CHECK_ARG(((uintptr_t)path & 7) == 0, "dtw_trace: path must be 8-byte aligned");
-    hipLaunchKernelGGL(dtw_trace_k, dim3(1), dim3(DT_THREADS), 0, (hipStream_t)stream, dirs, last_row, N, M, subsequence, path,
-                       state, cost);
+    hipLaunchKernelGGL(dtw_trace_k<false>, dim3(1), dim3(DT_THREADS), 0, (hipStream_t)stream, dirs, last_row, N, M, subsequence,
+                       path, state, cost, (const long*)nullptr, DtwExt{});
     RBVAE_CHECK_LAUNCH("dtw_trace");
+    return RBVAE_OK;
+}
+
+// ---- many pairs: two stacks and a pair list ---------------------------------------------------------------------------------------
+
+#define DTW_CHECK_PAIRS(name)                                                                                                  \
+    do {                                                                                                                      \
+        RBVAE_CHECK_ARG(len_x && len_y && pairs, name ": null pointer");                                                      \
+        if (const char* why = dtw_pairs_why(len_x, Sx, len_y, Sy, pairs, P, L, metric))                                       \
+            return fail(RBVAE_E_UNSUPPORTED, name ": %s", why);                                                               \
+    } while (0)
+
+extern "C" int rbvae_dtw_pairs_ok(const int* len_x, int Sx, const int* len_y, int Sy, const int* pairs, int P, int L,
+                                  int metric) {
+    return len_x && len_y && pairs && !dtw_pairs_why(len_x, Sx, len_y, Sy, pairs, P, L, metric) ? 1 : 0;
+}
+
+extern "C" int rbvae_dtw_pairs_sizes(const int* len_x, int Sx, const int* len_y, int Sy, const int* pairs, int P,
+                                     int64_t* dirs_off, int64_t* last_off, int64_t* ws_off, int64_t* path_off, size_t* totals) {
+    const int L = 1, metric = 0;
+    DTW_CHECK_PAIRS("dtw_pairs_sizes");
+    RBVAE_CHECK_ARG(dirs_off && last_off && ws_off && path_off && totals, "dtw_pairs_sizes: null pointer");
+    dtw_pairs_offsets(len_x, len_y, pairs, P, dirs_off, last_off, ws_off, path_off);
+    totals[0] = (size_t)dirs_off[P], totals[1] = (size_t)last_off[P], totals[2] = (size_t)ws_off[P], totals[3] = (size_t)path_off[P];
+    return RBVAE_OK;
+}
+
+extern "C" size_t rbvae_dtw_pairs_plan_bytes(int P) {
+    if (P < 1 || P > DTW_MAX_P) return 0;
+    return (DP_HDR + (size_t)P * DP_ROW) * sizeof(int64_t);
+}
+
+extern "C" int rbvae_dtw_pairs_plan(const int* len_x, int Sx, const int* len_y, int Sy, const int* pairs, int P, void* plan_dev,
+                                    size_t plan_bytes, int* launch, void* stream) {
+    const int L = 1, metric = 0;
+    DTW_CHECK_PAIRS("dtw_pairs_plan");
+    RBVAE_CHECK_ARG(plan_dev && launch, "dtw_pairs_plan: null pointer");
+    const size_t need = rbvae_dtw_pairs_plan_bytes(P);
+    RBVAE_CHECK_ARG(plan_bytes >= need, "dtw_pairs_plan: plan of %zu bytes, %zu needed", plan_bytes, need);
+    std::vector<int64_t> row_x(Sx + 1, 0), row_y(Sy + 1, 0), off[4];
+    for (int s = 0; s < Sx; ++s) row_x[s + 1] = row_x[s] + len_x[s];
+    for (int s = 0; s < Sy; ++s) row_y[s + 1] = row_y[s] + len_y[s];
+    for (auto& o : off) o.resize(P + 1);
+    dtw_pairs_offsets(len_x, len_y, pairs, P, off[0].data(), off[1].data(), off[2].data(), off[3].data());
+    std::vector<int64_t> h(need / sizeof(int64_t), 0);
+    h[0] = P, h[1] = row_x[Sx], h[2] = row_y[Sy];
+    int n_diag = 0, max_tiles = 0;
+    for (int p = 0; p < P; ++p) {
+        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        const int nTi = cdiv(len_x[a], DT_TI), nTj = cdiv(len_y[b], DT_TJ);
+        int64_t* r = h.data() + DP_HDR + (size_t)p * DP_ROW;
+        r[DP_X0] = row_x[a], r[DP_Y0] = row_y[b], r[DP_N] = len_x[a], r[DP_M] = len_y[b], r[DP_NTI] = nTi, r[DP_NTJ] = nTj;
+        r[DP_DIRS] = off[0][p], r[DP_LAST] = off[1][p], r[DP_WS] = off[2][p] / (int64_t)sizeof(double), r[DP_PATH] = off[3][p];
+        n_diag = nTi + nTj - 1 > n_diag ? nTi + nTj - 1 : n_diag;
+        max_tiles = (nTi < nTj ? nTi : nTj) > max_tiles ? (nTi < nTj ? nTi : nTj) : max_tiles;
+    }
+    // the host copy lives until the transfer has been taken: the stream is waited for (once per batch, not per launch)
+    hipError_t err = hipMemcpyAsync(plan_dev, h.data(), need, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
+    if (err != hipSuccess) return fail(RBVAE_E_LAUNCH, "dtw_pairs_plan: %s", hipGetErrorString(err));
+    launch[0] = n_diag, launch[1] = max_tiles;
+    return RBVAE_OK;
+}
+
+extern "C" int rbvae_dtw_pairs_fill(const float* X, int Nx, const float* Y, int Ny, int L, int metric, const void* plan, int P,
+                                    int n_diag, int max_tiles, unsigned char* dirs, size_t dirs_bytes, double* last_row,
+                                    size_t last_n, void* ws, size_t ws_bytes, void* stream) {
+    return dtw_pairs_fill("dtw_pairs_fill", false, X, Nx, Y, Ny, L, metric, plan, P, n_diag, max_tiles, dirs, dirs_bytes, last_row,
+                          last_n, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int rbvae_dtw_pairs_fill_bits(const uint32_t* xbits, int Nx, const uint32_t* ybits, int Ny, int L, const void* plan,
+                                         int P, int n_diag, int max_tiles, unsigned char* dirs, size_t dirs_bytes,
+                                         double* last_row, size_t last_n, void* ws, size_t ws_bytes, void* stream) {
+    return dtw_pairs_fill("dtw_pairs_fill_bits", true, xbits, Nx, ybits, Ny, L, 2, plan, P, n_diag, max_tiles, dirs, dirs_bytes,
+                          last_row, last_n, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int rbvae_dtw_pairs_trace(const unsigned char* dirs, size_t dirs_bytes, const double* last_row, size_t last_n,
+                                     const void* plan, int P, int* path, size_t path_rows, int* state, double* cost,
+                                     void* stream) {
+    if (P < 1 || P > DTW_MAX_P) return fail(RBVAE_E_UNSUPPORTED, "dtw_pairs_trace: P=%d outside 1 <= P <= %d", P, DTW_MAX_P);
+    RBVAE_CHECK_ARG(dirs && last_row && plan && path && state && cost, "dtw_pairs_trace: null pointer");
+    RBVAE_CHECK_ARG(dirs_bytes >= 1 && last_n >= 1 && path_rows >= 1, "dtw_pairs_trace: an array of no bytes");
+    RBVAE_CHECK_ARG(((uintptr_t)path & 7) == 0, "dtw_pairs_trace: path must be 8-byte aligned");
+    const DtwExt ext{DTW_MAX_N, DTW_MAX_N, (long)dirs_bytes, (long)last_n, 0, (long)path_rows};
+    hipLaunchKernelGGL(dtw_trace_k<true>, dim3(P), dim3(DT_THREADS), 0, (hipStream_t)stream, dirs, last_row, 0, 0, 0, path, state,
+                       cost, (const long*)plan, ext);
+    RBVAE_CHECK_LAUNCH("dtw_pairs_trace");
+    return RBVAE_OK;
+}
+
+extern "C" int rbvae_dtw_path_ranges(const int* path, const int* state, int n, int m, int* lo, int* hi, void* stream) {
+    if (!dtw_ok(n, m, 1, 0, -1, 0))
+        return fail(RBVAE_E_UNSUPPORTED, "dtw_path_ranges: (n=%d, m=%d) outside 1 <= n, m <= %d", n, m, DTW_MAX_N);
+    RBVAE_CHECK_ARG(path && state && lo && hi, "dtw_path_ranges: null pointer");
+    hipLaunchKernelGGL(dtw_ranges_k, dim3(cdiv(n + m - 1, DT_THREADS)), dim3(DT_THREADS), 0, (hipStream_t)stream, path, state, n, m,
+                       lo, hi);
+    RBVAE_CHECK_LAUNCH("dtw_path_ranges");
+    return RBVAE_OK;
+}
+
+extern "C" int rbvae_dtw_barycenter_update(const float* Y, int Ny, int L, const void* plan, int P, const int* lo, const int* hi,
+                                           int T, float* out, int* count, void* stream) {
+    if (Ny < 1 || L < 1 || L > DTW_MAX_L || P < 1 || P > DTW_MAX_P || T < 1 || T > DTW_MAX_N)
+        return fail(RBVAE_E_UNSUPPORTED,
+                    "dtw_barycenter_update: (Ny=%d, L=%d, P=%d, T=%d) outside 1 <= Ny, 1 <= L <= %d, 1 <= P <= %d, 1 <= T <= %d",
+                    Ny, L, P, T, DTW_MAX_L, DTW_MAX_P, DTW_MAX_N);
+    RBVAE_CHECK_ARG(Y && plan && lo && hi && out && count, "dtw_barycenter_update: null pointer");
+    const DtwExt ext{T, Ny, 0, 0, 0, 0};
+    hipLaunchKernelGGL(dtw_bary_update_k, dim3(cdiv((long)T * L, DT_THREADS)), dim3(DT_THREADS), 0, (hipStream_t)stream, Y,
+                       (const long*)plan, ext, P, L, T, lo, hi, out, count);
+    RBVAE_CHECK_LAUNCH("dtw_barycenter_update");
     return RBVAE_OK;
 }

@@ -490,7 +490,7 @@ using namespace rbvae;
 
 extern "C" {
 
-int rbvae_version(void) { return 110; }
+int rbvae_version(void) { return 111; }
 
 __global__ void counter_add_k(unsigned long long* c, unsigned long long inc) { c[0] += inc; }
 int rbvae_counter_add(unsigned long long* counter, unsigned long long inc, void* stream) {
