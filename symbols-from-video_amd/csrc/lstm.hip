@@ -9,7 +9,7 @@
 //
 // Weight block layout (= the reference's registration order, per layer):
 //   w_ih [4L][L], w_hh [4L][L], b_ih [4L], b_hh [4L]      -> 8*L*L + 8*L floats per layer
-#include "mma.h"
+#include "lstm_steps.h"
 #include <stdlib.h>
 
 // Wave priority of the latency-bound kernels that share the chip with full-grid GEMMs on the side stream (the LSTM
@@ -26,7 +26,6 @@
 
 namespace rbvae {
 
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 int lstm_unit_threads = 1;       // 0: the gate-row kernels also at L == 32 (rbvae_dbg_lstm_unit_threads: identity tests, A/B timing)
 
 __device__ __forceinline__ long lstm_layer_floats(int L) { return 8l * L * L + 8l * L; }
@@ -187,14 +186,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_k(const float* __restrict__ wblk
 // d - l at diagonal d.  The dependent chain shrinks from layers*T cells to T + layers - 1 steps,
 // barriers wait on LDS only (global stores of the saved state stay in flight).
 // ---------------------------------------------------------------------------------------------
-// sigmoid / tanh on the hardware exp2 and reciprocal (about 1 ulp each): the wavefront kernels sit on a
-// short dependent chain where the library expf/tanhf sequences would dominate.
-__device__ __forceinline__ float fast_sigmoid(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
-__device__ __forceinline__ float fast_tanh(float x) {
-    return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)) - 1.0f;
-}
+// (fast_sigmoid / fast_tanh and every step these kernels share: lstm_steps.h)
 
 // ---------------------------------------------------------------------------------------------
 // 32 < L <= 128 (the reference's sweeps and best models use latent_dim 50 / 75 / 100): one workgroup per sequence,
@@ -315,8 +307,9 @@ __global__ __launch_bounds__(512) void lstm_fwd_big_k(const float* __restrict__ 
             if (tid < L) {
                 const float ig = gates[tid], fg = gates[L + tid], gg = gates[2 * L + tid], og = gates[3 * L + tid];
                 const float hp = hcur[tid];
-                c = fmaf(fg, c, ig * gg);
-                const float h = og * fast_tanh(c);
+                const LstmCell cell = lstm_cell(ig, fg, gg, og, c);
+                c = cell.c;
+                const float h = cell.h;
                 if (acts) {
                     cs[o * L + tid] = c;
                     hprev[o * L + tid] = hp;
@@ -396,6 +389,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_big_k(const float* __restrict__ 
             }
             if (tid < L) {
                 const int u = tid;
+                // lstm_gate_grad's expressions, typed out: with the helper the <16> listing changes
                 const float tc = fast_tanh(c);
                 const float dh = dhout[t * BIG_VS + u] + dhrec[u];
                 const float dc = dc_next + dh * og * (1.f - tc * tc);
@@ -460,15 +454,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_wave_k(const float* __restrict_
     } else {
         for (int i = threadIdx.x; i < T * L; i += blockDim.x) hbuf[i] = hs_all[((long)s * T) * L + i];
     }
-    if (cast_out) {
-        // padding columns [L, cast_ld) of this sequence's rows of the cast copy (the consumer GEMM reads whole
-        // 128-byte K slices)
-        const int pw = cast_ld - L;
-        for (int i = threadIdx.x; i < T * pw; i += blockDim.x) {
-            const long o = ((long)s * T + i / pw) * cast_ld + L + i % pw;
-            if (cast_bf16) ((bf16_t*)cast_out)[o] = 0; else ((float*)cast_out)[o] = 0.f;
-        }
-    }
+    if (cast_out) lstm_cast_pad(cast_out, cast_bf16, cast_ld, s, T, L);
     const float* wl = wblk + l * lstm_layer_floats(L);
     float wih[LMAX], whh[LMAX];
     float bsum = 0.f;
@@ -527,8 +513,9 @@ __global__ __launch_bounds__(1024) void lstm_fwd_wave_k(const float* __restrict_
             const float* gl = gates + l * 4 * L;
             const float ig = gl[j], fg = gl[L + j], gg = gl[2 * L + j], og = gl[3 * L + j];
             const float hp = t > 0 ? hbuf[((l + 1) * T + t - 1) * L + j] : 0.f;
-            c = fmaf(fg, c, ig * gg);        // explicit: the same rounding in every kernel that runs this cell
-            const float h = og * fast_tanh(c);
+            const LstmCell cell = lstm_cell(ig, fg, gg, og, c);
+            c = cell.c;
+            const float h = cell.h;
             hbuf[((l + 1) * T + t) * L + j] = h;
             const long o = (((long)l * S + s) * T + t);
             if (acts) {
@@ -539,7 +526,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_wave_k(const float* __restrict_
             if (cast_out && l == layers - 1) {
                 // the top layer's output again in the next GEMM's operand type (what rbvae_cast_pad would make of it)
                 const long o = ((long)s * T + t) * cast_ld + j;
-                if (cast_bf16) ((bf16_t*)cast_out)[o] = f32_to_bf16(h); else ((float*)cast_out)[o] = h;
+                lstm_cast_store(cast_out, cast_bf16, o, h);
             }
         }
         lds_barrier();
@@ -594,7 +581,8 @@ __global__ __launch_bounds__(1024) void lstm_pair_fwd_k(const PairArgs p) {
     float* acts = stack ? p.acts_d : p.acts_e;
     float* cs = stack ? p.cs_d : p.cs_e;
     float* hb = hbuf + stack * (layers + 1) * T * LS;    // this stack's slots
-    // this thread's weight rows first: their loads are in flight while the input is staged
+    // this thread's weight rows first: their loads are in flight while the input is staged (the loads of
+    // lstm_fwd_wave_k, typed out again: as a helper every forward listing changed and the launches were slower)
     const float* wblk = stack ? p.wblk_d : p.wblk_e;
     const float* wT = stack ? p.wT_d : p.wT_e;
     const float* wl = wblk + l * lstm_layer_floats(L);
@@ -643,13 +631,7 @@ __global__ __launch_bounds__(1024) void lstm_pair_fwd_k(const PairArgs p) {
         const float u = p.U ? uin : (float)(hash_u32(seed, (unsigned long long)o) >> 8) * (1.0f / 16777216.0f);
         nbuf[li] = p.ratio * (logf(u + p.neps) - logf(1.0f - u + p.neps));
     }
-    if (p.cast_out) {
-        const int pw = p.cast_ld - L;
-        for (int i = threadIdx.x; i < T * pw; i += blockDim.x) {
-            const long o = ((long)s * T + i / pw) * p.cast_ld + L + i % pw;
-            if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = 0; else ((float*)p.cast_out)[o] = 0.f;
-        }
-    }
+    if (p.cast_out) lstm_cast_pad(p.cast_out, p.cast_bf16, p.cast_ld, s, T, L);
     float c = 0.f;
     // every slot but the encoder input is read (times a zero factor) before it is written: keep them finite
     // (and the padding of the input rows: read by the last 16-byte chunk of a dot product)
@@ -688,8 +670,9 @@ __global__ __launch_bounds__(1024) void lstm_pair_fwd_k(const PairArgs p) {
             const float* gl = gates + q * 4 * L;
             const float ig = gl[j], fg = gl[L + j], gg = gl[2 * L + j], og = gl[3 * L + j];
             const float hpv = t > 0 ? hb[((l + 1) * T + t - 1) * LS + j] : 0.f;
-            c = fmaf(fg, c, ig * gg);        // explicit: the same rounding in every kernel that runs this cell
-            const float h = og * fast_tanh(c);
+            const LstmCell cell = lstm_cell(ig, fg, gg, og, c);
+            c = cell.c;
+            const float h = cell.h;
             hb[((l + 1) * T + t) * LS + j] = h;
             const long o = (((long)l * S + s) * T + t);
             if (acts) {
@@ -700,15 +683,14 @@ __global__ __launch_bounds__(1024) void lstm_pair_fwd_k(const PairArgs p) {
             if (q == layers - 1) {
                 // binary_concrete_logits on the encoder's output (percep_RBVAE_model.py:17-44): z feeds the decoder stack
                 const long e = ((long)s * T + t) * L + j;
-                const float y = sigmoidf_((h + nbuf[t * LS + j]) / inv_tau_src);
-                const float zz = p.hard ? (y > 0.5f ? 1.0f : 0.0f) : y;
-                p.y_soft[e] = y;
-                p.hs_d[e] = zz;
-                hbuf[(layers + 1) * T * LS + t * LS + j] = zz;        // decoder stack, slot 0
+                const LstmCode code = lstm_binarise(h, nbuf[t * LS + j], inv_tau_src, p.hard);
+                p.y_soft[e] = code.y;
+                p.hs_d[e] = code.z;
+                hbuf[(layers + 1) * T * LS + t * LS + j] = code.z;        // decoder stack, slot 0
             }
             if (p.cast_out && q == 2 * layers - 1) {
                 const long oc = ((long)s * T + t) * p.cast_ld + j;
-                if (p.cast_bf16) ((bf16_t*)p.cast_out)[oc] = f32_to_bf16(h); else ((float*)p.cast_out)[oc] = h;
+                lstm_cast_store(p.cast_out, p.cast_bf16, oc, h);
             }
         }
         lds_barrier();
@@ -762,6 +744,7 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
     const float* wblk = stack ? p.wblk_d : p.wblk_e;
     const float* wT = stack ? p.wT_d : p.wT_e;
     const float* wl = wblk + l * lstm_layer_floats(L);
+    // the weight loads of lstm_pair_fwd_k for this lane's two gate rows (L == LMAX: nothing to clamp)
     float wih[2][L], whh[2][L], bsum[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -773,6 +756,8 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
 #pragma unroll
         for (int k = 0; k < L; ++k) { wih[g][k] = pi[k * kstride]; whh[g][k] = ph[k * kstride]; }
     }
+    // the input staging of lstm_pair_fwd_k, typed out again with LS == L (as a helper one scalar branch of each
+    // listing changes, and the timing check cannot tell that from a rebuild); keep the two alike
     for (int i = threadIdx.x; i < T * L; i += blockDim.x) {
         const long o = ((long)s * T) * L + i;
         const bool parts = p.in_parts != nullptr;
@@ -796,13 +781,7 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
         const float u = p.U ? uin : (float)(hash_u32(seed, (unsigned long long)o) >> 8) * (1.0f / 16777216.0f);
         nbuf[i] = p.ratio * (logf(u + p.neps) - logf(1.0f - u + p.neps));
     }
-    if (p.cast_out) {
-        const int pw = p.cast_ld - L;
-        for (int i = threadIdx.x; i < T * pw; i += blockDim.x) {
-            const long o = ((long)s * T + i / pw) * p.cast_ld + L + i % pw;
-            if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = 0; else ((float*)p.cast_out)[o] = 0.f;
-        }
-    }
+    if (p.cast_out) lstm_cast_pad(p.cast_out, p.cast_bf16, p.cast_ld, s, T, L);
     float c = 0.f;
     for (int i = threadIdx.x; i < 2 * (layers + 1) * T * LS; i += blockDim.x)
         if (i >= T * LS) hbuf[i] = 0.f;
@@ -853,8 +832,9 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
             if (hf == 0) {
                 const float ig = av[0], fg = av[1];
                 const float hpv = t > 0 ? hp[j] : 0.f;
-                c = fmaf(fg, c, ig * gg);        // explicit: the same rounding in every kernel that runs this cell
-                const float h = og * fast_tanh(c);
+                const LstmCell cell = lstm_cell(ig, fg, gg, og, c);
+                c = cell.c;
+                const float h = cell.h;
                 hb[((l + 1) * T + t) * LS + j] = h;
                 if (acts) {
                     cs[o * L + j] = c;
@@ -863,21 +843,20 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
                 hs_all[(((long)(l + 1) * S + s) * T + t) * L + j] = h;
                 if (q == layers - 1) {
                     const long e = ((long)s * T + t) * L + j;
-                    const float y = sigmoidf_((h + nbuf[t * LS + j]) / inv_tau_src);
-                    const float zz = p.hard ? (y > 0.5f ? 1.0f : 0.0f) : y;
-                    p.y_soft[e] = y;
-                    p.hs_d[e] = zz;
-                    hbuf[(layers + 1) * T * LS + t * LS + j] = zz;        // decoder stack, slot 0
+                    const LstmCode code = lstm_binarise(h, nbuf[t * LS + j], inv_tau_src, p.hard);
+                    p.y_soft[e] = code.y;
+                    p.hs_d[e] = code.z;
+                    hbuf[(layers + 1) * T * LS + t * LS + j] = code.z;        // decoder stack, slot 0
                 }
                 if (p.cast_out && q == 2 * layers - 1) {
                     const long oc = ((long)s * T + t) * p.cast_ld + j;
-                    if (p.cast_bf16) ((bf16_t*)p.cast_out)[oc] = f32_to_bf16(h); else ((float*)p.cast_out)[oc] = h;
+                    lstm_cast_store(p.cast_out, p.cast_bf16, oc, h);
                 }
             }
         }
         lds_barrier();
     }
-    if (p.kl_parts) {
+    if (p.kl_parts) {           // the KL tail of lstm_pair_fwd_k with LS == L
         float a = 0.f;
         for (int i = threadIdx.x; i < T * L; i += blockDim.x)
             a += kl_elem(hbuf[(layers + 1) * T * LS + i], p.lp, p.l1p, p.keps, p.clamp);
@@ -946,9 +925,10 @@ __global__ __launch_bounds__(1024) void lstm_bwd_wave_k(const float* __restrict_
                 const float hsv = bb.g_hs ? bb.g_hs[e] : 0.f;
                 float gg = g;
                 if (bb.klw != 0.f) gg += bb.klw * kl_elem_grad(zv, bb.lp, bb.l1p, bb.keps, bb.clamp);
-                gt = hsv + gg * yv * (1.0f - yv) / bin_tau;
+                gt = lstm_seam_bwd(gg, yv, hsv, bin_tau);
             } else {
-                // plain, or K-split slabs (rbvae_skinny_linear_parts) summed in slab order, four loads in flight
+                // plain, or K-split slabs (rbvae_skinny_linear_parts) summed in slab order, four loads in flight; the
+                // same sum is typed out in the prologues of lstm_pair_bwd_k and lstm_pair_bwd_unit_k
                 const float* gp = g_top + e;
                 gt = gp[0];
                 int q = 1;
@@ -974,26 +954,10 @@ __global__ __launch_bounds__(1024) void lstm_bwd_wave_k(const float* __restrict_
             sm[base] = ((in_acts ? acts : cs) + (((long)ll * S + s) * T) * (in_acts ? 4 * L : L))[r];
         }
     }
-    if (cast_out) {
-        const int pw = cast_ld - L;
-        for (int i = threadIdx.x; i < T * pw; i += blockDim.x) {
-            const long o = ((long)s * T + i / pw) * cast_ld + L + i % pw;
-            if (cast_bf16) ((bf16_t*)cast_out)[o] = 0; else ((float*)cast_out)[o] = 0.f;
-        }
-    }
+    if (cast_out) lstm_cast_pad(cast_out, cast_bf16, cast_ld, s, T, L);
     const float* wl = wblk + l * lstm_layer_floats(L);
     float wic[LMAX], whc[LMAX];
-    if (row) {
-        const float* pi = wl + prt * L * L + kcol;
-        const float* ph = pi + 4 * L * L;
-#pragma unroll
-        for (int jj = 0; jj < LMAX; ++jj) {
-            const int o = (jj < L ? jj : L - 1) * L;
-            const float a = pi[o], b = ph[o];
-            wic[jj] = jj < L ? a : 0.f;
-            whc[jj] = jj < L ? b : 0.f;
-        }
-    }
+    if (row) lstm_load_gate_cols<LMAX>(wic, whc, wl, L, prt, kcol);
     float dc_next = 0.f;
     float dx_sum = 0.f;                  // layer 0, j < L: sum over t of this sequence's input gradient (dx_colsum)
     __syncthreads();
@@ -1004,7 +968,9 @@ __global__ __launch_bounds__(1024) void lstm_bwd_wave_k(const float* __restrict_
         const int t = T - 1 - q;
         const bool active = q >= 0 && q < T;
         if (j < L) {
-            // layer 0: the input gradient of the step finished at the previous diagonal (time t+1)
+            // layer 0: the input gradient of the step finished at the previous diagonal (time t+1).  A dx row -- block sums
+            // in block order, store, dx_sum, cast copy -- is typed out at each of its five sites in the backward kernels:
+            // as a helper (with or without the block sums) the gate-row listings change.  Keep the sites alike.
             if (l == 0 && q >= 1 && q <= T) {
                 const float* p0 = part;
                 const float dv = p0[0 * L + j] + p0[2 * L + j] + p0[4 * L + j] + p0[6 * L + j];
@@ -1012,7 +978,7 @@ __global__ __launch_bounds__(1024) void lstm_bwd_wave_k(const float* __restrict_
                 dx_sum += dv;
                 if (cast_out) {
                     const long o = ((long)s * T + t + 1) * cast_ld + j;
-                    if (cast_bf16) ((bf16_t*)cast_out)[o] = f32_to_bf16(dv); else ((float*)cast_out)[o] = dv;
+                    lstm_cast_store(cast_out, cast_bf16, o, dv);
                 }
             }
             if (active) {
@@ -1030,21 +996,19 @@ __global__ __launch_bounds__(1024) void lstm_bwd_wave_k(const float* __restrict_
                 const float ig = ap[j], fg = ap[L + j], gg = ap[2 * L + j], og = ap[3 * L + j];
                 const float c = scs[(l * T + t) * L + j];
                 const float cprev = t > 0 ? scs[(l * T + t - 1) * L + j] : 0.f;
-                const float tc = fast_tanh(c);
-                const float dc = dc_next + dh * og * (1.f - tc * tc);
-                const float d_o = dh * tc * og * (1.f - og);
-                const float d_i = dc * gg * ig * (1.f - ig);
-                const float d_f = dc * cprev * fg * (1.f - fg);
-                const float d_g = dc * ig * (1.f - gg * gg);
-                dc_next = dc * fg;
+                const LstmGateGrad gr = lstm_gate_grad(ig, fg, gg, og, c, cprev, dh, dc_next);
+                const float d_i = gr.d_i, d_f = gr.d_f, d_g = gr.d_g, d_o = gr.d_o;
+                dc_next = gr.dc_next;
                 float* dl = dg + l * 4 * L;
-                dl[j] = d_i; dl[L + j] = d_f; dl[2 * L + j] = d_g; dl[3 * L + j] = d_o;
+                lstm_store_gates(dl, L, j, d_i, d_f, d_g, d_o);
                 float* gp = dG + (((long)l * S + s) * T + t) * 4 * L;
-                gp[j] = d_i; gp[L + j] = d_f; gp[2 * L + j] = d_g; gp[3 * L + j] = d_o;
+                lstm_store_gates(gp, L, j, d_i, d_f, d_g, d_o);
             }
         }
         lds_barrier();
         if (active && row) {
+            // two chains per product (even / odd rows); typed out here and in lstm_pair_bwd_k, keep them alike: as a
+            // helper the <32, false> listings of both change
             float ax0 = 0.f, ax1 = 0.f, ah0 = 0.f, ah1 = 0.f;
             const float* dgp = dg + l * 4 * L + prt * L;
 #pragma unroll
@@ -1069,7 +1033,7 @@ __global__ __launch_bounds__(1024) void lstm_bwd_wave_k(const float* __restrict_
         dx_sum += dv;
         if (cast_out) {
             const long o = ((long)s * T) * cast_ld + j;
-            if (cast_bf16) ((bf16_t*)cast_out)[o] = f32_to_bf16(dv); else ((float*)cast_out)[o] = dv;
+            lstm_cast_store(cast_out, cast_bf16, o, dv);
         }
         // per-sequence column sums of dx: the bias gradient of the Linear that feeds this stack, minus one launch
         if (dx_colsum) dx_colsum[(long)s * L + j] = dx_sum;
@@ -1116,7 +1080,8 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
     const bool row = j < 4 * L;
     const int kcol = j % L, prt = j / L;
     {
-        // every global load of the prologue in flight before the first use (see lstm_bwd_wave_k)
+        // every global load of the prologue in flight before the first use (see lstm_bwd_wave_k); the same text in
+        // lstm_pair_bwd_k and lstm_pair_bwd_unit_k: as a helper taking the fields by value it slowed lstm_pair_bwd_k
         constexpr int U = 12;
         const int n0 = T * L, na = T * 4 * L, n1 = VL * na, ntot = n1 + VL * n0;
         const int nth = blockDim.x;
@@ -1172,26 +1137,10 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
             sacts[i] = base[(((long)ll * S + s) * T) * (in_acts ? 4 * L : L) + r];
         }
     }
-    if (p.cast_out) {
-        const int pw = p.cast_ld - L;
-        for (int i = threadIdx.x; i < T * pw; i += blockDim.x) {
-            const long o = ((long)s * T + i / pw) * p.cast_ld + L + i % pw;
-            if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = 0; else ((float*)p.cast_out)[o] = 0.f;
-        }
-    }
+    if (p.cast_out) lstm_cast_pad(p.cast_out, p.cast_bf16, p.cast_ld, s, T, L);
     const float* wl = (dec ? p.wblk_d : p.wblk_e) + l * lstm_layer_floats(L);
     float wic[LMAX], whc[LMAX];
-    if (row) {
-        const float* pi = wl + prt * L * L + kcol;
-        const float* ph = pi + 4 * L * L;
-#pragma unroll
-        for (int jj = 0; jj < LMAX; ++jj) {
-            const int o = (jj < L ? jj : L - 1) * L;
-            const float a = pi[o], b = ph[o];
-            wic[jj] = jj < L ? a : 0.f;
-            whc[jj] = jj < L ? b : 0.f;
-        }
-    }
+    if (row) lstm_load_gate_cols<LMAX>(wic, whc, wl, L, prt, kcol);
     float dc_next = 0.f;
     float dx_sum = 0.f;
     float* dG = dec ? p.dG_d : p.dG_e;
@@ -1203,7 +1152,8 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
         const int t = T - 1 - q;
         const bool active = q >= 0 && q < T;
         if (j < L) {
-            // encoder layer 0: the input gradient of the step finished at the previous diagonal (time t+1)
+            // encoder layer 0: the input gradient of the step finished at the previous diagonal (time t+1); the dx row as
+            // lstm_bwd_wave_k types it out
             if (vl == 0 && q >= 1 && q <= T) {
                 const float* p0 = part;
                 const float dv = p0[0 * L + j] + p0[2 * L + j] + p0[4 * L + j] + p0[6 * L + j];
@@ -1211,7 +1161,7 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
                 dx_sum += dv;
                 if (p.cast_out) {
                     const long o = ((long)s * T + t + 1) * p.cast_ld + j;
-                    if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = f32_to_bf16(dv); else ((float*)p.cast_out)[o] = dv;
+                    lstm_cast_store(p.cast_out, p.cast_bf16, o, dv);
                 }
             }
             if (active) {
@@ -1225,8 +1175,7 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
                         if (p.dz) p.dz[((long)s * T + t) * L + j] = dh;
                         float gg = p.gz_extra ? dh + sx[t * L + j] : dh;
                         if (bb.klw != 0.f) gg += bb.klw * sk[t * L + j];
-                        const float yv = sy[t * L + j];
-                        dh = sh[t * L + j] + gg * yv * (1.0f - yv) / bin_tau;
+                        dh = lstm_seam_bwd(gg, sy[t * L + j], sh[t * L + j], bin_tau);
                     }
                 }
                 if (q > 0) {
@@ -1237,21 +1186,18 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
                 const float ig = ap[j], fg = ap[L + j], gg = ap[2 * L + j], og = ap[3 * L + j];
                 const float c = scs[(vl * T + t) * L + j];
                 const float cprev = t > 0 ? scs[(vl * T + t - 1) * L + j] : 0.f;
-                const float tc = fast_tanh(c);
-                const float dc = dc_next + dh * og * (1.f - tc * tc);
-                const float d_o = dh * tc * og * (1.f - og);
-                const float d_i = dc * gg * ig * (1.f - ig);
-                const float d_f = dc * cprev * fg * (1.f - fg);
-                const float d_g = dc * ig * (1.f - gg * gg);
-                dc_next = dc * fg;
+                const LstmGateGrad gr = lstm_gate_grad(ig, fg, gg, og, c, cprev, dh, dc_next);
+                const float d_i = gr.d_i, d_f = gr.d_f, d_g = gr.d_g, d_o = gr.d_o;
+                dc_next = gr.dc_next;
                 float* dl = dg + vl * 4 * L;
-                dl[j] = d_i; dl[L + j] = d_f; dl[2 * L + j] = d_g; dl[3 * L + j] = d_o;
+                lstm_store_gates(dl, L, j, d_i, d_f, d_g, d_o);
                 float* gp = dG + (((long)l * S + s) * T + t) * 4 * L;
-                gp[j] = d_i; gp[L + j] = d_f; gp[2 * L + j] = d_g; gp[3 * L + j] = d_o;
+                lstm_store_gates(gp, L, j, d_i, d_f, d_g, d_o);
             }
         }
         lds_barrier();
         if (active && row) {
+            // the transposed product of lstm_bwd_wave_k, typed out again (as a helper the <32, false> listings change)
             float ax0 = 0.f, ax1 = 0.f, ah0 = 0.f, ah1 = 0.f;
             const float* dgp = dg + vl * 4 * L + prt * L;
 #pragma unroll
@@ -1276,7 +1222,7 @@ __global__ __launch_bounds__(1024) void lstm_pair_bwd_k(const PairBwdArgs p) {
         dx_sum += dv;
         if (p.cast_out) {
             const long o = ((long)s * T) * p.cast_ld + j;
-            if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = f32_to_bf16(dv); else ((float*)p.cast_out)[o] = dv;
+            lstm_cast_store(p.cast_out, p.cast_bf16, o, dv);
         }
         if (p.dx_colsum) p.dx_colsum[(long)s * L + j] = dx_sum;
     }
@@ -1311,7 +1257,8 @@ __global__ __launch_bounds__(512) void lstm_pair_bwd_unit_k(const PairBwdArgs p)
     const int l = dec ? vl - layers : vl;
     const int s = blockIdx.x;
     {
-        // every global load of the prologue in flight before the first use (see lstm_bwd_wave_k)
+        // every global load of the prologue in flight before the first use (see lstm_bwd_wave_k); the same text in
+        // lstm_pair_bwd_k and lstm_pair_bwd_unit_k: as a helper taking the fields by value it slowed lstm_pair_bwd_k
         constexpr int U = 12;
         const int n0 = T * L, na = T * 4 * L, n1 = VL * na, ntot = n1 + VL * n0;
         const int nth = blockDim.x;
@@ -1367,22 +1314,11 @@ __global__ __launch_bounds__(512) void lstm_pair_bwd_unit_k(const PairBwdArgs p)
             sacts[i] = base[(((long)ll * S + s) * T) * (in_acts ? 4 * L : L) + r];
         }
     }
-    if (p.cast_out) {
-        const int pw = p.cast_ld - L;
-        for (int i = threadIdx.x; i < T * pw; i += blockDim.x) {
-            const long o = ((long)s * T + i / pw) * p.cast_ld + L + i % pw;
-            if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = 0; else ((float*)p.cast_out)[o] = 0.f;
-        }
-    }
+    if (p.cast_out) lstm_cast_pad(p.cast_out, p.cast_bf16, p.cast_ld, s, T, L);
     const float* wl = (dec ? p.wblk_d : p.wblk_e) + l * lstm_layer_floats(L);
     float wic[2][L], whc[2][L];
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const float* pi = wl + (2 * hf + g) * L * L + j;
-        const float* ph = pi + 4 * L * L;
-#pragma unroll
-        for (int jj = 0; jj < L; ++jj) { wic[g][jj] = pi[jj * L]; whc[g][jj] = ph[jj * L]; }
-    }
+    for (int g = 0; g < 2; ++g) lstm_load_gate_cols<L>(wic[g], whc[g], wl, L, 2 * hf + g, j);
     float dc_next = 0.f, dx_sum = 0.f, dh_rec = 0.f;
     float* dG = dec ? p.dG_d : p.dG_e;
     __syncthreads();
@@ -1403,8 +1339,7 @@ __global__ __launch_bounds__(512) void lstm_pair_bwd_unit_k(const PairBwdArgs p)
                         if (p.dz) p.dz[((long)s * T + t) * L + j] = dh;
                         float gg = p.gz_extra ? dh + sx[t * L + j] : dh;
                         if (bb.klw != 0.f) gg += bb.klw * sk[t * L + j];
-                        const float yv = sy[t * L + j];
-                        dh = sh[t * L + j] + gg * yv * (1.0f - yv) / bin_tau;
+                        dh = lstm_seam_bwd(gg, sy[t * L + j], sh[t * L + j], bin_tau);
                     }
                 }
                 if (q > 0) dh += dh_rec;
@@ -1412,16 +1347,12 @@ __global__ __launch_bounds__(512) void lstm_pair_bwd_unit_k(const PairBwdArgs p)
                 const float ig = ap[j], fg = ap[L + j], gg = ap[2 * L + j], og = ap[3 * L + j];
                 const float c = scs[(vl * T + t) * L + j];
                 const float cprev = t > 0 ? scs[(vl * T + t - 1) * L + j] : 0.f;
-                const float tc = fast_tanh(c);
-                const float dc = dc_next + dh * og * (1.f - tc * tc);
-                const float d_o = dh * tc * og * (1.f - og);
-                const float d_i = dc * gg * ig * (1.f - ig);
-                const float d_f = dc * cprev * fg * (1.f - fg);
-                const float d_g = dc * ig * (1.f - gg * gg);
-                dc_next = dc * fg;
-                dl[j] = d_i; dl[L + j] = d_f; dl[2 * L + j] = d_g; dl[3 * L + j] = d_o;
+                const LstmGateGrad gr = lstm_gate_grad(ig, fg, gg, og, c, cprev, dh, dc_next);
+                const float d_i = gr.d_i, d_f = gr.d_f, d_g = gr.d_g, d_o = gr.d_o;
+                dc_next = gr.dc_next;
+                lstm_store_gates(dl, L, j, d_i, d_f, d_g, d_o);
                 float* gp = dG + (((long)l * S + s) * T + t) * 4 * L;
-                gp[j] = d_i; gp[L + j] = d_f; gp[2 * L + j] = d_g; gp[3 * L + j] = d_o;
+                lstm_store_gates(gp, L, j, d_i, d_f, d_g, d_o);
             }
             // the wave's own gate gradients back from LDS (same wave: in issue order behind the writes above)
             const float* dgp = dl + 2 * hf * L;
@@ -1457,7 +1388,7 @@ __global__ __launch_bounds__(512) void lstm_pair_bwd_unit_k(const PairBwdArgs p)
                     dx_sum += dxv;
                     if (p.cast_out) {
                         const long o = ((long)s * T + t) * p.cast_ld + j;
-                        if (p.cast_bf16) ((bf16_t*)p.cast_out)[o] = f32_to_bf16(dxv); else ((float*)p.cast_out)[o] = dxv;
+                        lstm_cast_store(p.cast_out, p.cast_bf16, o, dxv);
                     }
                 }
             }
@@ -1542,39 +1473,80 @@ using namespace rbvae;
 
 extern "C" {
 
+// threads of one layer's group: a gate row each, in whole waves
+static int lstm_group_threads(int L) { return ((4 * L + 63) / 64) * 64; }
+
+// LDS bytes of the wavefront kernels, as their LDS layouts spell them out; the _ok functions and the launchers ask these
+static size_t fwd_wave_lds(int T, int L, int layers) {
+    return ((size_t)(layers + 1) * T * L + (size_t)layers * 4 * L) * sizeof(float);
+}
+static size_t bwd_wave_lds(int T, int L, int layers) {
+    return ((size_t)T * L + (size_t)layers * T * 5 * L + (size_t)layers * 12 * L) * sizeof(float);
+}
+static size_t pair_fwd_lds(int T, int L, int layers) {
+    const int LS = (L + 3) & ~3;
+    return (size_t)(2 * (layers + 1) * T * LS + 2 * layers * 4 * L + T * LS + 16) * sizeof(float);
+}
+static size_t pair_bwd_lds(int T, int L, int layers) {
+    return (size_t)(5 * T * L + 2 * layers * (T * 5 * L + 12 * L)) * sizeof(float);
+}
+
+// Argument checks that several entry points share (`who` starts the message).  The pair forward launch words its
+// tau / kl_p check differently (one message for both, kl_p only with kl_parts) and keeps it.
+#define LSTM_CHECK_CAST(who) \
+    RBVAE_CHECK_ARG(!cast_out || ((cast_dtype == RBVAE_F32 || cast_dtype == RBVAE_BF16) && cast_ld >= L), \
+                    who ": cast output dtype %d ld %d", cast_dtype, cast_ld)
+#define LSTM_CHECK_KL_P(who) \
+    RBVAE_CHECK_ARG(kl_weight == 0.f || (kl_p > 0.f && kl_p < 1.f), who ": kl_p=%g outside (0,1)", kl_p)
+
+// lstm_fwd_big_k / lstm_bwd_big_k are instantiated for these dot-product lengths (16-byte chunks): LAUNCH(N) with the
+// smallest N >= nch
+#define LSTM_BIG_DISPATCH(LAUNCH, nch) \
+    do { \
+        if (nch <= 10) LAUNCH(10); else if (nch <= 13) LAUNCH(13); else if (nch <= 16) LAUNCH(16); \
+        else if (nch <= 19) LAUNCH(19); else if (nch <= 22) LAUNCH(22); else if (nch <= 25) LAUNCH(25); \
+        else if (nch <= 28) LAUNCH(28); else LAUNCH(32); \
+    } while (0)
+
+// the binarise backward's arguments as the kernels take them (gz: null where the gradient of the codes never leaves the chip)
+static BinBwd bin_bwd_args(const float* gz, const float* y_soft, const float* z, const float* g_hs, float tau,
+                           const float* tau_dev, float kl_weight, float kl_p, float kl_eps, int kl_clamp, int S, int T) {
+    BinBwd bb;
+    bb.gz = gz; bb.y = y_soft; bb.z = z; bb.g_hs = g_hs; bb.tau = tau; bb.tau_dev = tau_dev;
+    bb.klw = kl_weight / (float)((long)S * T);
+    bb.lp = kl_weight != 0.f ? logf(kl_p) : 0.f; bb.l1p = kl_weight != 0.f ? logf(1.0f - kl_p) : 0.f;
+    bb.keps = kl_eps; bb.clamp = kl_clamp; bb.on = 1;
+    return bb;
+}
+
 // The wavefront kernels' own range: one thread group per layer and the whole sequence's state in LDS.  The dispatchers
 // below and the callers that want the slab / cast / binarise epilogues (which only these kernels have) ask the same
 // two functions.
 int rbvae_lstm_fwd_wave_ok(int T, int L, int layers) {
     if (T <= 0 || L <= 0 || layers <= 0 || L > 32) return 0;
-    const int threads = ((4 * L + 63) / 64) * 64;
-    const size_t wlds = ((size_t)(layers + 1) * T * L + (size_t)layers * 4 * L) * sizeof(float);
-    return (long)layers * threads <= 1024 && wlds <= 64 * 1024;
+    return (long)layers * lstm_group_threads(L) <= 1024 && fwd_wave_lds(T, L, layers) <= 64 * 1024;
 }
 
 int rbvae_lstm_bwd_wave_ok(int T, int L, int layers) {
     if (T <= 0 || L <= 0 || layers <= 0 || L > 32) return 0;
-    const int threads = ((4 * L + 63) / 64) * 64;
-    const size_t wlds = ((size_t)T * L + (size_t)layers * T * 5 * L + (size_t)layers * 12 * L) * sizeof(float);
-    return (long)layers * threads <= 1024 && wlds <= 64 * 1024;
+    return (long)layers * lstm_group_threads(L) <= 1024 && bwd_wave_lds(T, L, layers) <= 64 * 1024;
 }
 
 static int lstm_fwd_impl(const float* wblk, const float* wT, float* hs_all, float* hprev, float* acts, float* cs, int S,
                          int T, int L, int layers, const float* in_parts, int nparts, long part_stride, void* cast_out,
                          int cast_dtype, int cast_ld, void* stream) {
     RBVAE_CHECK_ARG(wblk && hs_all && S > 0 && T > 0 && L > 0 && layers > 0, "lstm_fwd: bad arguments");
-    RBVAE_CHECK_ARG(!cast_out || ((cast_dtype == RBVAE_F32 || cast_dtype == RBVAE_BF16) && cast_ld >= L),
-                    "lstm_fwd: cast output dtype %d ld %d", cast_dtype, cast_ld);
+    LSTM_CHECK_CAST("lstm_fwd");
     const int cast_bf16 = cast_dtype == RBVAE_BF16;
     RBVAE_CHECK_ARG(L <= 128, "lstm_fwd: latent_dim %d > 128 is not supported", L);
     RBVAE_CHECK_ARG((acts == nullptr) == (cs == nullptr) && (acts == nullptr) == (hprev == nullptr),
                     "lstm_fwd: hprev/acts/cs must be given together");
-    const int threads = ((4 * L + 63) / 64) * 64;
+    const int threads = lstm_group_threads(L);
     const size_t lds = (size_t)(2 * T * L + 5 * L) * sizeof(float);
     RBVAE_CHECK_ARG(lds <= 64 * 1024, "lstm_fwd: T*L=%d too large", T * L);
     hipStream_t st = (hipStream_t)stream;
     // wavefront kernel: one thread group per layer (weights in registers, L <= 32)
-    const size_t wlds = (size_t)((layers + 1) * T * L + layers * 4 * L) * sizeof(float);
+    const size_t wlds = fwd_wave_lds(T, L, layers);
     if (rbvae_lstm_fwd_wave_ok(T, L, layers)) {
         if (L == 32)
             hipLaunchKernelGGL((lstm_fwd_wave_k<32, true, true>), dim3(S), dim3(layers * threads), wlds, st, wblk, wT,
@@ -1594,15 +1566,13 @@ static int lstm_fwd_impl(const float* wblk, const float* wT, float* hs_all, floa
     RBVAE_CHECK_ARG(!in_parts && !cast_out, "lstm_fwd_ex: only the wavefront kernel (rbvae_lstm_fwd_wave_ok) sums input slabs / writes a cast copy");
     if (L > 32) {
         // two lanes per gate row, the input half batched over time (lstm_fwd_big_k)
-        const int RP = ((4 * L + 63) / 64) * 64;
+        const int RP = lstm_group_threads(L);
         const size_t blds = (size_t)((2 * T + 1) * BIG_VS + RP + T * RP) * sizeof(float);
         RBVAE_CHECK_ARG(blds <= 64 * 1024, "lstm_fwd: T=%d too long for L=%d", T, L);
         const int nch = (L + 3) / 4;                              // 16-byte chunks of a weight row
 #define FWD_BIG(N) hipLaunchKernelGGL(lstm_fwd_big_k<N>, dim3(S), dim3(RP), blds, st, wblk, wT, hs_all, hprev, acts, cs, \
                                       S, T, L, layers, RP)
-        if (nch <= 10) FWD_BIG(10); else if (nch <= 13) FWD_BIG(13); else if (nch <= 16) FWD_BIG(16);
-        else if (nch <= 19) FWD_BIG(19); else if (nch <= 22) FWD_BIG(22); else if (nch <= 25) FWD_BIG(25);
-        else if (nch <= 28) FWD_BIG(28); else FWD_BIG(32);
+        LSTM_BIG_DISPATCH(FWD_BIG, nch);
 #undef FWD_BIG
         RBVAE_CHECK_LAUNCH("lstm_fwd_big");
         return RBVAE_OK;
@@ -1627,10 +1597,7 @@ int rbvae_lstm_fwd_ex(const float* wblk, const float* wT, float* hs_all, float* 
 }
 
 int rbvae_lstm_pair_fwd_ok(int T, int L, int layers) {
-    const int threads = ((4 * L + 63) / 64) * 64;
-    const int LS = (L + 3) & ~3;
-    const size_t lds = (size_t)(2 * (layers + 1) * T * LS + 2 * layers * 4 * L + T * LS + 16) * sizeof(float);
-    return L <= 32 && 2 * layers * threads <= 1024 && lds <= 64 * 1024;
+    return L <= 32 && 2 * layers * lstm_group_threads(L) <= 1024 && pair_fwd_lds(T, L, layers) <= 64 * 1024;
 }
 
 int rbvae_lstm_pair_fwd(const float* wblk_enc, const float* wT_enc, const float* wblk_dec, const float* wT_dec,
@@ -1649,8 +1616,7 @@ int rbvae_lstm_pair_fwd(const float* wblk_enc, const float* wT_enc, const float*
                     (hprev_dec == nullptr) == (acts_enc == nullptr), "lstm_pair_fwd: saved-state buffers must be given together");
     RBVAE_CHECK_ARG((tau_dev || tau > 0.f) && (!kl_parts || (kl_p > 0.f && kl_p < 1.f)), "lstm_pair_fwd: tau=%g kl_p=%g", tau, kl_p);
     RBVAE_CHECK_ARG(!in_parts || (nparts >= 1 && part_stride >= (long)S * T * L), "lstm_pair_fwd: bad slabs");
-    RBVAE_CHECK_ARG(!cast_out || ((cast_dtype == RBVAE_F32 || cast_dtype == RBVAE_BF16) && cast_ld >= L),
-                    "lstm_pair_fwd: cast output dtype %d ld %d", cast_dtype, cast_ld);
+    LSTM_CHECK_CAST("lstm_pair_fwd");
     PairArgs a;
     a.wblk_e = wblk_enc; a.wT_e = wT_enc; a.wblk_d = wblk_dec; a.wT_d = wT_dec;
     a.hs_e = hs_enc; a.hp_e = hprev_enc; a.acts_e = acts_enc; a.cs_e = cs_enc;
@@ -1661,10 +1627,10 @@ int rbvae_lstm_pair_fwd(const float* wblk_enc, const float* wT_enc, const float*
     a.l1p = kl_parts ? logf(1.0f - kl_p) : 0.f; a.keps = kl_eps; a.hard = hard; a.clamp = kl_clamp;
     a.seed = seed; a.seed_dev = seed_dev;
     a.cast_out = cast_out; a.cast_bf16 = cast_dtype == RBVAE_BF16; a.cast_ld = cast_ld;
-    const int threads = ((4 * L + 63) / 64) * 64;
+    const int threads = lstm_group_threads(L);
     a.S = S; a.T = T; a.L = L; a.layers = layers; a.G = threads;
     const int LS = (L + 3) & ~3;
-    const size_t lds = (size_t)(2 * (layers + 1) * T * LS + 2 * layers * 4 * L + T * LS + 16) * sizeof(float);
+    const size_t lds = pair_fwd_lds(T, L, layers);
     if (L == 32 && 2 * layers * 64 <= 512 && lstm_unit_threads)
         hipLaunchKernelGGL(lstm_pair_fwd_unit_k, dim3(S), dim3(2 * layers * 64), lds, (hipStream_t)stream, a);
     else if (L == 32)
@@ -1682,15 +1648,14 @@ static int lstm_bwd_impl(const float* wblk, const float* wT, const float* acts, 
                          int cast_ld, float* dx_colsum, const BinBwd& bb, void* stream) {
     RBVAE_CHECK_ARG(wblk && acts && cs && g_top && dG && dx && S > 0 && T > 0 && L > 0 && layers > 0,
                     "lstm_bwd: bad arguments");
-    RBVAE_CHECK_ARG(!cast_out || ((cast_dtype == RBVAE_F32 || cast_dtype == RBVAE_BF16) && cast_ld >= L),
-                    "lstm_bwd: cast output dtype %d ld %d", cast_dtype, cast_ld);
+    LSTM_CHECK_CAST("lstm_bwd");
     const int cast_bf16 = cast_dtype == RBVAE_BF16;
     RBVAE_CHECK_ARG(L <= 128, "lstm_bwd: latent_dim %d > 128 is not supported", L);
-    const int threads = ((4 * L + 63) / 64) * 64;
+    const int threads = lstm_group_threads(L);
     const size_t lds = (size_t)(2 * T * L + 13 * L) * sizeof(float);
     RBVAE_CHECK_ARG(lds <= 64 * 1024, "lstm_bwd: T*L=%d too large", T * L);
     hipStream_t st = (hipStream_t)stream;
-    const size_t wlds = (size_t)(T * L + layers * T * 5 * L + layers * 12 * L) * sizeof(float);
+    const size_t wlds = bwd_wave_lds(T, L, layers);
     if (rbvae_lstm_bwd_wave_ok(T, L, layers)) {
         if (L == 32)
             hipLaunchKernelGGL((lstm_bwd_wave_k<32, true>), dim3(S), dim3(layers * threads), wlds, st, wblk, acts, cs,
@@ -1711,9 +1676,7 @@ static int lstm_bwd_impl(const float* wblk, const float* wT, const float* acts, 
         const int nch = (L + 3) / 4;                              // 16-byte chunks of a lane's gate rows
 #define BWD_BIG(N) hipLaunchKernelGGL(lstm_bwd_big_k<N>, dim3(S), dim3(4 * KP), blds, st, wblk, wT, acts, cs, g_top, dG, \
                                       dx, S, T, L, layers)
-        if (nch <= 10) BWD_BIG(10); else if (nch <= 13) BWD_BIG(13); else if (nch <= 16) BWD_BIG(16);
-        else if (nch <= 19) BWD_BIG(19); else if (nch <= 22) BWD_BIG(22); else if (nch <= 25) BWD_BIG(25);
-        else if (nch <= 28) BWD_BIG(28); else BWD_BIG(32);
+        LSTM_BIG_DISPATCH(BWD_BIG, nch);
 #undef BWD_BIG
         RBVAE_CHECK_LAUNCH("lstm_bwd_big");
         return RBVAE_OK;
@@ -1742,23 +1705,14 @@ int rbvae_lstm_bwd_bin(const float* wblk, const float* acts, const float* cs, co
                        float kl_eps, int kl_clamp, float* dG, float* dx, void* cast_out, int cast_dtype, int cast_ld, float* dx_colsum,
                        int S, int T, int L, int layers, void* stream) {
     RBVAE_CHECK_ARG(g_z && y_soft && z && (tau_dev || tau > 0.f), "lstm_bwd_bin: bad arguments");
-    RBVAE_CHECK_ARG(kl_weight == 0.f || (kl_p > 0.f && kl_p < 1.f), "lstm_bwd_bin: kl_p=%g outside (0,1)", kl_p);
-    BinBwd bb;
-    bb.gz = g_z; bb.y = y_soft; bb.z = z; bb.g_hs = g_hs; bb.tau = tau; bb.tau_dev = tau_dev;
-    bb.klw = kl_weight / (float)((long)S * T);
-    bb.lp = kl_weight != 0.f ? logf(kl_p) : 0.f; bb.l1p = kl_weight != 0.f ? logf(1.0f - kl_p) : 0.f;
-    bb.keps = kl_eps; bb.clamp = kl_clamp; bb.on = 1;
+    LSTM_CHECK_KL_P("lstm_bwd_bin");
+    const BinBwd bb = bin_bwd_args(g_z, y_soft, z, g_hs, tau, tau_dev, kl_weight, kl_p, kl_eps, kl_clamp, S, T);
     return lstm_bwd_impl(wblk, nullptr, acts, cs, g_z, dG, dx, S, T, L, layers, 1, 0, cast_out, cast_dtype, cast_ld, dx_colsum, bb,
                          stream);
 }
 
-static size_t pair_bwd_lds(int T, int L, int layers) {
-    return (size_t)(5 * T * L + 2 * layers * (T * 5 * L + 12 * L)) * sizeof(float);
-}
-
 int rbvae_lstm_pair_bwd_ok(int T, int L, int layers) {
-    const int threads = ((4 * L + 63) / 64) * 64;
-    return L <= 32 && 2 * layers * threads <= 1024 && pair_bwd_lds(T, L, layers) <= 64 * 1024;
+    return L <= 32 && 2 * layers * lstm_group_threads(L) <= 1024 && pair_bwd_lds(T, L, layers) <= 64 * 1024;
 }
 
 int rbvae_lstm_pair_bwd(const float* wblk_enc, const float* wblk_dec, const float* acts_enc, const float* cs_enc,
@@ -1773,19 +1727,15 @@ int rbvae_lstm_pair_bwd(const float* wblk_enc, const float* wblk_dec, const floa
                     "range (rbvae_lstm_pair_bwd_ok)", T, L, layers);
     RBVAE_CHECK_ARG(nparts >= 1 && (nparts == 1 || part_stride >= (long)S * T * L), "lstm_pair_bwd: bad slabs");
     RBVAE_CHECK_ARG(tau_dev || tau > 0.f, "lstm_pair_bwd: tau=%g", tau);
-    RBVAE_CHECK_ARG(kl_weight == 0.f || (kl_p > 0.f && kl_p < 1.f), "lstm_pair_bwd: kl_p=%g outside (0,1)", kl_p);
-    RBVAE_CHECK_ARG(!cast_out || ((cast_dtype == RBVAE_F32 || cast_dtype == RBVAE_BF16) && cast_ld >= L),
-                    "lstm_pair_bwd: cast output dtype %d ld %d", cast_dtype, cast_ld);
+    LSTM_CHECK_KL_P("lstm_pair_bwd");
+    LSTM_CHECK_CAST("lstm_pair_bwd");
     PairBwdArgs a;
     a.wblk_e = wblk_enc; a.wblk_d = wblk_dec; a.acts_e = acts_enc; a.cs_e = cs_enc; a.acts_d = acts_dec; a.cs_d = cs_dec;
     a.g_top = g_top_parts; a.nparts = nparts; a.part_stride = part_stride;
     a.dG_e = dG_enc; a.dG_d = dG_dec; a.dx = dx; a.dz = dz; a.gz_extra = gz_extra;
     a.cast_out = cast_out; a.cast_bf16 = cast_dtype == RBVAE_BF16; a.cast_ld = cast_ld; a.dx_colsum = dx_colsum;
-    a.bb.gz = nullptr; a.bb.y = y_soft; a.bb.z = z; a.bb.g_hs = g_hs; a.bb.tau = tau; a.bb.tau_dev = tau_dev;
-    a.bb.klw = kl_weight / (float)((long)S * T);
-    a.bb.lp = kl_weight != 0.f ? logf(kl_p) : 0.f; a.bb.l1p = kl_weight != 0.f ? logf(1.0f - kl_p) : 0.f;
-    a.bb.keps = kl_eps; a.bb.clamp = kl_clamp; a.bb.on = 1;
-    const int threads = ((4 * L + 63) / 64) * 64;
+    a.bb = bin_bwd_args(nullptr, y_soft, z, g_hs, tau, tau_dev, kl_weight, kl_p, kl_eps, kl_clamp, S, T);
+    const int threads = lstm_group_threads(L);
     a.S = S; a.T = T; a.L = L; a.layers = layers; a.G = threads;
     const size_t lds = pair_bwd_lds(T, L, layers);
     if (L == 32 && 2 * layers * 64 <= 512 && lstm_unit_threads)

@@ -542,7 +542,7 @@ def test_lstm_pair_forward_equals_three_launches(sfv, L, layers, S, T, hard):
 
 @pytest.mark.parametrize("layers,S,T,hard,use_wT,nparts", [(4, 5, 8, 0, True, 3), (2, 3, 5, 1, False, 1), (4, 2, 1, 0, True, 1), (3, 4, 11, 0, False, 5)])
 def test_lstm_pair_forward_unit_threads_bit_identical(sfv, layers, S, T, hard, use_wT, nparts):
-    """lstm_pair_fwd_unit_k (L == 32: one thread per hidden unit holds its four gate rows, one barrier per diagonal)
+    """lstm_pair_fwd_unit_k (L == 32: one wave per layer, a lane holds two gate rows of its unit, one barrier per diagonal)
     against lstm_pair_fwd_k (one thread per gate row), selected through rbvae_dbg_lstm_unit_threads: the same
     accumulator chains and expressions, so EVERY output is bit for bit the same -- saved activations, cell states, codes,
     the bf16 cast of the decoder's top layer, the per-sequence KL sums -- also from K-split input slabs, with device noise."""
@@ -586,18 +586,9 @@ def test_lstm_pair_forward_unit_threads_bit_identical(sfv, layers, S, T, hard, u
     assert torch.isfinite(outs[0][8]).all() and float(outs[0][4][layers].abs().max()) > 0
 
 
-@pytest.mark.parametrize("L,layers,S,T,nparts,klw,ghs,extra", [(32, 4, 5, 8, 4, 1.0, True, False), (32, 2, 3, 5, 1, 0.0, False, True),
-                                                              (25, 4, 3, 8, 3, 0.5, True, True), (7, 2, 2, 3, 1, 1.0, False, False),
-                                                              (30, 3, 2, 9, 2, 0.0, True, False),
-                                                              # L == 32: lstm_pair_bwd_unit_k (one wave per layer)
-                                                              (32, 3, 4, 11, 5, 0.5, True, True), (32, 4, 2, 1, 1, 1.0, False, False),
-                                                              (32, 1, 3, 4, 2, 0.0, False, True)])
-def test_lstm_pair_backward_equals_two_launches(sfv, L, layers, S, T, nparts, klw, ghs, extra):
-    """rbvae_lstm_pair_bwd (decoder stack -> binarise backward -> encoder stack, one wavefront) against
-    rbvae_lstm_bwd_ex(decoder) + rbvae_lstm_bwd_bin(encoder): gate gradients of both stacks, the input gradient, its cast
-    copy and per-sequence sums, and the codes' gradient -- the same expressions in the same order, so bit for bit."""
-    lib = sfv._lib
-    assert lib.query("rbvae_lstm_pair_bwd_ok", T, L, layers)
+def _pair_bwd_inputs(L, layers, S, T, nparts, ghs, extra):
+    """Operands of one BPTT launch over both stacks: weights, saved gates / cell states, the decoder top's gradient slabs,
+    y, z, and the optional g_hs / extra code gradient."""
     g = torch.Generator().manual_seed(70 + L + layers)
     N = S * T
     per = layers * (8 * L * L + 8 * L)
@@ -613,6 +604,23 @@ def test_lstm_pair_backward_equals_two_launches(sfv, L, layers, S, T, nparts, kl
     z = torch.rand(N, L, generator=g).clamp(1e-3, 1 - 1e-3).cuda()
     g_hs = torch.randn(N, L, generator=g).cuda() if ghs else None
     gzx = torch.randn(N, L, generator=g).cuda() if extra else None
+    return we, wd, ae, ce, ad, cd, gparts, y, z, g_hs, gzx
+
+
+@pytest.mark.parametrize("L,layers,S,T,nparts,klw,ghs,extra", [(32, 4, 5, 8, 4, 1.0, True, False), (32, 2, 3, 5, 1, 0.0, False, True),
+                                                              (25, 4, 3, 8, 3, 0.5, True, True), (7, 2, 2, 3, 1, 1.0, False, False),
+                                                              (30, 3, 2, 9, 2, 0.0, True, False),
+                                                              # L == 32: lstm_pair_bwd_unit_k (one wave per layer)
+                                                              (32, 3, 4, 11, 5, 0.5, True, True), (32, 4, 2, 1, 1, 1.0, False, False),
+                                                              (32, 1, 3, 4, 2, 0.0, False, True)])
+def test_lstm_pair_backward_equals_two_launches(sfv, L, layers, S, T, nparts, klw, ghs, extra):
+    """rbvae_lstm_pair_bwd (decoder stack -> binarise backward -> encoder stack, one wavefront) against
+    rbvae_lstm_bwd_ex(decoder) + rbvae_lstm_bwd_bin(encoder): gate gradients of both stacks, the input gradient, its cast
+    copy and per-sequence sums, and the codes' gradient -- the same expressions in the same order, so bit for bit."""
+    lib = sfv._lib
+    assert lib.query("rbvae_lstm_pair_bwd_ok", T, L, layers)
+    N = S * T
+    we, wd, ae, ce, ad, cd, gparts, y, z, g_hs, gzx = _pair_bwd_inputs(L, layers, S, T, nparts, ghs, extra)
     tau = torch.tensor([0.7], device="cuda")
     Lp = 64
     # two launches
@@ -639,6 +647,44 @@ def test_lstm_pair_backward_equals_two_launches(sfv, L, layers, S, T, nparts, kl
              torch.empty_like(dGe0), torch.empty_like(dGd0), dx2, None, None, 0, 0, None, S, T, L, layers)
     assert torch.equal(dx2, dx0)
     assert not lib.query("rbvae_lstm_pair_bwd_ok", 8, 64, 2) and not lib.query("rbvae_lstm_pair_bwd_ok", 64, 32, 4)
+
+
+@pytest.mark.parametrize("layers,S,T,nparts,klw,ghs,extra", [
+    (4, 2, 9, 4, 1.0, True, False),         # T = 9: the largest T the fused launch takes at four layers
+    (3, 4, 11, 5, 0.5, True, True),
+    (1, 3, 4, 2, 0.0, False, True),         # one layer per stack: the seam layer is also layer 0
+    (4, 2, 1, 1, 1.0, False, False)])       # T = 1: no recurrent term anywhere
+def test_lstm_pair_backward_unit_threads_bit_identical(sfv, layers, S, T, nparts, klw, ghs, extra):
+    """lstm_pair_bwd_unit_k (L == 32: one wave per virtual layer, a lane multiplies two gate blocks of its column) against
+    lstm_pair_bwd_k (one thread per gate row), selected through rbvae_dbg_lstm_unit_threads, on the inputs of
+    test_lstm_pair_backward_equals_two_launches: both run the same gate gradients, seam and block sums in the same order, so
+    dG of both stacks, dx, dz, the bf16 cast copy and the per-sequence column sums are bit for bit the same."""
+    L, Lp = 32, 64
+    lib = sfv._lib
+    assert lib.query("rbvae_lstm_pair_bwd_ok", T, L, layers)
+    if layers == 4:
+        assert not lib.query("rbvae_lstm_pair_bwd_ok", 10, L, layers)
+    N = S * T
+    we, wd, ae, ce, ad, cd, gparts, y, z, g_hs, gzx = _pair_bwd_inputs(L, layers, S, T, nparts, ghs, extra)
+    tau = torch.tensor([0.7], device="cuda")
+    dbg = lib.dbg_lib()
+    outs = []
+    for unit in (1, 0):
+        old = dbg.rbvae_dbg_lstm_unit_threads(unit)
+        try:
+            dGe, dGd = torch.empty(layers, S, T, 4 * L, device="cuda"), torch.empty(layers, S, T, 4 * L, device="cuda")
+            dx, dz = torch.empty(N, L, device="cuda"), torch.empty(N, L, device="cuda")
+            pad, sums = torch.full((N, Lp), 3.0, dtype=torch.bfloat16, device="cuda"), torch.empty(S, L, device="cuda")
+            lib.call("rbvae_lstm_pair_bwd", we, wd, ae, ce, ad, cd, gparts, nparts, N * L, gzx, y, z, g_hs, 9.0, tau, klw, 0.1, 1e-8,
+                     1, dGe, dGd, dx, dz, pad, 1, Lp, sums, S, T, L, layers)
+            torch.cuda.synchronize()
+            outs.append((dGe, dGd, dx, dz, pad, sums))
+        finally:
+            dbg.rbvae_dbg_lstm_unit_threads(old)
+    for nm, a, b in zip(("dG_enc", "dG_dec", "dx", "dz", "cast", "sums"), *outs):
+        assert torch.equal(a, b), (nm, (a.float() - b.float()).abs().max().item())
+    assert torch.isfinite(outs[0][2]).all() and float(outs[0][2].abs().max()) > 0
+    assert torch.equal(outs[0][4][:, L:], torch.zeros(N, Lp - L, dtype=torch.bfloat16, device="cuda"))
 
 
 @pytest.mark.parametrize("N,IH,IW,C1,Cout", [(3, 16, 16, 256, 4), (2, 11, 20, 256, 4), (2, 8, 8, 64, 3), (1, 5, 37, 128, 4)])

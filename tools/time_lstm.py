@@ -2,7 +2,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, sfv_amd as sfv
 L_ = sfv._lib
-S, T, L, layers = 32, 8, 32, 4
+S, T, L, layers = 32, 8, int(sys.argv[1]) if len(sys.argv) > 1 else 32, 4        # optional argument: another L <= 32
 def timeit(fn, iters=50):
     for _ in range(5): fn()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,12 +1,13 @@
 """rbvae_lstm_pair_fwd / rbvae_lstm_pair_bwd alone at the bench geometry (S sequences, L = 32, 4 + 4 layers) for several T: us per launch with one
 wave per layer (lstm_pair_fwd_unit_k) and one thread per gate row (lstm_pair_fwd_k); the slope over T is the cost of a
-diagonal, the intercept the prologue (weights into registers, input staging)."""
+diagonal, the intercept the prologue (weights into registers, input staging).  An argument gives another L <= 32: both
+columns then time the gate-row kernels' instance for that L (roundup4(L) == 28: the forward instance with LC = 28)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, sfv_amd as sfv
 Lb = sfv._lib
 dbg = Lb.dbg_lib()
-S, L, layers = 32, 32, 4
+S, L, layers = 32, int(sys.argv[1]) if len(sys.argv) > 1 else 32, 4
 def timeit(fn, iters=100):
     for _ in range(5): fn()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
