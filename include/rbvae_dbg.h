@@ -22,7 +22,8 @@ int rbvae_dbg_wr_stamps(unsigned long long* buf, void* stream);
  * slot k % 16 (its first 4 096 workgroups) */
 int rbvae_dbg_jobs_stamps(unsigned long long* buf, void* stream);
 /* librbvae_hip: which kernel rbvae_conv3x3_halo runs for bf16: 2 (default) the product dispatch -- the persistent kernel with
- * producer / MFMA wave roles (conv_halo_ws.hip) for layers of at most 256 input channels and at least 512 tiles, else the
+ * producer / MFMA wave roles (conv_halo_ws.hip) for launches of at least 512 tiles that it covers (ch_ws_covers: Kc a multiple
+ * of 64, Nout <= 512, every operand below 2 GiB, statistics groups whose size divides 64), else the
  * one-tile-per-workgroup kernel (conv_halo.hip); 1 the latter always; 0 the persistent kernel wherever it covers -- for the
  * bit-identity test and A/B timing; returns the previous value */
 int rbvae_dbg_conv_halo_variant(int v);

@@ -27,14 +27,6 @@
 
 namespace rbvae {
 
-// bytes of the staging buffers / epilogue tile + statistics scratch (the tables follow)
-template <typename T, int RING> constexpr int ch_lds_main() {
-    constexpr int ES = sizeof(T);
-    constexpr int ring = 2 * CH_ABUF + RING * CH_BBYTES;
-    constexpr int epi = CH_BM * (CH_BN * ES + 16);          // (the statistics scratch reuses the tile)
-    return ring > epi ? ring : epi;
-}
-
 // build-time ablation switches for timing-only builds (tools/ab_variants.sh; results are wrong with any bit set):
 // 1 no weight LDS-DMA in the loop, 2 no workgroup barrier in the loop, 4 no fragment reads in the loop, 8 no patch staging
 #ifndef CH_ABL
@@ -56,8 +48,7 @@ template <typename T, int RING, bool GN>
 __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     constexpr int ES = sizeof(T);
     constexpr int KE = 128 / ES, EC = 16 / ES;
-    constexpr int MT = 4, NTW = 4;
-    constexpr int LOADS = 2;                                  // weight LDS-DMA instructions per wave and step
+    constexpr int MT = CH_MT, NTW = CH_NTW, LOADS = CH_LOADS;
     constexpr int PITCH = CH_BN * ES + 16;
     constexpr int A_BYTES = 2 * CH_ABUF;
     constexpr int CPR = CH_BN / EC;              // 16-B chunks per tile row
@@ -75,12 +66,8 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // work item: the N tiles of one pixel tile run back to back on ONE XCD (they re-read the same patch from its L2), and
-    // an XCD walks a contiguous range of pixel tiles (neighbours share halo rows).  Bijective for any total.
-    int item;
-    {
-        const int lin = blockIdx.x, xcd = lin & 7, q = p.total >> 3, r = p.total & 7;
-        item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    }
+    // an XCD walks a contiguous range of pixel tiles (neighbours share halo rows)
+    const int item = xcd_item(blockIdx.x, p.total);
     const int mtile = item / p.ntn, ntile = item - mtile * p.ntn;
     const int per_img = p.tiles_r * p.tiles_c;
     const int n = mtile / per_img, trc = mtile - n * per_img;
@@ -92,7 +79,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
         const int oh = r0 + (tid >> 4), ow = c0 + (tid & 15);
         s_orow[tid] = (oh < p.OH && ow < p.OW) ? (n * p.OH + oh) * p.OW + ow : -1;
     }
-    if (tid < CH_NSLOT_PAD) {
+    if (tid < CH_NSLOT_PAD) {                      // (inline: mirrored by upconv_halo_k's slot table, dh0 = dw0 = -1)
         int v = -1;
         if (tid < CH_NSLOT) {
             const int pr = tid / CH_PW, pc = tid - pr * CH_PW;
@@ -109,8 +96,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     }
     __syncthreads();
 
-    // ---- input staging roles: piece i of this thread = (slot (tid>>3) + 64 i, chunk tid&7): 8 lanes read one pixel's
-    // 128-byte slice (coalesced), and write it to 8 chunk planes
+    // ---- input staging roles (conv_halo.h): piece i of this thread = (slot (tid>>3) + 64 i, chunk tid&7)
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const int chunk = tid & 7;
     const unsigned char* zsrc = p.zero + chunk * 16;
@@ -118,10 +104,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     // compiler-issued LDS read inside the loop waits lgkmcnt(0), i.e. for the fragment reads in flight around it
     int pixr[CH_NA];
 #pragma unroll
-    for (int i = 0; i < CH_NA; ++i) {
-        const int slot = (tid >> 3) + 64 * i;
-        pixr[i] = slot < CH_NSLOT_PAD ? s_pix[slot] : -2;
-    }
+    for (int i = 0; i < CH_NA; ++i) pixr[i] = ch_piece_pix(s_pix, tid, i);
     // (a runtime-indexed pick of pixr[i] becomes a scratch array: the staged steps rotate the six registers instead --
     // one full turn per slice, so every a_load sees them in order)
     // GroupNorm scale / shift of this thread's chunk for the slice being staged (loaded right behind a barrier)
@@ -137,26 +120,13 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             for (int e = 0; e < EC; ++e) asm volatile("" : "+v"(gsc[e]), "+v"(gsh[e]));   // landed HERE
         }
     };
-    // The six staged pieces of a slice: asm loads (the compiler would drain the weight tiles' LDS-DMA in front of a load
-    // of its own), destinations tied to the counted wait that covers them.  Loads, wait and uses all sit inside ONE
-    // unrolled slice body (taps 1, 3 and 3..8): a value that stayed in flight across the loop's back edge got copied by
-    // the compiler's phi moves right behind the load instruction, before its data had landed.  The build's ISA check
-    // proves that nothing touches a destination between its load and the wait.
+    // The six staged pieces of a slice (ch_piece_load, ch_a_landed).  Loads, wait and uses all sit inside ONE unrolled slice
+    // body (taps 1, 3 and 3..8): a value that stayed in flight across the loop's back edge got copied by the compiler's phi
+    // moves right behind the load instruction, before its data had landed.
     u32x4_t areg[CH_NA];
     auto a_load = [&](int kc) {
 #pragma unroll
-        for (int i = 0; i < CH_NA; ++i) {
-            const int pv = pixr[i];
-            const unsigned char* src = pv >= 0 ? p.A + ((size_t)pv * p.lda) * ES + (size_t)kc * 128 + chunk * 16 : zsrc;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(areg[i]) : "v"(src) : "memory");
-        }
-    };
-    // wait until at most YOUNGER vector-memory operations are outstanding: the six staged pieces have landed
-    auto a_landed = [](auto younger_tag, u32x4_t (&ar)[CH_NA]) {
-        constexpr int YOUNGER = decltype(younger_tag)::value;
-        asm volatile("s_waitcnt vmcnt(%6)"
-                     : "+v"(ar[0]), "+v"(ar[1]), "+v"(ar[2]), "+v"(ar[3]), "+v"(ar[4]), "+v"(ar[5])
-                     : "n"(YOUNGER));
+        for (int i = 0; i < CH_NA; ++i) areg[i] = ch_piece_load(ch_piece_src<ES>(p.A, pixr[i], p.lda, kc, chunk, zsrc));
     };
     // the producer's GroupNorm (+ swish) on one staged 16-byte piece of slice kc (padding pixels stay zero)
     auto gn_piece = [&](u32x4_t v, int kc, int pv) -> u32x4_t {
@@ -176,7 +146,8 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
         for (int q = 0; q < 4; ++q) t[q] = pv >= 0 ? t[q] : v[q];
         return t;
     };
-    // (asm store: a compiler-issued LDS store would first drain the weight tiles' LDS-DMA -- it cannot tell them apart)
+    // (asm store: a compiler-issued LDS store would first drain the weight tiles' LDS-DMA -- it cannot tell them apart; the
+    // address is inline: mirrored by upconv_halo_k's a_write and conv_halo_ws_k's piece)
     auto piece_write = [&](const u32x4_t& v, int buf, int i, int pv) {
         const unsigned dst = lds0 + (unsigned)buf * CH_ABUF + ch_plane_off(chunk) + (unsigned)((tid >> 3) + 64 * i) * 16;
         if (pv >= -1) asm volatile("ds_write_b128 %0, %1" ::"v"(dst), "v"(v) : "memory");
@@ -187,27 +158,19 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
         for (int i = 0; i < CH_NA; ++i) piece_write(gn_piece(areg[i], kc, pixr[i]), buf, i, pixr[i]);
     };
 
-    // ---- weight staging roles (LDS-DMA): instruction i of wave w moves rows (w*2+i)*8 .. +7 of the tap tile
+    // ---- weight staging roles (LDS-DMA, conv_halo.h): instruction i of wave w moves rows (w*2+i)*8 .. +7 of the tap tile
     static_assert(RING == 3, "the unrolled slice body relies on 9 taps % RING == 0 (static ring slots)");
     const int srow = lane >> 3, schunk = lane & 7;
-    // source = uniform base (tile, tap, slice: scalar registers) + a 32-bit per-lane offset (row, swizzled chunk): with
-    // per-tap 64-bit lane pointers the unrolled slice body kept 18 of them live and spilled
     unsigned blane[LOADS];
 #pragma unroll
-    for (int i = 0; i < LOADS; ++i) {
-        const int r = (w * LOADS + i) * 8 + srow;
-        blane[i] = (unsigned)(r * 9 * p.Kc) * ES + (unsigned)((schunk ^ ((r >> 1) & 7)) * 16);
-    }
+    for (int i = 0; i < LOADS; ++i) blane[i] = ch_blane<ES, 9>((w * LOADS + i) * 8 + srow, schunk, p.Kc);
     const unsigned char* wtile = p.W + ((size_t)n0 * 9 * p.Kc) * ES;
     const int nkc = p.Kc / KE;
     // weight tile of (slice kc, tap j) -> ring slot j % 3
     auto b_issue = [&](int kc, auto j_tag) {
         constexpr int j = decltype(j_tag)::value;
 #if !(CH_ABL & 1)
-        const unsigned char* src = wtile + ((size_t)j * p.Kc) * ES + (size_t)kc * 128;
-        unsigned char* lb = smem + A_BYTES + (j % RING) * CH_BBYTES + (w * LOADS) * 1024;
-#pragma unroll
-        for (int i = 0; i < LOADS; ++i) glds16(src + blane[i], lb + i * 1024);
+        ch_tile_issue(ch_tap_src<ES, j>(wtile, p.Kc, kc), blane, smem + A_BYTES + (j % RING) * CH_BBYTES + (w * LOADS) * 1024);
 #endif
     };
 
@@ -216,11 +179,9 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     const int wr = w >> 1, wc = w & 1;
     unsigned abase[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-        abase[mt] = lds0 + (unsigned)fg * CH_PLANE + (unsigned)(fg >> 1) * 32 + (unsigned)((wr * MT + mt) * CH_PW + fi) * 16;
+    for (int mt = 0; mt < MT; ++mt) abase[mt] = ch_aplane(lds0, fg) + (unsigned)((wr * MT + mt) * CH_PW + fi) * 16;
     const int fsw = (fi >> 1) & 7;
-    const unsigned offB0 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((0 + fg) ^ fsw) * 16);
-    const unsigned offB1 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((4 + fg) ^ fsw) * 16);
+    const unsigned offB0 = ch_boff(lds0, wc * NTW * 16 + fi, (0 + fg) ^ fsw), offB1 = ch_boff(lds0, wc * NTW * 16 + fi, (4 + fg) ^ fsw);
 
     f32x4_t acc[MT][NTW];
 #pragma unroll
@@ -228,37 +189,16 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    // One 32-k half of a step: MT + NTW fragment reads (inline asm, counted waits: see gather_gemm.hip) and MT x NTW
-    // MFMAs.  The tap and the ring slot are compile-time constants (the nine taps of a slice are unrolled): the tap's
-    // shift of the patch and the weight tile's slot are immediate offsets of the reads.
+    // One 32-k half of a step (ch_read_half, ch_landed, ch_mma_half).  The tap and the ring slot are compile-time constants
+    // (the nine taps of a slice are unrolled).
     unsigned ta[MT];                         // patch read addresses of the slice being read (buffer folded in)
     auto set_slice = [&](int kc) {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) ta[mt] = abase[mt] + (unsigned)((kc & 1) * CH_ABUF);
+        for (int mt = 0; mt < MT; ++mt) ta[mt] = ch_slice_addr(abase[mt], kc);
     };
     auto read_half = [&](auto j_tag, auto kk_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
         constexpr int j = decltype(j_tag)::value, kk = decltype(kk_tag)::value;
-        constexpr int aoff = kk * CH_KKOFF + ((j / 3) * CH_PW + (j % 3)) * 16;
-        constexpr int boff = (j % RING) * CH_BBYTES;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[mt]) : "v"(ta[mt]), "n"(aoff));
-        const unsigned ab_ = kk == 0 ? offB0 : offB1;
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[nt]) : "v"(ab_), "n"(boff + nt * 2048));
-    };
-    auto landed = [&](auto younger_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
-        constexpr int YOUNGER = decltype(younger_tag)::value;
-        asm volatile("s_waitcnt lgkmcnt(%8)"
-                     : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3])
-                     : "n"(YOUNGER));
-    };
-    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
+        ch_read_half<kk * CH_KKOFF + ((j / 3) * CH_PW + (j % 3)) * 16, (j % RING) * CH_BBYTES>(ta, kk == 0 ? offB0 : offB1, 0u, fa, fb);
     };
     // The same MFMA group with patch piece I of slice kcn riding in it: its GroupNorm + swish arithmetic fills the
     // vector-issue slots between the MFMAs (done as one block at the slice boundary it left the matrix pipe idle for
@@ -266,7 +206,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     auto mma_half_stage = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW], int kcn, auto i_tag) {
         constexpr int I = decltype(i_tag)::value;
         const u32x4_t v = gn_piece(areg[I], kcn, pixr[I]);
-        mma_half(fa, fb);
+        ch_mma_half<T>(acc, fa, fb);
         if constexpr (GN && ES == 2) {
 #pragma unroll
             for (int k = 0; k < MT * NTW; ++k) {
@@ -281,14 +221,12 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     };
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
-    using Younger = std::integral_constant<int, MT + NTW>;
-    using None = std::integral_constant<int, 0>;
 
     // ---- prologue: patch of slice 0, the first two weight tiles
     a_load(0);
     b_issue(0, std::integral_constant<int, 0>{});
     b_issue(0, std::integral_constant<int, 1>{});
-    a_landed(std::integral_constant<int, 0>{}, areg);
+    ch_a_landed<0>(areg);
     a_write(0, 0);
     ch_wait_barrier<0>();
     b_issue(0, std::integral_constant<int, 2>{});
@@ -309,14 +247,14 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             constexpr int nj = (j + 1) % 9;                  // tap of the next step
             using NJ = std::integral_constant<int, nj>;
             read_half(j_tag, K1{}, fa1, fb1);
-            landed(Younger{}, fa0, fb0);
+            ch_landed<MT + NTW>(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            mma_half(fa0, fb0);
+            ch_mma_half<T>(acc, fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            landed(None{}, fa1, fb1);
+            ch_landed<0>(fa1, fb1);
             if constexpr (j == 8 && !more) {                 // the very last step reads nothing ahead
                 __builtin_amdgcn_sched_barrier(0);
-                mma_half(fa1, fb1);
+                ch_mma_half<T>(acc, fa1, fb1);
             } else {
                 const int kn = j == 8 ? kc + 1 : kc;         // slice of the next step
                 // does a slice follow the NEXT step's slice?  (compile-time inside a slice; at the hand-over to the
@@ -334,7 +272,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
 #if !(CH_ABL & 8)
                 if constexpr (nj == 1 && more) a_load(kn + 1);
                 if constexpr (nj == 2 && more) gn_coeffs(kn + 1);
-                if constexpr (nj == 3 && more) a_landed(std::integral_constant<int, 2 * LOADS>{}, areg);   // behind them: the tiles of taps 4, 5
+                if constexpr (nj == 3 && more) ch_a_landed<2 * LOADS>(areg);   // behind them: the tiles of taps 4, 5
 #endif
                 if constexpr (nj == 0) set_slice(kn);
                 read_half(NJ{}, K0{}, fa0, fb0);
@@ -343,7 +281,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
                 if constexpr (nj >= 3 && nj < 3 + CH_NA && more) mma_half_stage(fa1, fb1, kn + 1, std::integral_constant<int, nj - 3>{});
                 else
 #endif
-                    mma_half(fa1, fb1);
+                    ch_mma_half<T>(acc, fa1, fb1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
@@ -371,12 +309,11 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             const int row = (wr * MT + mt) * 16 + fi;
             unsigned char* dst = tile + row * PITCH + cb * ES;
             if constexpr (ES == 4) {
-                *(float4*)dst = make_float4(acc[mt][nt][0] + bz[0], acc[mt][nt][1] + bz[1], acc[mt][nt][2] + bz[2],
-                                            acc[mt][nt][3] + bz[3]);
-            } else {
+                epi_stage<T>(dst, acc[mt][nt][0] + bz[0], acc[mt][nt][1] + bz[1], acc[mt][nt][2] + bz[2], acc[mt][nt][3] + bz[3]);
+            } else {                                       // (epi_stage's bf16 half changes the listings: ch_bias_pack2)
                 uint2 pk;
-                pk.x = (unsigned)f32_to_bf16(acc[mt][nt][0] + bz[0]) | ((unsigned)f32_to_bf16(acc[mt][nt][1] + bz[1]) << 16);
-                pk.y = (unsigned)f32_to_bf16(acc[mt][nt][2] + bz[2]) | ((unsigned)f32_to_bf16(acc[mt][nt][3] + bz[3]) << 16);
+                pk.x = ch_bias_pack2(acc[mt][nt][0], bz[0], acc[mt][nt][1], bz[1]);
+                pk.y = ch_bias_pack2(acc[mt][nt][2], bz[2], acc[mt][nt][3], bz[3]);
                 *(uint2*)dst = pk;
             }
         }
@@ -393,26 +330,27 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         orow_[it] = s_orow[it * RL + rl];
-        if (p.addend) av[it] = *(const u32x4_t*)(p.addend + ((size_t)(orow_[it] < 0 ? 0 : orow_[it]) * p.ldo + scol) * ES);
+        if (p.addend) av[it] = ch_addend_chunk<ES>(p.addend, orow_[it], p.ldo, scol);
     }
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int row = it * RL + rl;
         u32x4_t val = *(const u32x4_t*)(tile + row * PITCH + sch * 16);
-        if (p.addend) {
+        if (p.addend) {                               // (inline: mirrored by upconv_halo_k's residual add)
             T* ev = (T*)&val;
             const T* ae = (const T*)&av[it];
 #pragma unroll
             for (int e = 0; e < EC; ++e) Elem<T>::store(ev + e, Elem<T>::load(ev + e) + Elem<T>::load(ae + e));
         }
         vals[it] = val;
-        if (orow_[it] >= 0) *(u32x4_t*)(p.Out + ((size_t)orow_[it] * p.ldo + scol) * ES) = val;
+        ch_store_chunk<ES>(p.Out, orow_[it], p.ldo, scol, val);
     }
     if (p.stats) {
         // GroupNorm partial statistics of the STORED tile, per group of cg consecutive channels: the tile's mean and its sum
         // of squared deviations from that mean (gn_finish_tiles_k merges tiles with the parallel-variance formula).  Every
         // thread reduces its own rows (two passes over its registers: exact mean first), then the partials (count, sum,
         // M2) merge over the row lanes and over a group's channels by the same formula: as stable as torch's two passes.
+        // (Inline: mirrored operation for operation by conv_halo_ws_k's statistics, whose bit-identity is tested.)
         float sum[EC], m2[EC];
         int cnt = 0;
 #pragma unroll
@@ -565,15 +503,9 @@ __global__ void gn_affine_k(const float* __restrict__ mean, const float* __restr
 
 template <typename T, int RING, bool GN>
 static int launch_ch(const ChArgs& a, hipStream_t st) {
-    constexpr int ES = sizeof(T);
     const size_t lds = (size_t)ch_lds_main<T, RING>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + (a.gn_scale ? (size_t)2 * a.Kc * 4 : 0) + 16;
     if (lds > 160 * 1024) return fail(RBVAE_E_UNSUPPORTED, "conv3x3_halo: %zu bytes of LDS", lds);
-    (void)ES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_halo_k<T, RING, GN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    ch_lds_attr_once<conv_halo_k<T, RING, GN>>(160 * 1024);
     hipLaunchKernelGGL((conv_halo_k<T, RING, GN>), dim3(a.total), dim3(512), lds, st, a);
     RBVAE_CHECK_LAUNCH("conv3x3_halo");
     return RBVAE_OK;
@@ -604,12 +536,11 @@ extern "C" int rbvae_conv3x3_halo(int dtype, const void* A, const void* W, void*
     RBVAE_CHECK_ARG(rbvae_conv3x3_halo_ok(dtype, IH, IW, OH, OW, Kc, Nout),
                     "conv3x3_halo: shape not covered (dtype %d, %dx%d -> %dx%d, Kc %d, Nout %d)", dtype, IH, IW, OH, OW, Kc, Nout);
     const int ES = dtype == RBVAE_F32 ? 4 : 2;
-    RBVAE_CHECK_ARG(lda >= Kc && (lda * ES) % 16 == 0 && ldo >= Nout && (ldo * ES) % 16 == 0,
-                    "conv3x3_halo: leading dimensions lda=%d ldo=%d", lda, ldo);
+    if (const int e = ch_check_rows("conv3x3_halo", ES, Kc, Nout, lda, ldo,
+                                    (uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)addend | (uintptr_t)bias))
+        return e;
     RBVAE_CHECK_ARG(Nimg > 0 && (long)Nimg * IH * IW < (1l << 30) && (long)Nimg * OH * OW < (1l << 30),
                     "conv3x3_halo: more than 2^30 pixel rows");
-    RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)addend | (uintptr_t)bias) % 16 == 0,
-                    "conv3x3_halo: pointers must be 16-byte aligned");
     RBVAE_CHECK_ARG((gn_scale == nullptr) == (gn_shift == nullptr), "conv3x3_halo: gn_scale and gn_shift go together");
     RBVAE_CHECK_ARG(!stats_part || (stats_cg > 0 && CH_BN % stats_cg == 0 && Nout % stats_cg == 0),
                     "conv3x3_halo: stats_cg=%d must divide %d", stats_cg, CH_BN);

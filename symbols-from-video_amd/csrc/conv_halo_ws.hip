@@ -63,7 +63,7 @@ __host__ __device__ constexpr int cw_ntop(int j, int nc) {
 
 template <bool GN>
 __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
-    constexpr int MT = 4, NTW = 4;
+    constexpr int MT = CH_MT, NTW = CH_NTW;
     constexpr int NC = GN ? 4 : 0;                           // coefficient loads per slice
     constexpr int PERIOD = 36 + CW_NP + NC;                  // vector-memory operations of a producer wave per slice
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -257,6 +257,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) t[c] = real ? t[c] : v[c];
             }
+            // (conv_halo_k's piece address with this kernel's slots: 256 producer threads, 32 slots apart)
             const unsigned dst = lds0 + (unsigned)buf * CH_ABUF + ch_plane_off(chunk) + (unsigned)(slot0 + 32 * K) * 16;
             if (K < CW_NP - 1 || last_ok) asm volatile("ds_write_b128 %0, %1" ::"v"(dst), "v"(t) : "memory");
         };
@@ -336,11 +337,9 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
     const int wr = w >> 1, wc = w & 1;
     unsigned abase[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-        abase[mt] = lds0 + (unsigned)fg * CH_PLANE + (unsigned)(fg >> 1) * 32 + (unsigned)((wr * MT + mt) * CH_PW + fi) * 16;
+    for (int mt = 0; mt < MT; ++mt) abase[mt] = ch_aplane(lds0, fg) + (unsigned)((wr * MT + mt) * CH_PW + fi) * 16;
     const int fsw = (fi >> 1) & 7;
-    const unsigned offB0 = lds0 + 2 * CH_ABUF + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((0 + fg) ^ fsw) * 16);
-    const unsigned offB1 = lds0 + 2 * CH_ABUF + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((4 + fg) ^ fsw) * 16);
+    const unsigned offB0 = ch_boff(lds0, wc * NTW * 16 + fi, (0 + fg) ^ fsw), offB1 = ch_boff(lds0, wc * NTW * 16 + fi, (4 + fg) ^ fsw);
 
     f32x4_t acc[MT][NTW];
 #pragma unroll
@@ -351,28 +350,13 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
     unsigned ta[MT];
     auto read_half = [&](auto j_tag, auto kk_tag, unsigned rs, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
         constexpr int j = decltype(j_tag)::value, kk = decltype(kk_tag)::value;
-        constexpr int aoff = kk * CH_KKOFF + ((j / 3) * CH_PW + (j % 3)) * 16;
 #if CW_ABL & 8
         return;
 #endif
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[mt]) : "v"(ta[mt]), "n"(aoff));
-        const unsigned ab_ = (kk == 0 ? offB0 : offB1) + rs;
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[nt]) : "v"(ab_), "n"(nt * 2048));
+        ch_read_half<kk * CH_KKOFF + ((j / 3) * CH_PW + (j % 3)) * 16, 0>(ta, kk == 0 ? offB0 : offB1, rs, fa, fb);
     };
-    auto landed = [&](u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-    };
-    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) Mma<bf16_t>::run(acc[mt][nt], fb[nt], fa[mt]);
-    };
+    // (a lambda around the shared step: called directly from the slice body it changes both instances' register allocation)
+    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) { ch_mma_half<bf16_t>(acc, fa, fb); };
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
     u32x4_t xa[MT], xb[NTW], ya[MT], yb[NTW];
@@ -385,7 +369,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
     // before have landed) -> first half's reads -> the second half of the unit before -> second half's reads -> first half
     auto slice = [&](int g) {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) ta[mt] = abase[mt] + (unsigned)((g & 1) * CH_ABUF);
+        for (int mt = 0; mt < MT; ++mt) ta[mt] = ch_slice_addr(abase[mt], g);
         static_for<0, 9>([&](auto j_tag) {
             constexpr int j = decltype(j_tag)::value;
             const unsigned rs = (unsigned)(((g + j) & (CW_RING - 1)) * CH_BBYTES);
@@ -396,12 +380,12 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             mma_half(ya, yb);
             __builtin_amdgcn_sched_barrier(0);
-            landed(xa, xb);
+            ch_landed<0>(xa, xb);
             read_half(j_tag, K1{}, rs, ya, yb);
             __builtin_amdgcn_sched_barrier(0);
             mma_half(xa, xb);
             __builtin_amdgcn_sched_barrier(0);
-            landed(ya, yb);
+            ch_landed<0>(ya, yb);
         });
     };
 
@@ -444,8 +428,8 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             const float bz[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                pk[mt][nt].x = (unsigned)f32_to_bf16(acc[mt][nt][0] + bz[0]) | ((unsigned)f32_to_bf16(acc[mt][nt][1] + bz[1]) << 16);
-                pk[mt][nt].y = (unsigned)f32_to_bf16(acc[mt][nt][2] + bz[2]) | ((unsigned)f32_to_bf16(acc[mt][nt][3] + bz[3]) << 16);
+                pk[mt][nt].x = ch_bias_pack2(acc[mt][nt][0], bz[0], acc[mt][nt][1], bz[1]);
+                pk[mt][nt].y = ch_bias_pack2(acc[mt][nt][2], bz[2], acc[mt][nt][3], bz[3]);
             }
         }
         const int scol = n0 + sch * 8;
@@ -481,7 +465,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             for (int i = 0; i < 4; ++i) {
                 const int it = round * 4 + i, row = i * 32 + rl;
                 u32x4_t val = *(const u32x4_t*)(tile + row * CW_PITCH + sch * 16);
-                if (p.addend) {
+                if (p.addend) {                       // (inline: mirrors conv_halo_k's residual add)
                     bf16_t* ev = (bf16_t*)&val;
                     const bf16_t* ae = (const bf16_t*)&av[i];
 #pragma unroll
@@ -496,7 +480,8 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             }
         }
         if (p.stats) {
-            // GroupNorm partial statistics of the STORED tile (conv_halo_k's, operation for operation)
+            // GroupNorm partial statistics of the STORED tile (inline: mirrors conv_halo_k's, operation for operation; the
+            // neighbour reads are this kernel's own)
             float sum[8], m2[8];
             int cn = 0;
 #pragma unroll
@@ -606,15 +591,13 @@ bool ch_ws_covers(const ChArgs& a) {
 
 int launch_ch_ws(const ChArgs& a, hipStream_t st) {
     static int ncu = 0;
-    static bool attr_set = false;
-    if (!attr_set) {
+    if (ncu == 0) {
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        (void)hipFuncSetAttribute((const void*)conv_halo_ws_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS);
-        (void)hipFuncSetAttribute((const void*)conv_halo_ws_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS);
-        attr_set = true;
     }
+    ch_lds_attr_once<conv_halo_ws_k<true>>(CW_LDS);
+    ch_lds_attr_once<conv_halo_ws_k<false>>(CW_LDS);
     const int grid = a.total < ncu ? a.total : ncu;
     if (a.gn_scale) hipLaunchKernelGGL((conv_halo_ws_k<true>), dim3(grid), dim3(768), CW_LDS, st, a);
     else hipLaunchKernelGGL((conv_halo_ws_k<false>), dim3(grid), dim3(768), CW_LDS, st, a);

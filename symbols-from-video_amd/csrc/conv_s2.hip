@@ -92,11 +92,7 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
 
     // work item: the channel tiles of one pixel tile run back to back on ONE XCD (they re-read the same patch from its L2),
     // and an XCD walks a contiguous range of pixel tiles (neighbours share halo rows).  Bijective for any total.
-    int item;
-    {
-        const int lin = blockIdx.x, xcd = lin & 7, q = p.total >> 3, r = p.total & 7;
-        item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    }
+    const int item = xcd_item(blockIdx.x, p.total);
     const int mtile = item / p.ntn, ntile = item - mtile * p.ntn;
     const int per_img = p.tiles_r * p.tiles_c;
     const int n = mtile / per_img, trc = mtile - n * per_img;

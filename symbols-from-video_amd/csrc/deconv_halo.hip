@@ -114,11 +114,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
         for (int i = 0; i < DH_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
     }
 #endif
-    int item;
-    {
-        const int lin = blockIdx.x, xcd = lin & 7, q = p.total >> 3, r = p.total & 7;
-        item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    }
+    const int item = xcd_item(blockIdx.x, p.total);
     const int mtile = item / p.ntn, ntile = item - mtile * p.ntn;
     const int n0 = ntile * DH_BN;
     const int g0 = mtile * G::TR;

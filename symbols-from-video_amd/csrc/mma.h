@@ -58,6 +58,13 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
     }
 }
 
+// Workgroup lin of a one-dimensional grid -> work item: workgroups are dealt to the 8 XCDs round-robin by id, and XCD x walks
+// the x-th contiguous eighth of the items (neighbouring items share an L2).  Bijective for any total.
+__device__ __forceinline__ int xcd_item(int lin, int total) {
+    const int xcd = lin & 7, q = total >> 3, r = total & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+}
+
 // acc += rowop x colop over one 16-byte fragment per lane of both operands
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {

@@ -39,24 +39,17 @@ struct UcArgs {
 constexpr int UC_RING = 4;         // = taps per class: ring slot of tap j is j
 constexpr int UC_TAPS = 4;
 
-template <typename T> constexpr int uc_lds_main() {
-    constexpr int ring = 2 * CH_ABUF + UC_RING * CH_BBYTES;
-    constexpr int epi = CH_BM * (CH_BN * (int)sizeof(T) + 16);
-    return ring > epi ? ring : epi;
-}
-
 template <typename T>
 __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     constexpr int ES = sizeof(T);
     constexpr int KE = 128 / ES, EC = 16 / ES;
-    constexpr int MT = 4, NTW = 4;
-    constexpr int LOADS = 2;                                  // weight LDS-DMA instructions per wave and step
+    constexpr int MT = CH_MT, NTW = CH_NTW, LOADS = CH_LOADS;
     constexpr int PITCH = CH_BN * ES + 16;
     constexpr int A_BYTES = 2 * CH_ABUF;
     constexpr int CPR = CH_BN / EC;              // 16-B chunks per tile row
     constexpr int RL = 512 / CPR;                // row lanes of the store phase
     constexpr int ITERS = CH_BM / RL;
-    constexpr int RINGB = uc_lds_main<T>();
+    constexpr int RINGB = ch_lds_main<T, UC_RING>();
     static_assert(CH_BM * PITCH <= RINGB && A_BYTES + UC_RING * CH_BBYTES <= RINGB, "LDS carve");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* s_orow = (int*)(smem + RINGB);            // [256]
@@ -67,11 +60,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
 
     // work item: (pixel block, channel tile, class), class fastest; an XCD walks a contiguous range of items, so the
     // 4 * ntn items that read one patch share an L2.  Bijective for any total.
-    int item;
-    {
-        const int lin = blockIdx.x, xcd = lin & 7, q = p.total >> 3, r = p.total & 7;
-        item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    }
+    const int item = xcd_item(blockIdx.x, p.total);
     const int cls = item & 3, it4 = item >> 2;
     const int mtile = it4 / p.ntn, ntile = it4 - mtile * p.ntn;
     const int per_img = p.tiles_r * p.tiles_c;
@@ -86,7 +75,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
         const int r = r0 + (tid >> 4), c = c0 + (tid & 15);
         s_orow[tid] = (r < p.IH && c < p.IW) ? (n * OH + 2 * r + cp) * OW + 2 * c + cq : -1;
     }
-    if (tid < CH_NSLOT_PAD) {
+    if (tid < CH_NSLOT_PAD) {                      // (inline: mirrors conv_halo_k's slot table with dh0 = dw0 = -1)
         int v = -1;
         if (tid < CH_NSLOT) {
             const int pr = tid / CH_PW, pc = tid - pr * CH_PW;
@@ -103,30 +92,18 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     const unsigned char* zsrc = p.zero + chunk * 16;
     int pixr[CH_NA];                 // source pixel row of the six pieces: -1 zero (padding), -2 no such slot
 #pragma unroll
-    for (int i = 0; i < CH_NA; ++i) {
-        const int slot = (tid >> 3) + 64 * i;
-        pixr[i] = slot < CH_NSLOT_PAD ? s_pix[slot] : -2;
-    }
-    // asm loads with destinations tied to the counted wait that covers them (see conv_halo.hip); loads, wait and uses sit
-    // inside one unrolled slice body
+    for (int i = 0; i < CH_NA; ++i) pixr[i] = ch_piece_pix(s_pix, tid, i);
+    // the six staged pieces (ch_piece_load, ch_a_landed); loads, wait and uses sit inside one unrolled slice body (see
+    // conv_halo.hip)
     u32x4_t areg[CH_NA];
     auto a_load = [&](int kc) {
 #pragma unroll
-        for (int i = 0; i < CH_NA; ++i) {
-            const int pv = pixr[i];
-            const unsigned char* src = pv >= 0 ? p.A + ((size_t)pv * p.lda) * ES + (size_t)kc * 128 + chunk * 16 : zsrc;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(areg[i]) : "v"(src) : "memory");
-        }
-    };
-    auto a_landed = [](auto younger_tag, u32x4_t (&ar)[CH_NA]) {
-        constexpr int YOUNGER = decltype(younger_tag)::value;
-        asm volatile("s_waitcnt vmcnt(%6)"
-                     : "+v"(ar[0]), "+v"(ar[1]), "+v"(ar[2]), "+v"(ar[3]), "+v"(ar[4]), "+v"(ar[5])
-                     : "n"(YOUNGER));
+        for (int i = 0; i < CH_NA; ++i) areg[i] = ch_piece_load(ch_piece_src<ES>(p.A, pixr[i], p.lda, kc, chunk, zsrc));
     };
     auto a_write = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < CH_NA; ++i) {
+            // (inline: mirrors conv_halo_k's piece_write)
             const unsigned dst = lds0 + (unsigned)buf * CH_ABUF + ch_plane_off(chunk) + (unsigned)((tid >> 3) + 64 * i) * 16;
             if (pixr[i] >= -1) asm volatile("ds_write_b128 %0, %1" ::"v"(dst), "v"(areg[i]) : "memory");
         }
@@ -136,19 +113,13 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     const int srow = lane >> 3, schunk = lane & 7;
     unsigned blane[LOADS];
 #pragma unroll
-    for (int i = 0; i < LOADS; ++i) {
-        const int r = (w * LOADS + i) * 8 + srow;
-        blane[i] = (unsigned)(r * 16 * p.Kc) * ES + (unsigned)((schunk ^ ((r >> 1) & 7)) * 16);
-    }
+    for (int i = 0; i < LOADS; ++i) blane[i] = ch_blane<ES, 16>((w * LOADS + i) * 8 + srow, schunk, p.Kc);
     const unsigned char* wtile = p.W + ((size_t)n0 * 16 * p.Kc + (size_t)cls * UC_TAPS * p.Kc) * ES;
     const int nkc = p.Kc / KE;
     // folded tap tile of (slice kc, tap j) -> ring slot j
     auto b_issue = [&](int kc, auto j_tag) {
         constexpr int j = decltype(j_tag)::value;
-        const unsigned char* src = wtile + ((size_t)j * p.Kc) * ES + (size_t)kc * 128;
-        unsigned char* lb = smem + A_BYTES + j * CH_BBYTES + (w * LOADS) * 1024;
-#pragma unroll
-        for (int i = 0; i < LOADS; ++i) glds16(src + blane[i], lb + i * 1024);
+        ch_tile_issue(ch_tap_src<ES, j>(wtile, p.Kc, kc), blane, smem + A_BYTES + j * CH_BBYTES + (w * LOADS) * 1024);
     };
 
     // ---- fragment addresses: the class shifts every patch read by (p, q), a tap by its constant (th, tw)
@@ -156,12 +127,9 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     const int wr = w >> 1, wc = w & 1;
     unsigned abase[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-        abase[mt] = lds0 + (unsigned)fg * CH_PLANE + (unsigned)(fg >> 1) * 32 +
-                    (unsigned)((wr * MT + mt + cp) * CH_PW + fi + cq) * 16;
+    for (int mt = 0; mt < MT; ++mt) abase[mt] = ch_aplane(lds0, fg) + (unsigned)((wr * MT + mt + cp) * CH_PW + fi + cq) * 16;
     const int fsw = (fi >> 1) & 7;
-    const unsigned offB0 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((0 + fg) ^ fsw) * 16);
-    const unsigned offB1 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((4 + fg) ^ fsw) * 16);
+    const unsigned offB0 = ch_boff(lds0, wc * NTW * 16 + fi, (0 + fg) ^ fsw), offB1 = ch_boff(lds0, wc * NTW * 16 + fi, (4 + fg) ^ fsw);
 
     f32x4_t acc[MT][NTW];
 #pragma unroll
@@ -172,36 +140,14 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     unsigned ta[MT];                         // patch read addresses of the slice being read (buffer folded in)
     auto set_slice = [&](int kc) {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) ta[mt] = abase[mt] + (unsigned)((kc & 1) * CH_ABUF);
+        for (int mt = 0; mt < MT; ++mt) ta[mt] = ch_slice_addr(abase[mt], kc);
     };
     auto read_half = [&](auto j_tag, auto kk_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
         constexpr int j = decltype(j_tag)::value, kk = decltype(kk_tag)::value;
-        constexpr int aoff = kk * CH_KKOFF + ((j >> 1) * CH_PW + (j & 1)) * 16;
-        constexpr int boff = j * CH_BBYTES;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[mt]) : "v"(ta[mt]), "n"(aoff));
-        const unsigned ab_ = kk == 0 ? offB0 : offB1;
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[nt]) : "v"(ab_), "n"(boff + nt * 2048));
-    };
-    auto landed = [&](auto younger_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
-        constexpr int YOUNGER = decltype(younger_tag)::value;
-        asm volatile("s_waitcnt lgkmcnt(%8)"
-                     : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3])
-                     : "n"(YOUNGER));
-    };
-    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
+        ch_read_half<kk * CH_KKOFF + ((j >> 1) * CH_PW + (j & 1)) * 16, j * CH_BBYTES>(ta, kk == 0 ? offB0 : offB1, 0u, fa, fb);
     };
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
-    using Younger = std::integral_constant<int, MT + NTW>;
-    using None = std::integral_constant<int, 0>;
 
     // ---- prologue: patch of slice 0 and its four tap tiles
     a_load(0);
@@ -209,7 +155,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
     b_issue(0, std::integral_constant<int, 1>{});
     b_issue(0, std::integral_constant<int, 2>{});
     b_issue(0, std::integral_constant<int, 3>{});
-    a_landed(std::integral_constant<int, 0>{}, areg);
+    ch_a_landed<0>(areg);
     a_write(0);
     wait_vm_lgkm_barrier<0>();
     u32x4_t fa0[MT], fb0[NTW], fa1[MT], fb1[NTW];
@@ -231,18 +177,18 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
             constexpr int nj = (j + 1) % UC_TAPS;            // tap of the next step
             using NJ = std::integral_constant<int, nj>;
             read_half(j_tag, K1{}, fa1, fb1);
-            landed(Younger{}, fa0, fb0);
+            ch_landed<MT + NTW>(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            mma_half(fa0, fb0);
+            ch_mma_half<T>(acc, fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            landed(None{}, fa1, fb1);
+            ch_landed<0>(fa1, fb1);
             if constexpr (j == UC_TAPS - 1 && !more) {       // the very last step reads nothing ahead
                 __builtin_amdgcn_sched_barrier(0);
-                mma_half(fa1, fb1);
+                ch_mma_half<T>(acc, fa1, fb1);
             } else {
                 if constexpr (more) {
                     if constexpr (j == 3) {
-                        a_landed(std::integral_constant<int, 2 * LOADS>{}, areg);
+                        ch_a_landed<2 * LOADS>(areg);
                         a_write((kc + 1) & 1);
                     }
                     if constexpr (j == 1 || j == 2) wait_vm_lgkm_barrier<2 * LOADS + CH_NA>();
@@ -258,7 +204,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
                 if constexpr (nj == 0) set_slice(kc + 1);
                 read_half(NJ{}, K0{}, fa0, fb0);
                 __builtin_amdgcn_sched_barrier(0);
-                mma_half(fa1, fb1);
+                ch_mma_half<T>(acc, fa1, fb1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
@@ -286,12 +232,11 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
             const int row = (wr * MT + mt) * 16 + fi;
             unsigned char* dst = tile + row * PITCH + cb * ES;
             if constexpr (ES == 4) {
-                *(float4*)dst = make_float4(acc[mt][nt][0] + bz[0], acc[mt][nt][1] + bz[1], acc[mt][nt][2] + bz[2],
-                                            acc[mt][nt][3] + bz[3]);
-            } else {
+                epi_stage<T>(dst, acc[mt][nt][0] + bz[0], acc[mt][nt][1] + bz[1], acc[mt][nt][2] + bz[2], acc[mt][nt][3] + bz[3]);
+            } else {                                       // (epi_stage's bf16 half changes the listings: ch_bias_pack2)
                 uint2 pk;
-                pk.x = (unsigned)f32_to_bf16(acc[mt][nt][0] + bz[0]) | ((unsigned)f32_to_bf16(acc[mt][nt][1] + bz[1]) << 16);
-                pk.y = (unsigned)f32_to_bf16(acc[mt][nt][2] + bz[2]) | ((unsigned)f32_to_bf16(acc[mt][nt][3] + bz[3]) << 16);
+                pk.x = ch_bias_pack2(acc[mt][nt][0], bz[0], acc[mt][nt][1], bz[1]);
+                pk.y = ch_bias_pack2(acc[mt][nt][2], bz[2], acc[mt][nt][3], bz[3]);
                 *(uint2*)dst = pk;
             }
         }
@@ -307,31 +252,27 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         orow_[it] = s_orow[it * RL + rl];
-        if (p.addend) av[it] = *(const u32x4_t*)(p.addend + ((size_t)(orow_[it] < 0 ? 0 : orow_[it]) * p.ldo + scol) * ES);
+        if (p.addend) av[it] = ch_addend_chunk<ES>(p.addend, orow_[it], p.ldo, scol);
     }
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int row = it * RL + rl;
         u32x4_t val = *(const u32x4_t*)(tile + row * PITCH + sch * 16);
-        if (p.addend) {
+        if (p.addend) {                               // (inline: mirrored by conv_halo_k's residual add)
             T* ev = (T*)&val;
             const T* ae = (const T*)&av[it];
 #pragma unroll
             for (int e = 0; e < EC; ++e) Elem<T>::store(ev + e, Elem<T>::load(ev + e) + Elem<T>::load(ae + e));
         }
-        if (orow_[it] >= 0) *(u32x4_t*)(p.Out + ((size_t)orow_[it] * p.ldo + scol) * ES) = val;
+        ch_store_chunk<ES>(p.Out, orow_[it], p.ldo, scol, val);
     }
 }
 
 template <typename T>
 static int launch_uc(const UcArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)uc_lds_main<T>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + 16;
-    static_assert(uc_lds_main<float>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + 16 <= 160 * 1024, "LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)upconv_halo_k<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    const size_t lds = (size_t)ch_lds_main<T, UC_RING>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + 16;
+    static_assert(ch_lds_main<float, UC_RING>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + 16 <= 160 * 1024, "LDS");
+    ch_lds_attr_once<upconv_halo_k<T>>(160 * 1024);
     hipLaunchKernelGGL((upconv_halo_k<T>), dim3(a.total), dim3(512), lds, st, a);
     RBVAE_CHECK_LAUNCH("upconv3x3_halo");
     return RBVAE_OK;
@@ -450,10 +391,9 @@ extern "C" int rbvae_upconv3x3_halo(int dtype, const void* A, const void* Wf, vo
                     IH, IW, Kc, Nout);
     RBVAE_CHECK_ARG(A && Wf && Out && zero_page, "upconv3x3_halo: null pointer");
     const int ES = dtype == RBVAE_F32 ? 4 : 2;
-    RBVAE_CHECK_ARG(lda >= Kc && (lda * ES) % 16 == 0 && ldo >= Nout && (ldo * ES) % 16 == 0,
-                    "upconv3x3_halo: leading dimensions lda=%d ldo=%d", lda, ldo);
-    RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)Wf | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)addend | (uintptr_t)bias) % 16 == 0,
-                    "upconv3x3_halo: pointers must be 16-byte aligned");
+    if (const int e = ch_check_rows("upconv3x3_halo", ES, Kc, Nout, lda, ldo,
+                                    (uintptr_t)A | (uintptr_t)Wf | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)addend | (uintptr_t)bias))
+        return e;
     UcArgs a;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)Wf; a.Out = (unsigned char*)Out; a.bias = bias;
     a.addend = (const unsigned char*)addend; a.zero = (const unsigned char*)zero_page;
