@@ -24,6 +24,25 @@ int fail(int code, const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// dynamic LDS of a kernel instance: once per instance, allow `bytes` ...
+template <auto KERNEL> static inline void lds_attr_once(int bytes) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        attr_set = true;
+    }
+}
+// ... or, where the size depends on the launch, raise the instance's limit when a launch of the wrapper `who` needs more
+template <auto KERNEL> static inline int lds_attr_grow(const char* who, size_t lds) {
+    static size_t attr_lds = 0;
+    if (lds > attr_lds) {
+        hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return fail(RBVAE_E_LAUNCH, "%s: %s (dynamic LDS %zu)", who, hipGetErrorString(e), lds);
+        attr_lds = lds;
+    }
+    return RBVAE_OK;
+}
+
 // ---- device helpers -------------------------------------------------------
 typedef unsigned short bf16_t;   // raw bf16 bits
 

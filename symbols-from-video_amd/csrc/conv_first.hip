@@ -13,12 +13,12 @@
 //
 // They replace rbvae_im2col(_frames) + the single-slice rbvae_gather_gemm (same arithmetic per element: one 64-deep MFMA
 // chain; same dropout key and chunk indices; stored values are bit-identical).
-#include "epilogue.h"
+//
+// The steps the kernels of this file share with each other, with deconv_last_fwd_bwd_k and with conv_in_k are ends.h's.  A step
+// that is typed out in several kernels carries "(inline: mirrors ...)": every helper form tried changed a listing (DESIGN.md,
+// "Shared steps of the end kernels").
+#include "ends.h"
 #include <stdlib.h>
-
-#ifndef CF_DBG      // timing experiments only: 1 no output stores, 2 no col stores, 3 stop after the staging, 4 no patch loads, 5 no gate reads
-#define CF_DBG 0
-#endif
 
 namespace rbvae {
 
@@ -39,22 +39,6 @@ struct CfArgs {
     const unsigned long long* seed_dev;
 };
 
-constexpr int CF_TA = 8, CF_TB = 16;                          // output block
-constexpr int CF_PA = 2 * CF_TA + 1, CF_PB = 2 * CF_TB + 1;   // input patch 17 x 33
-constexpr int CF_PP = CF_PB + 1;                              // patch row pitch (pixels)
-
-// patch offset of im2col column k = (kh*3+kw)*CIN + ci relative to the output pixel's corner; -1 = padding column.
-// MODE 0 keeps the patch as [ci][row][col], MODE 1 as [row][col][ci] (the order the input arrives in).
-template <int CIN, int MODE> struct CfOff {
-    int v[64];
-    constexpr CfOff() : v{} {
-        for (int k = 0; k < 64; ++k) {
-            const int t = k / CIN, ci = k % CIN, kh = t / 3, kw = t % 3;
-            v[k] = k >= 9 * CIN ? -1 : MODE == 0 ? (ci * CF_PA + kh) * CF_PP + kw : (kh * CF_PP + kw) * CIN + ci;
-        }
-    }
-};
-
 // NQ = 64-channel quads of the tile: 4 (Nout <= 256: wave = 64 pixels x one quad) or 1 (Nout <= 64, the cfg 3 widths: wave =
 // 16 pixels x the one quad -- with the 256-wide tile three of four waves multiplied and staged zero weights and sat out the
 // epilogue; 8 KB of weights instead of 32 and 16 accumulators per lane let four workgroups share a CU)
@@ -62,25 +46,23 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
     constexpr int MT = NQ == 4 ? 4 : 1;                                          // 16-pixel tiles per wave
     __shared__ __attribute__((aligned(16))) unsigned char s_a[128 * 128];        // im2col rows, swizzled chunks
     __shared__ __attribute__((aligned(16))) unsigned char s_b[64 * NQ * 128];    // weights in fragment-row order
-    __shared__ float s_patch[4 * CF_PA * CF_PP];
+    __shared__ float s_patch[4 * EN_PA * EN_PP];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int tb_n = (p.OW + CF_TB - 1) / CF_TB, ta_n = (p.OH + CF_TA - 1) / CF_TA;
-    unsigned blk = blockIdx.x;
-    const int tbi = blk % (unsigned)tb_n; blk /= (unsigned)tb_n;
-    const int tai = blk % (unsigned)ta_n;
-    const int n = blk / (unsigned)ta_n;
-    const int oh0 = tai * CF_TA, ow0 = tbi * CF_TB;
+    const int tb_n = en_tb_n(p.OW), ta_n = en_ta_n(p.OH);
+    const EnBlk bk = en_blk(blockIdx.x, ta_n, tb_n);
+    const int n = bk.n, oh0 = bk.tai * EN_TA, ow0 = bk.tbi * EN_TB;
     const int ih0 = 2 * oh0 - 1, iw0 = 2 * ow0 - 1;
 
     // ---- weights -> LDS by LDS-DMA: image row ct*16 + j holds channel 64*(ct/4) + 16*(j/4) + 4*(ct%4) + j%4, so that a
     // lane's accumulators of a tile quad are 16 consecutive channels (32 bytes per pixel, 128 per pixel and wave)
+    // (inline: conv_in_k and deconv_last_fwd_bwd_k mirror this row permutation)
     {
         const int srow = lane >> 3, schunk = lane & 7;
         for (int q = w; q < 8 * NQ; q += 8) {                // 8 NQ instructions of 8 rows
             const int r = q * 8 + srow;
             const int ct = r >> 4, j = r & 15;
             const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
-            const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + ((schunk ^ ((r >> 1) & 7)) * 16) : p.zero;
+            const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + en_swz16(r, schunk) : p.zero;
             glds16(src, s_b + (size_t)(r - srow) * 128);
         }
     }
@@ -97,26 +79,26 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
     }
     DropKey dkey{0u, 0u};
     int koff[8];
-    static constexpr CfOff<CIN, MODE> otab{};
-    // ---- input patch
+    static constexpr EnOff<CIN, MODE, EN_PA, EN_PP> otab{};
+    // ---- input patch (inline: wgrad_first_k's load_patch / store_patch and wgrad_first_wide_k's branch-free form mirror it)
     if constexpr (MODE == 0) {
         // s_patch row c*17 + r, column 0 = the halo column 2*ow0 - 1, columns 1 .. 32 = the 128-byte run from 2*ow0: one
         // instruction loads two rows (32 lanes each)
         const float* xf = p.x + frame_off_u32(p.fm, n);
-        constexpr int R = CIN * CF_PA, PAIRS = (R + 1) / 2, PIT = (PAIRS + 7) / 8;
+        constexpr int R = CIN * EN_PA, PAIRS = (R + 1) / 2, PIT = (PAIRS + 7) / 8;
         float pv[PIT], hv = 0.f;
 #pragma unroll
         for (int it = 0; it < PIT; ++it) {
             const int row = 2 * (w + 8 * it) + (lane >> 5);
-            const int c = row / CF_PA, r = row - c * CF_PA;
+            const int c = row / EN_PA, r = row - c * EN_PA;
             const int ih = ih0 + r, iw = iw0 + 1 + (lane & 31);
             pv[it] = 0.f;
-            if (CF_DBG != 4 && row < R && ih >= 0 && ih < p.IH && iw < p.IW) pv[it] = xf[((size_t)c * p.IH + ih) * p.IW + iw];
+            if (row < R && ih >= 0 && ih < p.IH && iw < p.IW) pv[it] = xf[((size_t)c * p.IH + ih) * p.IW + iw];
         }
         if (tid < R) {
-            const int c = tid / CF_PA, r = tid - c * CF_PA;
+            const int c = tid / EN_PA, r = tid - c * EN_PA;
             const int ih = ih0 + r;
-            if (CF_DBG != 4 && ih >= 0 && ih < p.IH && iw0 >= 0) hv = xf[((size_t)c * p.IH + ih) * p.IW + iw0];
+            if (ih >= 0 && ih < p.IH && iw0 >= 0) hv = xf[((size_t)c * p.IH + ih) * p.IW + iw0];
         }
 #pragma unroll
         for (int k8 = 0; k8 < 8; ++k8) koff[k8] = otab.v[(tid & 7) * 8 + k8];
@@ -124,13 +106,13 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
 #pragma unroll
         for (int it = 0; it < PIT; ++it) {
             const int row = 2 * (w + 8 * it) + (lane >> 5);
-            if (row < R) s_patch[row * CF_PP + 1 + (lane & 31)] = pv[it];
+            if (row < R) s_patch[row * EN_PP + 1 + (lane & 31)] = pv[it];
         }
-        if (tid < R) s_patch[tid * CF_PP] = hv;
+        if (tid < R) s_patch[tid * EN_PP] = hv;
     } else {
         // [row][col][ci]: a patch row is one run of 33*CIN floats
         const float* xf = p.x + (size_t)n * p.IH * p.IW * CIN;
-        constexpr int RUN = CF_PB * CIN, PN = CF_PA * RUN, PIT = (PN + 511) / 512;
+        constexpr int RUN = EN_PB * CIN, PN = EN_PA * RUN, PIT = (PN + 511) / 512;
         float pv[PIT];
 #pragma unroll
         for (int it = 0; it < PIT; ++it) {
@@ -138,7 +120,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
             const int r = i / RUN, j = i - r * RUN;
             const int ih = ih0 + r, iw = iw0 + j / CIN;
             pv[it] = 0.f;
-            if (CF_DBG != 4 && i < PN && ih >= 0 && ih < p.IH && iw >= 0 && iw < p.IW)
+            if (i < PN && ih >= 0 && ih < p.IH && iw >= 0 && iw < p.IW)
                 pv[it] = xf[((long)ih * p.IW + iw0) * CIN + j];
         }
 #pragma unroll
@@ -147,7 +129,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
         for (int it = 0; it < PIT; ++it) {
             const int i = it * 512 + tid;
             const int r = i / RUN, j = i - r * RUN;
-            if (i < PN) s_patch[r * (CF_PP * CIN) + j] = pv[it];
+            if (i < PN) s_patch[r * (EN_PP * CIN) + j] = pv[it];
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // weights (LDS-DMA), bias, key: everything this wave asked for
@@ -157,30 +139,29 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
     asm volatile("" : "+v"(dkey.k0), "+v"(dkey.k1));
     __syncthreads();
     // ---- im2col rows: 128 rows x 8 chunks of 8 columns (a thread keeps its chunk index over both rounds)
+    // (inline: both weight-gradient kernels, deconv_last_fwd_bwd_k and conv_in_k mirror this loop; elements, pack and the
+    // swizzled offset are ends.h's)
 #pragma unroll
     for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
         const int i = i0 + tid;
         const int r = i >> 3, c = i & 7;
         const int oy = r >> 4, ox = r & 15;
-        const int corner = (2 * oy * CF_PP + 2 * ox) * (MODE == 0 ? 1 : CIN);
+        const int corner = (2 * oy * EN_PP + 2 * ox) * (MODE == 0 ? 1 : CIN);
         unsigned short e[8];
 #pragma unroll
-        for (int k8 = 0; k8 < 8; ++k8) {
-            const float v = koff[k8] >= 0 ? s_patch[corner + max(koff[k8], 0)] : 0.f;
-            e[k8] = f32_to_bf16(v);
-        }
+        for (int k8 = 0; k8 < 8; ++k8) e[k8] = en_col_elem(s_patch, corner, koff[k8]);
         u32x4_t pk;
-        pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
-        pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
-        *(u32x4_t*)(s_a + r * 128 + ((c ^ ((r >> 1) & 7)) * 16)) = pk;
+        pk[0] = en_pack2(e[0], e[1]); pk[1] = en_pack2(e[2], e[3]);
+        pk[2] = en_pack2(e[4], e[5]); pk[3] = en_pack2(e[6], e[7]);
+        *(u32x4_t*)(s_a + en_a_off(r, c)) = pk;
         const int oh = oh0 + oy, ow = ow0 + ox;
-        if (CF_DBG != 2 && p.col && oh < p.OH && ow < p.OW)     // col == null: the weight gradient rebuilds the rows (wgrad_first_k)
-            *(u32x4_t*)(p.col + ((size_t)(n * p.OH + oh) * p.OW + ow) * 128 + c * 16) = pk;
+        if (p.col && oh < p.OH && ow < p.OW)     // col == null: the weight gradient rebuilds the rows (wgrad_first_k)
+            *(u32x4_t*)(p.col + (en_pix_row(n, p.OH, p.OW, oh, ow)) * 128 + c * 16) = pk;
     }
     __syncthreads();
 
     // ---- 128 x 256 x 64 on the matrix cores: wave w owns pixels 64*(w/4) .. +63 x the tile quad w%4 = channels 64*(w%4) .. +63
-    if (CF_DBG == 3) return;
+    // (inline: deconv_last_fwd_bwd_k and conv_in_k mirror this block; the chunk offset and the MFMA are ends.h's)
     const int fsw = (fi >> 1) & 7;
     f32x4_t acc[MT][4];
 #pragma unroll
@@ -189,7 +170,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
         for (int h = 0; h < 4; ++h) acc[mt][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int ch = ((4 * kk + fg) ^ fsw) * 16;
+        const int ch = en_frag_ch(kk, fg, fsw);
         u32x4_t wv[4], av[MT];
 #pragma unroll
         for (int h = 0; h < 4; ++h) wv[h] = *(const u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);
@@ -199,8 +180,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int h = 0; h < 4; ++h)
-                acc[mt][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&wv[h], *(const bf16x8_t*)&av[mt],
-                                                                     acc[mt][h], 0, 0, 0);
+                acc[mt][h] = en_mma(wv[h], av[mt], acc[mt][h]);
     }
     // ---- epilogue from registers: lane = pixel fi of tile mt, channels 64*wq + 16*fg .. +15 (two 16-byte chunks)
     if (MODE == 0 && !first) return;
@@ -212,15 +192,11 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
         const int r = (MT * wm + mt) * 16 + fi;
         const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
         if (oh >= p.OH || ow >= p.OW || !first) continue;
-        const size_t orow = (size_t)(n * p.OH + oh) * p.OW + ow;
+        const size_t orow = en_pix_row(n, p.OH, p.OW, oh, ow);
         u32x4_t g4[2];
         if constexpr (MODE == 1) {
-#if CF_DBG == 5
-            g4[0] = u32x4_t{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u}; g4[1] = g4[0];   // timing: no gate reads
-#else
             g4[0] = *(const u32x4_t*)(p.gate + (orow * p.ldo + col) * 2);
             g4[1] = second ? *(const u32x4_t*)(p.gate + (orow * p.ldo + col + 8) * 2) : u32x4_t{0u, 0u, 0u, 0u};
-#endif
         }
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -267,7 +243,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
                     val[e] = v;
                 }
             }
-            if (CF_DBG != 1 || val[0] == 0x12345678u) *(u32x4_t*)(p.out + (orow * p.ldo + col + 8 * half) * 2) = val;
+            *(u32x4_t*)(p.out + (orow * p.ldo + col + 8 * half) * 2) = val;
             if constexpr (MODE == 1) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
@@ -278,8 +254,9 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
     if constexpr (MODE == 1) {
         if (p.colsum_ws) {
             // bias gradient of the layer below: column sums of this block's stored values, pixels then wave halves
+            // (inline: deconv_last_fwd_bwd_k mirrors the row sums and scratch writes; the total is ends.h's)
             float* red = s_patch;                              // [pixel groups][64 NQ]; the patch is dead since the second barrier
-            constexpr int RW = 64 * NQ, NGRP = NQ == 4 ? 2 : 8;
+            constexpr int RW = 64 * NQ;
 #pragma unroll
             for (int e = 0; e < 16; ++e) csum[e] = row_sum(csum[e]);
             if (fi == 0) {
@@ -288,9 +265,7 @@ template <int CIN, int MODE, int NQ> __global__ __launch_bounds__(512, NQ == 1 ?
             }
             __syncthreads();
             if (tid < p.Nout) {
-                float t = red[tid];
-#pragma unroll
-                for (int g2 = 1; g2 < NGRP; ++g2) t += red[g2 * RW + tid];      // fixed order
+                const float t = en_colsum_total<NQ>(red, tid);
                 p.colsum_ws[(size_t)blockIdx.x * p.Nout + tid] = t;
             }
         }
@@ -317,43 +292,41 @@ struct WfArgs {
 template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_first_k(const WfArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char s_col[128 * 128];       // im2col rows [px][64 k], tr-swizzled
     __shared__ __attribute__((aligned(16))) unsigned char s_dy[2][128 * 128];     // dY tile [px][64 co], tr-swizzled, double-buffered
-    __shared__ float s_patch[4 * CF_PA * CF_PP];
+    __shared__ float s_patch[4 * EN_PA * EN_PP];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nco = p.Nout >> 6;
     const int cot = blockIdx.x % nco, ks = blockIdx.x / nco;
     const int co0 = cot * 64;
-    const int tb_n = (p.OW + CF_TB - 1) / CF_TB, ta_n = (p.OH + CF_TA - 1) / CF_TA;
+    const int tb_n = en_tb_n(p.OW), ta_n = en_ta_n(p.OH);
     const int blk0 = ks * p.per, blk1 = min(blk0 + p.per, p.nblk);
-    static constexpr CfOff<CIN, MODE> otab{};
+    static constexpr EnOff<CIN, MODE, EN_PA, EN_PP> otab{};
     int koff[8];
 #pragma unroll
     for (int k8 = 0; k8 < 8; ++k8) koff[k8] = otab.v[(tid & 7) * 8 + k8];
 
-    // patch of block blk -> registers (the loads of conv_first_fused_k)
-    constexpr int R0 = CIN * CF_PA, PIT0 = ((R0 + 1) / 2 + 7) / 8;
-    constexpr int RUN = CF_PB * CIN, PN = CF_PA * RUN, PIT1 = (PN + 511) / 512;
+    // patch of block blk -> registers (inline: mirrors the loads and stores of conv_first_fused_k)
+    constexpr int R0 = CIN * EN_PA, PIT0 = ((R0 + 1) / 2 + 7) / 8;
+    constexpr int RUN = EN_PB * CIN, PN = EN_PA * RUN, PIT1 = (PN + 511) / 512;
     constexpr int PIT = MODE == 0 ? PIT0 : PIT1;
     float pv[PIT], hv = 0.f;
     auto load_patch = [&](int blk) {
-        unsigned b = blk;
-        const int tbi = b % (unsigned)tb_n; b /= (unsigned)tb_n;
-        const int tai = b % (unsigned)ta_n;
-        const int n = b / (unsigned)ta_n;
-        const int ih0 = 2 * tai * CF_TA - 1, iw0 = 2 * tbi * CF_TB - 1;
+        const EnBlk bk = en_blk(blk, ta_n, tb_n);
+        const int n = bk.n, tai = bk.tai, tbi = bk.tbi;
+        const int ih0 = 2 * tai * EN_TA - 1, iw0 = 2 * tbi * EN_TB - 1;
         if constexpr (MODE == 0) {
             const float* xf = p.x + frame_off_u32(p.fm, n);
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int row = 2 * (w + 8 * it) + (lane >> 5);
-                const int c = row / CF_PA, r = row - c * CF_PA;
+                const int c = row / EN_PA, r = row - c * EN_PA;
                 const int ih = ih0 + r, iw = iw0 + 1 + (lane & 31);
                 pv[it] = 0.f;
                 if (row < R0 && ih >= 0 && ih < p.IH && iw < p.IW) pv[it] = xf[((size_t)c * p.IH + ih) * p.IW + iw];
             }
             hv = 0.f;
             if (tid < R0) {
-                const int c = tid / CF_PA, r = tid - c * CF_PA;
+                const int c = tid / EN_PA, r = tid - c * EN_PA;
                 const int ih = ih0 + r;
                 if (ih >= 0 && ih < p.IH && iw0 >= 0) hv = xf[((size_t)c * p.IH + ih) * p.IW + iw0];
             }
@@ -374,30 +347,29 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int row = 2 * (w + 8 * it) + (lane >> 5);
-                if (row < R0) s_patch[row * CF_PP + 1 + (lane & 31)] = pv[it];
+                if (row < R0) s_patch[row * EN_PP + 1 + (lane & 31)] = pv[it];
             }
-            if (tid < R0) s_patch[tid * CF_PP] = hv;
+            if (tid < R0) s_patch[tid * EN_PP] = hv;
         } else {
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int i = it * 512 + tid;
                 const int r = i / RUN, j = i - r * RUN;
-                if (i < PN) s_patch[r * (CF_PP * CIN) + j] = pv[it];
+                if (i < PN) s_patch[r * (EN_PP * CIN) + j] = pv[it];
             }
         }
     };
     // dY tile of block blk -> s_dy[buf]: 16 LDS-DMA instructions of 8 rows, two per wave
+    // (inline: wgrad_first_wide_k's load_block mirrors the source row and chunk)
     auto stage_dy = [&](int blk, int buf) {
-        unsigned b = blk;
-        const int tbi = b % (unsigned)tb_n; b /= (unsigned)tb_n;
-        const int tai = b % (unsigned)ta_n;
-        const int n = b / (unsigned)ta_n;
+        const EnBlk bk = en_blk(blk, ta_n, tb_n);
+        const int n = bk.n, tai = bk.tai, tbi = bk.tbi;
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
             const int r = (2 * w + i2) * 8 + (lane >> 3);
-            const int oh = tai * CF_TA + (r >> 4), ow = tbi * CF_TB + (r & 15);
+            const int oh = tai * EN_TA + (r >> 4), ow = tbi * EN_TB + (r & 15);
             const bool v = oh < p.OH && ow < p.OW;
-            const unsigned char* src = p.dY + ((size_t)(n * p.OH + oh) * p.OW + ow) * ((size_t)p.ldy * 2) + co0 * 2 +
+            const unsigned char* src = p.dY + (en_pix_row(n, p.OH, p.OW, oh, ow)) * ((size_t)p.ldy * 2) + co0 * 2 +
                                        (((lane & 7) ^ tr_swz<128>(r)) * 16);
             glds16(v ? src : p.zero, s_dy[buf] + (2 * w + i2) * 1024);
         }
@@ -408,9 +380,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
     const int q = fi >> 2, pp = fi & 3;
     const int mt = w & 3, nt0 = (w >> 2) * 2;
     const int row0 = 8 * fg + q;
-    const int offA = row0 * 128 + (((mt * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
-    const int offB0 = row0 * 128 + (((nt0 * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
-    const int offB1 = row0 * 128 + ((((nt0 + 1) * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
+    const int offA = en_tr_off(row0, mt, pp), offB0 = en_tr_off(row0, nt0, pp), offB1 = en_tr_off(row0, nt0 + 1, pp);
     f32x4_t acc0 = f32x4_t{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
     const unsigned l_col = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)s_col;
     const unsigned l_dy = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)s_dy[0];
@@ -428,22 +398,19 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
         store_patch();
         if (blk + 1 < blk1) load_patch(blk + 1);                         // lands under this block's work
         lds_barrier();
-        // im2col rows: 128 rows x 8 chunks of 8 columns
+        // im2col rows: 128 rows x 8 chunks of 8 columns (inline: mirrors conv_first_fused_k's row build, tr-swizzled)
 #pragma unroll
         for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
             const int i = i0 + tid;
             const int r = i >> 3, c = i & 7;
             const int oy = r >> 4, ox = r & 15;
-            const int corner = (2 * oy * CF_PP + 2 * ox) * (MODE == 0 ? 1 : CIN);
+            const int corner = (2 * oy * EN_PP + 2 * ox) * (MODE == 0 ? 1 : CIN);
             unsigned short e[8];
 #pragma unroll
-            for (int k8 = 0; k8 < 8; ++k8) {
-                const float v = koff[k8] >= 0 ? s_patch[corner + max(koff[k8], 0)] : 0.f;
-                e[k8] = f32_to_bf16(v);
-            }
+            for (int k8 = 0; k8 < 8; ++k8) e[k8] = en_col_elem(s_patch, corner, koff[k8]);
             u32x4_t pk;
-            pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
-            pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
+            pk[0] = en_pack2(e[0], e[1]); pk[1] = en_pack2(e[2], e[3]);
+            pk[2] = en_pack2(e[4], e[5]); pk[3] = en_pack2(e[6], e[7]);
             *(u32x4_t*)(s_col + r * 128 + ((c ^ tr_swz<128>(r)) * 16)) = pk;
         }
         lds_barrier();
@@ -453,6 +420,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
         const unsigned la = l_dy + buf * (128 * 128);
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
+            // (inline: wgrad_first_wide_k mirrors these reads, the tied wait and the slab store below)
             s16x4_t al, ah, b0l, b0h, b1l, b1h;
             const unsigned ada = la + offA + kb * (32 * 128), adb0 = l_col + offB0 + kb * (32 * 128), adb1 = l_col + offB1 + kb * (32 * 128);
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(al) : "v"(ada));
@@ -462,9 +430,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(b1l) : "v"(adb1));
             asm volatile("ds_read_b64_tr_b16 %0, %1 offset:512" : "=v"(b1h) : "v"(adb1));
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al), "+v"(ah), "+v"(b0l), "+v"(b0h), "+v"(b1l), "+v"(b1h));
-            const bf16x8_t fa = bf16x8_t{al[0], al[1], al[2], al[3], ah[0], ah[1], ah[2], ah[3]};
-            const bf16x8_t fb0 = bf16x8_t{b0l[0], b0l[1], b0l[2], b0l[3], b0h[0], b0h[1], b0h[2], b0h[3]};
-            const bf16x8_t fb1 = bf16x8_t{b1l[0], b1l[1], b1l[2], b1l[3], b1h[0], b1h[1], b1h[2], b1h[3]};
+            const bf16x8_t fa = en_tr_frag(al, ah), fb0 = en_tr_frag(b0l, b0h), fb1 = en_tr_frag(b1l, b1h);
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0, fa, acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1, fa, acc1, 0, 0, 0);
         }
@@ -485,7 +451,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
 // (each in wgrad_first_k's layout: the same fragment addressing with an image offset).  Both operands travel through
 // registers two blocks ahead (two register sets for the even / odd blocks of the walk; every load branch-free, so the
 // compiler's counted waits hold); one workgroup per CU (153 KB of LDS); rbvae_wgrad_gemm's slab layout.
-constexpr int WFW_LDS = 16384 + 2 * 4 * 16384 + 4 * CF_PA * CF_PP * 4;
+constexpr int WFW_LDS = 16384 + 2 * 4 * 16384 + 4 * EN_PA * EN_PP * 4;
 template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_first_wide_k(const WfArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
     unsigned char* s_col = wsm;                                   // im2col rows [px][64 k], tr-swizzled
@@ -496,36 +462,35 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
     const int nct = p.Nout >> 8;
     const int cot = blockIdx.x % nct, ks = blockIdx.x / nct;
     const int co0 = cot * 256;
-    const int tb_n = (p.OW + CF_TB - 1) / CF_TB, ta_n = (p.OH + CF_TA - 1) / CF_TA;
+    const int tb_n = en_tb_n(p.OW), ta_n = en_ta_n(p.OH);
     const int blk0 = ks * p.per, blk1 = min(blk0 + p.per, p.nblk);
-    static constexpr CfOff<CIN, MODE> otab{};
+    static constexpr EnOff<CIN, MODE, EN_PA, EN_PP> otab{};
     int koff[8];
 #pragma unroll
     for (int k8 = 0; k8 < 8; ++k8) koff[k8] = otab.v[(tid & 7) * 8 + k8];
 
-    constexpr int R0 = CIN * CF_PA, PIT0 = ((R0 + 1) / 2 + 7) / 8;
-    constexpr int RUN = CF_PB * CIN, PN = CF_PA * RUN, PIT1 = (PN + 511) / 512;
+    constexpr int R0 = CIN * EN_PA, PIT0 = ((R0 + 1) / 2 + 7) / 8;
+    constexpr int RUN = EN_PB * CIN, PN = EN_PA * RUN, PIT1 = (PN + 511) / 512;
     constexpr int PIT = MODE == 0 ? PIT0 : PIT1;
     struct Stage { float pv[PIT]; float hv; u32x4_t dy[8]; };
     auto load_block = [&](int blk_, Stage& st) {
-        unsigned b = (unsigned)min(blk_, blk1 - 1);                       // (past the end: the last block again, never used)
-        const int tbi = b % (unsigned)tb_n; b /= (unsigned)tb_n;
-        const int tai = b % (unsigned)ta_n;
-        const int n = b / (unsigned)ta_n;
-        const int ih0 = 2 * tai * CF_TA - 1, iw0 = 2 * tbi * CF_TB - 1;
+        const EnBlk bk = en_blk((unsigned)min(blk_, blk1 - 1), ta_n, tb_n);   // (past the end: the last block again, never used)
+        const int n = bk.n, tai = bk.tai, tbi = bk.tbi;
+        // (inline: mirrors conv_first_fused_k's patch loads, branch-free, and below its stores)
+        const int ih0 = 2 * tai * EN_TA - 1, iw0 = 2 * tbi * EN_TB - 1;
         if constexpr (MODE == 0) {
             const float* xf = p.x + frame_off_u32(p.fm, n);
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int row = 2 * (w + 8 * it) + (lane >> 5);
-                const int c = row / CF_PA, r = row - c * CF_PA;
+                const int c = row / EN_PA, r = row - c * EN_PA;
                 const int ih = ih0 + r, iw = iw0 + 1 + (lane & 31);
                 const bool ok = row < R0 && ih >= 0 && ih < p.IH && iw < p.IW;
                 const float v = xf[ok ? ((size_t)c * p.IH + ih) * p.IW + iw : 0];
                 st.pv[it] = ok ? v : 0.f;
             }
             {
-                const int c = tid / CF_PA, r = tid - c * CF_PA;
+                const int c = tid / EN_PA, r = tid - c * EN_PA;
                 const int ih = ih0 + r;
                 const bool ok = tid < R0 && ih >= 0 && ih < p.IH && iw0 >= 0;
                 const float v = xf[ok ? ((size_t)c * p.IH + ih) * p.IW + iw0 : 0];
@@ -545,12 +510,13 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
             st.hv = 0.f;
         }
         // the dY tile: thread -> pixel rows (2 w + i2) * 8 + lane / 8, swizzled 16-byte chunk lane % 8 of channel tile q
+        // (inline: mirrors wgrad_first_k's stage_dy)
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
             const int r = (2 * w + i2) * 8 + (lane >> 3);
-            const int oh = tai * CF_TA + (r >> 4), ow = tbi * CF_TB + (r & 15);
+            const int oh = tai * EN_TA + (r >> 4), ow = tbi * EN_TB + (r & 15);
             const bool v = oh < p.OH && ow < p.OW;
-            const unsigned char* src = p.dY + ((size_t)(n * p.OH + oh) * p.OW + ow) * ((size_t)p.ldy * 2) + co0 * 2 +
+            const unsigned char* src = p.dY + (en_pix_row(n, p.OH, p.OW, oh, ow)) * ((size_t)p.ldy * 2) + co0 * 2 +
                                        (((lane & 7) ^ tr_swz<128>(r)) * 16);
 #pragma unroll
             for (int q = 0; q < 4; ++q) st.dy[q * 2 + i2] = *(const u32x4_t*)(v ? src + q * 128 : p.zero);
@@ -561,15 +527,15 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int row = 2 * (w + 8 * it) + (lane >> 5);
-                if (row < R0) s_patch[row * CF_PP + 1 + (lane & 31)] = st.pv[it];
+                if (row < R0) s_patch[row * EN_PP + 1 + (lane & 31)] = st.pv[it];
             }
-            if (tid < R0) s_patch[tid * CF_PP] = st.hv;
+            if (tid < R0) s_patch[tid * EN_PP] = st.hv;
         } else {
 #pragma unroll
             for (int it = 0; it < PIT; ++it) {
                 const int i = it * 512 + tid;
                 const int r = i / RUN, j = i - r * RUN;
-                if (i < PN) s_patch[r * (CF_PP * CIN) + j] = st.pv[it];
+                if (i < PN) s_patch[r * (EN_PP * CIN) + j] = st.pv[it];
             }
         }
 #pragma unroll
@@ -584,9 +550,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
     const int qq = fi >> 2, pp = fi & 3;
     const int mt = w & 3, nt0 = (w >> 2) * 2;
     const int row0 = 8 * fg + qq;
-    const int offA = row0 * 128 + (((mt * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
-    const int offB0 = row0 * 128 + (((nt0 * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
-    const int offB1 = row0 * 128 + ((((nt0 + 1) * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
+    const int offA = en_tr_off(row0, mt, pp), offB0 = en_tr_off(row0, nt0, pp), offB1 = en_tr_off(row0, nt0 + 1, pp);
     f32x4_t acc[4][2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { acc[q][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[q][1] = acc[q][0]; }
@@ -597,28 +561,26 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
         store_block(st, buf);
         load_block(blk + 2, st);
         lds_barrier();
-        // im2col rows: 128 rows x 8 chunks of 8 columns
+        // im2col rows: 128 rows x 8 chunks of 8 columns (inline: mirrors wgrad_first_k's row build)
 #pragma unroll
         for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
             const int i = i0 + tid;
             const int r = i >> 3, c = i & 7;
             const int oy = r >> 4, ox = r & 15;
-            const int corner = (2 * oy * CF_PP + 2 * ox) * (MODE == 0 ? 1 : CIN);
+            const int corner = (2 * oy * EN_PP + 2 * ox) * (MODE == 0 ? 1 : CIN);
             unsigned short e[8];
 #pragma unroll
-            for (int k8 = 0; k8 < 8; ++k8) {
-                const float v = koff[k8] >= 0 ? s_patch[corner + max(koff[k8], 0)] : 0.f;
-                e[k8] = f32_to_bf16(v);
-            }
+            for (int k8 = 0; k8 < 8; ++k8) e[k8] = en_col_elem(s_patch, corner, koff[k8]);
             u32x4_t pk;
-            pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
-            pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
+            pk[0] = en_pack2(e[0], e[1]); pk[1] = en_pack2(e[2], e[3]);
+            pk[2] = en_pack2(e[4], e[5]); pk[3] = en_pack2(e[6], e[7]);
             *(u32x4_t*)(s_col + r * 128 + ((c ^ tr_swz<128>(r)) * 16)) = pk;
         }
         lds_barrier();
         const unsigned la = l_dy + buf * (4 * 16384);
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
+            // (inline: mirrors wgrad_first_k's reads and tied wait, with four dY images)
             s16x4_t al[4], ah[4], b0l, b0h, b1l, b1h;
             const unsigned ada = la + offA + kb * (32 * 128), adb0 = l_col + offB0 + kb * (32 * 128), adb1 = l_col + offB1 + kb * (32 * 128);
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(b0l) : "v"(adb0));
@@ -636,11 +598,10 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(b0l), "+v"(b0h), "+v"(b1l), "+v"(b1h), "+v"(al[0]), "+v"(ah[0]), "+v"(al[1]), "+v"(ah[1]), "+v"(al[2]),
                            "+v"(ah[2]), "+v"(al[3]), "+v"(ah[3]));
-            const bf16x8_t fb0 = bf16x8_t{b0l[0], b0l[1], b0l[2], b0l[3], b0h[0], b0h[1], b0h[2], b0h[3]};
-            const bf16x8_t fb1 = bf16x8_t{b1l[0], b1l[1], b1l[2], b1l[3], b1h[0], b1h[1], b1h[2], b1h[3]};
+            const bf16x8_t fb0 = en_tr_frag(b0l, b0h), fb1 = en_tr_frag(b1l, b1h);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const bf16x8_t fa = bf16x8_t{al[q][0], al[q][1], al[q][2], al[q][3], ah[q][0], ah[q][1], ah[q][2], ah[q][3]};
+                const bf16x8_t fa = en_tr_frag(al[q], ah[q]);
                 acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0, fa, acc[q][0], 0, 0, 0);
                 acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1, fa, acc[q][1], 0, 0, 0);
             }
@@ -666,54 +627,34 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
 }
 
 static int wf_shape_ok(int dtype, int Cin, int IH, int IW, int Nout, int N) {
-    const int OH = (IH + 2 - 3) / 2 + 1, OW = (IW + 2 - 3) / 2 + 1;
+    const int OH = ends_out_dim(IH), OW = ends_out_dim(IW);
     return dtype == RBVAE_BF16 && Cin >= 1 && Cin <= 4 && Nout >= 64 && Nout % 64 == 0 && N >= 1 && IH >= 1 && IW >= 1 &&
            (long)N * OH * OW * 256 < (1l << 31) && (long)N * Cin * IH * IW < (1l << 40);
 }
-template <int CIN, int MODE> static void wf_launch_wide(const WfArgs& a, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_first_wide_k<CIN, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, WFW_LDS);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((wgrad_first_wide_k<CIN, MODE>), dim3((a.Nout / 256) * a.ksplit), dim3(512), WFW_LDS, st, a);
-}
 template <int MODE> static void wf_launch(const WfArgs& a, hipStream_t st) {
-    if (a.Nout % 256 == 0) {           // all 256 channels of a block in one workgroup: the im2col rows are built once, not four times
-        switch (a.Cin) {
-            case 1: wf_launch_wide<1, MODE>(a, st); break;
-            case 2: wf_launch_wide<2, MODE>(a, st); break;
-            case 3: wf_launch_wide<3, MODE>(a, st); break;
-            default: wf_launch_wide<4, MODE>(a, st); break;
+    en_for_cin(a.Cin, [&](auto cin) {
+        constexpr int CIN = decltype(cin)::value;
+        if (a.Nout % 256 == 0) {       // all 256 channels of a block in one workgroup: the im2col rows are built once, not four times
+            lds_attr_once<wgrad_first_wide_k<CIN, MODE>>(WFW_LDS);
+            hipLaunchKernelGGL((wgrad_first_wide_k<CIN, MODE>), dim3((a.Nout / 256) * a.ksplit), dim3(512), WFW_LDS, st, a);
+        } else {
+            hipLaunchKernelGGL((wgrad_first_k<CIN, MODE>), dim3((a.Nout / 64) * a.ksplit), dim3(512), 0, st, a);
         }
-        return;
-    }
-    const int blocks = (a.Nout / 64) * a.ksplit;
-    switch (a.Cin) {
-        case 1: hipLaunchKernelGGL((wgrad_first_k<1, MODE>), dim3(blocks), dim3(512), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((wgrad_first_k<2, MODE>), dim3(blocks), dim3(512), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((wgrad_first_k<3, MODE>), dim3(blocks), dim3(512), 0, st, a); break;
-        default: hipLaunchKernelGGL((wgrad_first_k<4, MODE>), dim3(blocks), dim3(512), 0, st, a); break;
-    }
+    });
 }
 
 static int cf_shape_ok(int dtype, int Cin, int IH, int IW, int Nout, int N) {
-    const int OH = (IH + 2 - 3) / 2 + 1, OW = (IW + 2 - 3) / 2 + 1;
+    const int OH = ends_out_dim(IH), OW = ends_out_dim(IW);
     return dtype == RBVAE_BF16 && Cin >= 1 && Cin <= 4 && Nout >= 8 && Nout <= 256 && Nout % 8 == 0 && N >= 1 && IH >= 1 &&
            IW >= 1 && (long)N * OH * OW * 256 < (1l << 31) && (long)N * Cin * IH * IW < (1l << 40);
 }
-
-template <int MODE, int NQ> static void cf_launch_nq(const CfArgs& a, hipStream_t st) {
-    const int blocks = a.N * cdiv(a.OH, CF_TA) * cdiv(a.OW, CF_TB);
-    switch (a.Cin) {
-        case 1: hipLaunchKernelGGL((conv_first_fused_k<1, MODE, NQ>), dim3(blocks), dim3(512), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((conv_first_fused_k<2, MODE, NQ>), dim3(blocks), dim3(512), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((conv_first_fused_k<3, MODE, NQ>), dim3(blocks), dim3(512), 0, st, a); break;
-        default: hipLaunchKernelGGL((conv_first_fused_k<4, MODE, NQ>), dim3(blocks), dim3(512), 0, st, a); break;
-    }
-}
 template <int MODE> static void cf_launch(const CfArgs& a, hipStream_t st) {
-    if (a.Nout <= 64) cf_launch_nq<MODE, 1>(a, st); else cf_launch_nq<MODE, 4>(a, st);
+    const int blocks = en_blocks(a.N, a.OH, a.OW);
+    en_for_cin(a.Cin, [&](auto cin) {
+        constexpr int CIN = decltype(cin)::value;
+        if (a.Nout <= 64) hipLaunchKernelGGL((conv_first_fused_k<CIN, MODE, 1>), dim3(blocks), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((conv_first_fused_k<CIN, MODE, 4>), dim3(blocks), dim3(512), 0, st, a);
+    });
 }
 
 }  // namespace rbvae
@@ -742,7 +683,7 @@ extern "C" int rbvae_conv_first_fused(int dtype, const float* x, int fd1, int fd
     a.x = x; a.fm = FrameMap{fd1, fd2, fs0, fs1, fs2}; a.W = (const unsigned char*)W; a.bias = bias;
     a.zero = (const unsigned char*)zero_page; a.col = (unsigned char*)col; a.out = (unsigned char*)out;
     a.gate = nullptr; a.colsum_ws = nullptr;
-    a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = (IH + 2 - 3) / 2 + 1; a.OW = (IW + 2 - 3) / 2 + 1;
+    a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = ends_out_dim(IH); a.OW = ends_out_dim(IW);
     a.Nout = Nout; a.ldo = ldo; a.relu = relu; a.drop_mode = drop_mode; a.scale = scale;
     a.drop_thresh = drop_thresh; a.seed = seed; a.seed_dev = seed_dev;
     cf_launch<0>(a, (hipStream_t)stream);
@@ -753,7 +694,7 @@ extern "C" int rbvae_conv_first_fused(int dtype, const float* x, int fd1, int fd
 /* workgroups (= rows of colsum_ws) of rbvae_deconv_last_dgrad_fused; 0 when the shape is outside the fused kernel */
 extern "C" int rbvae_deconv_last_dgrad_blocks(int dtype, int Cout, int OH, int OW, int C1, int N) {
     if (!cf_shape_ok(dtype, Cout, OH, OW, C1, N)) return 0;
-    return N * cdiv((OH + 2 - 3) / 2 + 1, CF_TA) * cdiv((OW + 2 - 3) / 2 + 1, CF_TB);
+    return en_blocks(N, ends_out_dim(OH), ends_out_dim(OW));
 }
 
 extern "C" int rbvae_deconv_last_dgrad_fused(int dtype, const float* dpre, const void* W, const void* zero_page, void* col,
@@ -769,7 +710,7 @@ extern "C" int rbvae_deconv_last_dgrad_fused(int dtype, const float* dpre, const
     a.x = dpre; a.fm = FrameMap{0, 0, 0, 0, 0}; a.W = (const unsigned char*)W; a.bias = nullptr;
     a.zero = (const unsigned char*)zero_page; a.col = (unsigned char*)col; a.out = (unsigned char*)out;
     a.gate = (const unsigned char*)gate; a.colsum_ws = colsum_ws;
-    a.N = N; a.Cin = Cout; a.IH = OH; a.IW = OW; a.OH = (OH + 2 - 3) / 2 + 1; a.OW = (OW + 2 - 3) / 2 + 1;
+    a.N = N; a.Cin = Cout; a.IH = OH; a.IW = OW; a.OH = ends_out_dim(OH); a.OW = ends_out_dim(OW);
     a.Nout = C1; a.ldo = ldo; a.relu = 0; a.drop_mode = 0; a.scale = scale; a.drop_thresh = 0; a.seed = 0; a.seed_dev = nullptr;
     cf_launch<1>(a, (hipStream_t)stream);
     RBVAE_CHECK_LAUNCH("deconv_last_dgrad_fused");
@@ -780,7 +721,7 @@ extern "C" int rbvae_deconv_last_dgrad_fused(int dtype, const float* dpre, const
  * (bf16, Cin <= 4, Nout a multiple of 64) */
 extern "C" int rbvae_wgrad_first_blocks(int dtype, int Cin, int IH, int IW, int Nout, int N) {
     if (!wf_shape_ok(dtype, Cin, IH, IW, Nout, N)) return 0;
-    return N * cdiv((IH + 2 - 3) / 2 + 1, CF_TA) * cdiv((IW + 2 - 3) / 2 + 1, CF_TB);
+    return en_blocks(N, ends_out_dim(IH), ends_out_dim(IW));
 }
 
 extern "C" int rbvae_wgrad_first(int dtype, int mode, const float* x, int fd1, int fd2, long fs0, long fs1, long fs2, const void* dY,
@@ -795,9 +736,9 @@ extern "C" int rbvae_wgrad_first(int dtype, int mode, const float* x, int fd1, i
     WfArgs a;
     a.x = x; a.fm = mode == 0 ? FrameMap{fd1, fd2, fs0, fs1, fs2} : FrameMap{0, 0, 0, 0, 0};
     a.dY = (const unsigned char*)dY; a.zero = (const unsigned char*)zero_page; a.dW = dW_slabs;
-    a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = (IH + 2 - 3) / 2 + 1; a.OW = (IW + 2 - 3) / 2 + 1;
+    a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.OH = ends_out_dim(IH); a.OW = ends_out_dim(IW);
     a.Nout = Nout; a.ldy = ldy;
-    a.nblk = N * cdiv(a.OH, CF_TA) * cdiv(a.OW, CF_TB);
+    a.nblk = en_blocks(N, a.OH, a.OW);
     RBVAE_CHECK_ARG(ksplit >= 1 && ksplit <= a.nblk, "wgrad_first: ksplit=%d (1 .. %d blocks)", ksplit, a.nblk);
     a.ksplit = ksplit; a.per = cdiv(a.nblk, ksplit);
     if (mode == 0) wf_launch<0>(a, (hipStream_t)stream); else wf_launch<1>(a, (hipStream_t)stream);

@@ -146,14 +146,6 @@ template <typename T, int RING> constexpr int ch_lds_main() {
     constexpr int epi = CH_BM * (CH_BN * (int)sizeof(T) + 16);
     return ring > epi ? ring : epi;
 }
-// once per kernel instance: allow `bytes` of dynamic LDS
-template <auto KERNEL> static inline void ch_lds_attr_once(int bytes) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        attr_set = true;
-    }
-}
 // row pitches and pointer alignment of the wrapper named `who` (ptrs: every pointer of the call OR-ed together)
 static inline int ch_check_rows(const char* who, int ES, int Kc, int Nout, int lda, int ldo, uintptr_t ptrs) {
     RBVAE_CHECK_ARG(lda >= Kc && (lda * ES) % 16 == 0 && ldo >= Nout && (ldo * ES) % 16 == 0,

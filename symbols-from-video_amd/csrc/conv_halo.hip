@@ -505,7 +505,7 @@ template <typename T, int RING, bool GN>
 static int launch_ch(const ChArgs& a, hipStream_t st) {
     const size_t lds = (size_t)ch_lds_main<T, RING>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + (a.gn_scale ? (size_t)2 * a.Kc * 4 : 0) + 16;
     if (lds > 160 * 1024) return fail(RBVAE_E_UNSUPPORTED, "conv3x3_halo: %zu bytes of LDS", lds);
-    ch_lds_attr_once<conv_halo_k<T, RING, GN>>(160 * 1024);
+    lds_attr_once<conv_halo_k<T, RING, GN>>(160 * 1024);
     hipLaunchKernelGGL((conv_halo_k<T, RING, GN>), dim3(a.total), dim3(512), lds, st, a);
     RBVAE_CHECK_LAUNCH("conv3x3_halo");
     return RBVAE_OK;

@@ -596,8 +596,8 @@ int launch_ch_ws(const ChArgs& a, hipStream_t st) {
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
     }
-    ch_lds_attr_once<conv_halo_ws_k<true>>(CW_LDS);
-    ch_lds_attr_once<conv_halo_ws_k<false>>(CW_LDS);
+    lds_attr_once<conv_halo_ws_k<true>>(CW_LDS);
+    lds_attr_once<conv_halo_ws_k<false>>(CW_LDS);
     const int grid = a.total < ncu ? a.total : ncu;
     if (a.gn_scale) hipLaunchKernelGGL((conv_halo_ws_k<true>), dim3(grid), dim3(768), CW_LDS, st, a);
     else hipLaunchKernelGGL((conv_halo_ws_k<false>), dim3(grid), dim3(768), CW_LDS, st, a);

@@ -11,7 +11,9 @@
 // the accumulators, 32 bytes per lane and pixel.  Statistics: per workgroup tile and group of cg channels the mean and the
 // sum of squared deviations of the STORED (bf16) values, two passes over the registers, merged over lanes by DPP row sums
 // and over waves through LDS; rbvae_gn_finish_tiles (tile 8 x 16) merges the tiles.
-#include "mma.h"
+// What it has in common with conv_first_fused_k as one definition is in ends.h; "(inline: mirrors ...)" marks a step that is
+// typed out here as well because every helper form tried changed a listing ("Shared steps of the end kernels").
+#include "ends.h"
 #include <stdlib.h>
 
 namespace rbvae {
@@ -26,19 +28,8 @@ struct CiArgs {
     int N, Cin, H, Wd, Nout, ldo, cg;
 };
 
-constexpr int CI_TA = 8, CI_TB = 16;                  // output block
-constexpr int CI_PA = CI_TA + 2, CI_PB = CI_TB + 2;   // input patch 10 x 18
+constexpr int CI_PA = EN_TA + 2, CI_PB = EN_TB + 2;   // input patch 10 x 18
 constexpr int CI_PP = CI_PB + 1;                      // patch row pitch (floats)
-
-template <int CIN> struct CiOff {
-    int v[64];
-    constexpr CiOff() : v{} {
-        for (int k = 0; k < 64; ++k) {
-            const int t = k / CIN, ci = k % CIN, kh = t / 3, kw = t % 3;
-            v[k] = k >= 9 * CIN ? -1 : (ci * CI_PA + kh) * CI_PP + kw;
-        }
-    }
-};
 
 // NQ = 64-channel quads of the tile (Nout <= 64 NQ); wave = quad w % NQ x pixel tiles NQ (w / NQ) .. + NQ - 1
 template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) void conv_in_k(const CiArgs p) {
@@ -49,22 +40,19 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
     __shared__ float s_patch[4 * CI_PA * CI_PP];
     __shared__ float s_red[NWM * 64 * NQ];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int tb_n = (p.Wd + CI_TB - 1) / CI_TB, ta_n = (p.H + CI_TA - 1) / CI_TA;
-    unsigned blk = blockIdx.x;
-    const int tbi = blk % (unsigned)tb_n; blk /= (unsigned)tb_n;
-    const int tai = blk % (unsigned)ta_n;
-    const int n = blk / (unsigned)ta_n;
-    const int oh0 = tai * CI_TA, ow0 = tbi * CI_TB;
+    const int tb_n = en_tb_n(p.Wd), ta_n = en_ta_n(p.H);
+    const EnBlk bk = en_blk(blockIdx.x, ta_n, tb_n);
+    const int n = bk.n, oh0 = bk.tai * EN_TA, ow0 = bk.tbi * EN_TB;
 
     // weights -> LDS by LDS-DMA: image row ct*16 + j holds channel 64*(ct/4) + 16*(j/4) + 4*(ct%4) + j%4, so that a lane's
-    // accumulators of a tile quad are 16 consecutive channels (conv_first_fused_k's layout)
+    // accumulators of a tile quad are 16 consecutive channels (inline: mirrors conv_first_fused_k's weight staging)
     {
         const int srow = lane >> 3, schunk = lane & 7;
         for (int q = w; q < 8 * NQ; q += 8) {
             const int r = q * 8 + srow;
             const int ct = r >> 4, j = r & 15;
             const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
-            const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + ((schunk ^ ((r >> 1) & 7)) * 16) : p.zero;
+            const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + en_swz16(r, schunk) : p.zero;
             glds16(src, s_b + (size_t)(r - srow) * 128);
         }
     }
@@ -78,7 +66,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         bz4[h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (p.bias && col + 4 * h < p.Nout) bz4[h] = *(const f32x4_t*)(p.bias + col + 4 * h);
     }
-    static constexpr CiOff<CIN> otab{};
+    static constexpr EnOff<CIN, 0, CI_PA, CI_PP> otab{};
     int koff[8];
 #pragma unroll
     for (int k8 = 0; k8 < 8; ++k8) koff[k8] = otab.v[(tid & 7) * 8 + k8];
@@ -106,7 +94,8 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
 #pragma unroll
     for (int h = 0; h < 4; ++h) asm volatile("" : "+v"(bz4[h]));
     __syncthreads();
-    // im2col rows: 128 rows x 8 chunks of 8 columns
+    // im2col rows: 128 rows x 8 chunks of 8 columns (inline: mirrors conv_first_fused_k's row build at stride 1; here also the
+    // element, which as ends.h's en_col_elem changes all twelve instances)
 #pragma unroll
     for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
         const int i = i0 + tid;
@@ -120,13 +109,13 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
             e[k8] = f32_to_bf16(v);
         }
         u32x4_t pk;
-        pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
-        pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
-        *(u32x4_t*)(s_a + r * 128 + ((c ^ ((r >> 1) & 7)) * 16)) = pk;
+        pk[0] = en_pack2(e[0], e[1]); pk[1] = en_pack2(e[2], e[3]);
+        pk[2] = en_pack2(e[4], e[5]); pk[3] = en_pack2(e[6], e[7]);
+        *(u32x4_t*)(s_a + en_a_off(r, c)) = pk;
     }
     __syncthreads();
 
-    // 128 x 64 NQ x 64 on the matrix cores
+    // 128 x 64 NQ x 64 on the matrix cores (inline: mirrors conv_first_fused_k's block; the chunk offset and the MFMA are ends.h's)
     const int fsw = (fi >> 1) & 7;
     f32x4_t acc[MT][4];
 #pragma unroll
@@ -135,7 +124,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         for (int h = 0; h < 4; ++h) acc[mt][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int ch = ((4 * kk + fg) ^ fsw) * 16;
+        const int ch = en_frag_ch(kk, fg, fsw);
         u32x4_t wv[4], av[MT];
 #pragma unroll
         for (int h = 0; h < 4; ++h) wv[h] = *(const u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);
@@ -145,8 +134,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int h = 0; h < 4; ++h)
-                acc[mt][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&wv[h], *(const bf16x8_t*)&av[mt],
-                                                                     acc[mt][h], 0, 0, 0);
+                acc[mt][h] = en_mma(wv[h], av[mt], acc[mt][h]);
     }
     // epilogue from registers: lane = pixel fi of tile mt, channels 64*wq + 16*fg .. +15 (two 16-byte chunks); the stored
     // (rounded) values stay in xs for the statistics
@@ -157,7 +145,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         const int r = (MT * wm + mt) * 16 + fi;
         const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
         live[mt] = oh < p.H && ow < p.Wd && first;
-        const size_t orow = (size_t)(n * p.H + oh) * p.Wd + ow;
+        const size_t orow = en_pix_row(n, p.H, p.Wd, oh, ow);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             u32x4_t val;
@@ -201,7 +189,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         for (int g = 0; g < 4; ++g)
             if (g < ngl) s_red[wm * RW + gbase + g] = gs[g];
     }
-    const int vh = min(CI_TA, p.H - oh0), vw = min(CI_TB, p.Wd - ow0);
+    const int vh = min(EN_TA, p.H - oh0), vw = min(EN_TB, p.Wd - ow0);
     const float cnt = (float)(vh * vw * cg);                   // values per group in this tile
     __syncthreads();
     float mean[4];
@@ -267,7 +255,7 @@ int rbvae_conv_in_ok(int dtype, int Cin, int H, int W, int Nout, int N, int cg) 
 
 /* floats of stats_part: (mean, M2) per image, 8 x 16 tile and group */
 size_t rbvae_conv_in_stats_floats(int N, int H, int W, int Nout, int cg) {
-    return (size_t)2 * N * cdiv(H, CI_TA) * cdiv(W, CI_TB) * (Nout / cg);
+    return (size_t)2 * en_blocks(N, H, W) * (Nout / cg);
 }
 
 int rbvae_conv_in(int dtype, const float* x, const void* W, const float* bias, const void* zero_page, void* out, float* stats_part,
@@ -281,18 +269,16 @@ int rbvae_conv_in(int dtype, const float* x, const void* W, const float* bias, c
     CiArgs a;
     a.x = x; a.W = (const unsigned char*)W; a.bias = bias; a.zero = (const unsigned char*)zero_page; a.out = (unsigned char*)out;
     a.stats = (float2*)stats_part; a.N = N; a.Cin = Cin; a.H = H; a.Wd = Wd; a.Nout = Nout; a.ldo = ldo; a.cg = stats_part ? cg : 0;
-    const int blocks = N * cdiv(H, CI_TA) * cdiv(Wd, CI_TB);
-    hipStream_t st = (hipStream_t)stream;
-#define CI_LAUNCH(C, Q) hipLaunchKernelGGL((conv_in_k<C, Q>), dim3(blocks), dim3(512), 0, st, a)
-#define CI_NQ(C) do { if (Nout <= 64) CI_LAUNCH(C, 1); else if (Nout <= 128) CI_LAUNCH(C, 2); else CI_LAUNCH(C, 4); } while (0)
-    switch (Cin) {
-        case 1: CI_NQ(1); break;
-        case 2: CI_NQ(2); break;
-        case 3: CI_NQ(3); break;
-        default: CI_NQ(4); break;
-    }
-#undef CI_NQ
-#undef CI_LAUNCH
+    const int blocks = en_blocks(N, H, Wd);
+    en_for_cin(Cin, [&](auto cin) {
+        constexpr int CIN = decltype(cin)::value;
+        const auto launch = [&](auto nq) {
+            hipLaunchKernelGGL((conv_in_k<CIN, decltype(nq)::value>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, a);
+        };
+        if (Nout <= 64) launch(std::integral_constant<int, 1>{});
+        else if (Nout <= 128) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 4>{});
+    });
     RBVAE_CHECK_LAUNCH("conv_in");
     return RBVAE_OK;
 }

@@ -16,6 +16,10 @@
 //   Then conv_first_fused_k<MODE 1>'s steps on the 17 x 33 patch of dpre: im2col rows (to LDS and, when asked for, to
 //   `col`), 128 x C1 x 64 on the matrix cores, scale, gate (the bits), dd2 as 16-byte chunks of NHWC rows,
 //   column sums of the stored values.
+//   The steps this kernel has in common with those two are ends.h's (block decode, offset table, swizzles, fragment reads,
+//   MFMA, sigmoid and dpre, the fixed-order sums); where a step is typed out here although the other kernel has it too, the
+//   comment "(inline: mirrors ...)" names the copy, and DESIGN.md ("Shared steps of the end kernels") says which forms of a
+//   helper changed a listing.
 //
 // LDS (dynamic; KS = C1 / 64 slices, NBUF = 2 slice buffers (1 for C1 = 64), NQ = 4 for C1 > 64 else 1):
 //   [0, NBUF*30720)                   d2 tile slice [NBUF][192][128 B] + V slice [NBUF][48][128 B], swizzled 16-byte chunks
@@ -30,7 +34,7 @@
 // 117-123 for C1 = 64, no scratch, no spills.  Barriers behind global stores are lds_barrier() (LDS only): with
 // __syncthreads() every one of them waited for the x_recon / dpre / col / dd2 stores in flight (23.3 -> 21.7 us at the bench
 // shape; DESIGN.md 5, profiles/deconv_last_bwd_ab.txt).
-#include "mma.h"
+#include "ends.h"
 #include <stdlib.h>
 
 namespace rbvae {
@@ -53,30 +57,17 @@ struct FbArgs {
     int N, IH, IW, C1, NYP;
 };
 
-constexpr int FB_TA = 8, FB_TB = 16;                    // owned d2 block
-constexpr int FB_HB = FB_TB + 2;                        // staged tile 10 x 18
-constexpr int FB_PIX = (FB_TA + 2) * FB_HB;             // 180
-constexpr int FB_MROWS = 192, FB_WROWS = 48, FB_YP = 37;
-constexpr int FB_PA = 2 * FB_TA + 1, FB_PB = 2 * FB_TB + 1, FB_PP = FB_PB + 1;      // dpre patch 17 x 33, pitch 34
-constexpr int FB_PATCH_BYTES = 4 * FB_PA * FB_PP * 4;
-constexpr int FB_RIM = FB_PB + 2 * FB_TA;               // 49
-
-// patch offset of im2col column k = (kh*3+kw)*CIN + ci relative to the d2 pixel's corner; -1 = padding column
-template <int CIN> struct FbOff {
-    int v[64];
-    constexpr FbOff() : v{} {
-        for (int k = 0; k < 64; ++k) {
-            const int t = k / CIN, ci = k % CIN, kh = t / 3, kw = t % 3;
-            v[k] = k >= 9 * CIN ? -1 : (kh * FB_PP + kw) * CIN + ci;
-        }
-    }
-};
+constexpr int FB_HB = EN_TB + 2;                        // staged tile 10 x 18
+constexpr int FB_PIX = (EN_TA + 2) * FB_HB;             // 180
+constexpr int FB_MROWS = 192;
+constexpr int FB_PATCH_BYTES = 4 * EN_PA * EN_PP * 4;
+constexpr int FB_RIM = EN_PB + 2 * EN_TA;               // 49
 
 // slice buffers (two for a layer of several slices), over them later Y and then the im2col rows + W
 static size_t fb_region(int C1) {
     const int NBUF = C1 > 64 ? 2 : 1, NQ = C1 > 64 ? 4 : 1;
-    size_t b = (size_t)NBUF * (FB_MROWS + FB_WROWS) * 128;
-    if (b < (size_t)FB_MROWS * FB_YP * 4) b = (size_t)FB_MROWS * FB_YP * 4;
+    size_t b = (size_t)NBUF * (FB_MROWS + EN_WROWS) * 128;
+    if (b < (size_t)FB_MROWS * EN_YP * 4) b = (size_t)FB_MROWS * EN_YP * 4;
     if (b < (size_t)16384 + NQ * 8192) b = (size_t)16384 + NQ * 8192;
     return b;
 }
@@ -89,12 +80,12 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
     constexpr int MT = NQ == 4 ? 4 : 1;
     const int KS = p.C1 >> 6;
     constexpr int NBUF = NQ == 4 ? 2 : 1;                                    // NQ == 1: one slice in all
-    constexpr int REGION = (NBUF * (FB_MROWS + FB_WROWS) * 128 > FB_MROWS * FB_YP * 4) ? NBUF * (FB_MROWS + FB_WROWS) * 128
-                                                                                      : FB_MROWS * FB_YP * 4;
+    constexpr int REGION = (NBUF * (FB_MROWS + EN_WROWS) * 128 > FB_MROWS * EN_YP * 4) ? NBUF * (FB_MROWS + EN_WROWS) * 128
+                                                                                      : FB_MROWS * EN_YP * 4;
     static_assert(REGION >= 16384 + NQ * 8192, "the im2col rows and W take the slices' place");
     unsigned char* s_pix = smem;                                             // [NBUF][FB_MROWS][128]
-    unsigned char* s_wts = smem + NBUF * FB_MROWS * 128;                     // [NBUF][FB_WROWS][128]
-    float* s_y = (float*)smem;                                               // [FB_MROWS][FB_YP], once the slices are dead
+    unsigned char* s_wts = smem + NBUF * FB_MROWS * 128;                     // [NBUF][EN_WROWS][128]
+    float* s_y = (float*)smem;                                               // [FB_MROWS][EN_YP], once the slices are dead
     unsigned char* s_a = smem;                                               // [128][128], once Y is dead
     unsigned char* s_b = smem + 16384;                                       // [64 NQ][128]
     float* s_patch = (float*)(smem + REGION);                                // [17][34][CIN]
@@ -102,15 +93,13 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int OH = 2 * p.IH, OW = 2 * p.IW;
-    const int tb_n = (p.IW + FB_TB - 1) / FB_TB, ta_n = (p.IH + FB_TA - 1) / FB_TA;
-    unsigned blk = blockIdx.x;
-    const int tbi = blk % (unsigned)tb_n; blk /= (unsigned)tb_n;
-    const int tai = blk % (unsigned)ta_n;
-    const int n = blk / (unsigned)ta_n;
-    const int a0 = tai * FB_TA, b0 = tbi * FB_TB;
+    const int tb_n = en_tb_n(p.IW), ta_n = en_ta_n(p.IH);
+    const EnBlk bk = en_blk(blockIdx.x, ta_n, tb_n);
+    const int n = bk.n, a0 = bk.tai * EN_TA, b0 = bk.tbi * EN_TB;
 
     // the input gradient's weight, through registers: asked for first (the oldest loads of the wave:
     // landed long before the counted waits below), written to LDS once Y is dead (its place)
+    // (inline: mirrors the row permutation of conv_first_fused_k's weight tile)
     u32x4_t wreg[NQ];
 #pragma unroll
     for (int it = 0; it < NQ; ++it) {
@@ -118,14 +107,14 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         const int r = idx >> 3, sc = idx & 7;
         const int ct = r >> 4, j = r & 15;
         const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
-        wreg[it] = *(const u32x4_t*)(ch < p.C1 ? p.W + (size_t)ch * 128 + ((sc ^ ((r >> 1) & 7)) * 16) : p.zero);
+        wreg[it] = *(const u32x4_t*)(ch < p.C1 ? p.W + (size_t)ch * 128 + en_swz16(r, sc) : p.zero);
     }
     // the patch starts as zeros: output pixels outside the image and channels never written read as padding
     for (int i = tid; i < FB_PATCH_BYTES / 4; i += 512) s_patch[i] = 0.f;
 
-    // ---- epilogue operands that depend on nothing, asked for first (deconv_last_fused_k): waves 0-3 the two output pixels
-    // a thread owns, waves 4-7 one rim pixel
-    constexpr int EPI = (2 * FB_TA * 2 * FB_TB) / 256;
+    // ---- epilogue operands that depend on nothing, asked for first: waves 0-3 the two output pixels a thread owns, waves 4-7
+    // one rim pixel (inline: mirrors deconv_last_fused_k's prefetch, with the rim arm)
+    constexpr int EPI = (2 * EN_TA * 2 * EN_TB) / 256;
     const int OHW = OH * OW;
     float tg[EPI][4], bz[4];
 #pragma unroll
@@ -133,14 +122,14 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
     int rim_oh = -1, rim_ow = -1, rim_pos = 0;
     if (w >= 4) {
         const int j = tid - 256;
-        if (j < FB_PB) { rim_oh = 2 * a0 - 1; rim_ow = 2 * b0 - 1 + j; rim_pos = j; }
-        else if (j < FB_RIM) { rim_oh = 2 * a0 + (j - FB_PB); rim_ow = 2 * b0 - 1; rim_pos = (j - FB_PB + 1) * FB_PP; }
+        if (j < EN_PB) { rim_oh = 2 * a0 - 1; rim_ow = 2 * b0 - 1 + j; rim_pos = j; }
+        else if (j < FB_RIM) { rim_oh = 2 * a0 + (j - EN_PB); rim_ow = 2 * b0 - 1; rim_pos = (j - EN_PB + 1) * EN_PP; }
         if (rim_oh >= OH || rim_ow >= OW || rim_ow < 0) rim_oh = -1;
     }
 #pragma unroll
     for (int it = 0; it < EPI; ++it) {
         const int q = tid + 256 * it;
-        int oh = 2 * a0 + q / (2 * FB_TB), ow = 2 * b0 + q % (2 * FB_TB);
+        int oh = 2 * a0 + q / (2 * EN_TB), ow = 2 * b0 + q % (2 * EN_TB);
         bool ok = oh < OH && ow < OW;
         if (w >= 4) { oh = rim_oh; ow = rim_ow; ok = it == 0 && rim_oh >= 0; }
         const float* tp = p.target + (ok ? frame_off_u32(p.tfm, n) + (long)oh * OW + ow : 0);
@@ -148,12 +137,13 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         for (int c = 0; c < 4; ++c) tg[it][c] = (ok && c < Cout) ? tp[(long)c * OHW] : 0.f;
     }
 
-    // ---- stage d2 tile + V slice by slice (double buffer, slice s + 1 in flight under slice s's MFMAs as in
-    // deconv_last_fused_k): 30 LDS-DMA instructions of 8 rows per slice, q = w, w + 8, ...
+    // ---- stage d2 tile + V slice by slice (double buffer, slice s + 1 in flight under slice s's MFMAs): 30 LDS-DMA
+    // instructions of 8 rows per slice, q = w, w + 8, ... (inline: mirrors deconv_last_fused_k's piece table and slice loop; the
+    // tile here has a halo on all four sides and eight waves share it)
     const int srow = lane >> 3, schunk = lane & 7;
     const int fi = lane & 15, fg = lane >> 4;
     const int fsw = (fi >> 1) & 7;
-    constexpr int PIX_I = FB_MROWS / 8, WTS_I = FB_WROWS / 8;
+    constexpr int PIX_I = FB_MROWS / 8, WTS_I = EN_WROWS / 8;
     const unsigned char* psrc[4];
     unsigned pinc[4], pdst[4], pstep[4];
     {
@@ -162,21 +152,21 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
             const int q = w + 8 * i;
             const bool is_w = q >= PIX_I;
             const int r = (is_w ? q - PIX_I : q) * 8 + srow;
-            const int sw = (schunk ^ ((r >> 1) & 7)) * 16;
+            const int sw = en_swz16(r, schunk);
             const unsigned char* src = p.zero;
             unsigned inc = 0;
             if (is_w) {
-                if (r < p.NYP) { src = p.V + ((size_t)r * p.C1) * 2 + sw; inc = 128; }
+                if (r < p.NYP) { src = en_row_src(p.V, r, p.C1, sw); inc = 128; }
             } else if (r < FB_PIX) {
                 const int la = r / FB_HB, lb = r - la * FB_HB;
                 const int a = a0 - 1 + la, b = b0 - 1 + lb;
                 if (a >= 0 && a < p.IH && b >= 0 && b < p.IW) {
-                    src = p.D2 + ((size_t)((n * p.IH + a) * p.IW + b) * p.C1) * 2 + sw; inc = 128;
+                    src = en_row_src(p.D2, (n * p.IH + a) * p.IW + b, p.C1, sw); inc = 128;
                 }
             }
             psrc[i] = src; pinc[i] = inc;
             pdst[i] = (unsigned)((is_w ? (size_t)(s_wts - smem) : 0) + (size_t)(r - srow) * 128);
-            pstep[i] = is_w ? FB_WROWS * 128 : FB_MROWS * 128;
+            pstep[i] = is_w ? EN_WROWS * 128 : FB_MROWS * 128;
         }
     }
     auto stage = [&](int s, int buf) __attribute__((always_inline)) {
@@ -213,22 +203,18 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const unsigned ad = lds_pix + (unsigned)((buf * FB_MROWS + gtr) * 128 + (((2 * ggrp + h) ^ ((gtr >> 1) & 7)) * 16));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(gq[h]) : "v"(ad));
+            gq[h] = en_frag_asm(ad);
         }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            const int ch = ((4 * kk + fg) ^ fsw) * 16;
+            const int ch = en_frag_ch(kk, fg, fsw);
             u32x4_t wf[3], pf[2];
 #pragma unroll
-            for (int rt = 0; rt < 3; ++rt) {
-                const unsigned ad = lds_wts + (unsigned)((buf * FB_WROWS + rt * 16 + fi) * 128 + ch);
-                asm volatile("ds_read_b128 %0, %1" : "=v"(wf[rt]) : "v"(ad));
-            }
+            for (int rt = 0; rt < 3; ++rt) wf[rt] = en_frag_asm(lds_wts + (unsigned)((buf * EN_WROWS + rt * 16 + fi) * 128 + ch));
 #pragma unroll
             for (int pi = 0; pi < 2; ++pi) {
                 const int pt = pi == 0 ? w + 4 : (w & 3);                     // waves 4-7 have no second tile: read, not used
-                const unsigned ad = lds_pix + (unsigned)((buf * FB_MROWS + pt * 16 + fi) * 128 + ch);
-                asm volatile("ds_read_b128 %0, %1" : "=v"(pf[pi]) : "v"(ad));
+                pf[pi] = en_frag_asm(lds_pix + (unsigned)((buf * FB_MROWS + pt * 16 + fi) * 128 + ch));
             }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(pf[0]), "+v"(pf[1]), "+v"(gq[0]), "+v"(gq[1]));
 #pragma unroll
@@ -236,13 +222,12 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
                 if (pi == 0 || w < 4) {
 #pragma unroll
                     for (int rt = 0; rt < 3; ++rt)
-                        acc[pi][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&wf[rt],
-                                                                              *(const bf16x8_t*)&pf[pi], acc[pi][rt], 0, 0, 0);
+                        acc[pi][rt] = en_mma(wf[rt], pf[pi], acc[pi][rt]);
                 }
             }
         }
         {
-            // a bf16 pattern g is > 0 (NaN excluded) iff (g - 1) mod 2^16 < 0x7f80: conv_first_fused_k's gate, as bits
+            // a bf16 pattern g is > 0 (NaN excluded) iff (g - 1) mod 2^16 < 0x7f80: the test of conv_first_fused_k's gate, as bits
             unsigned bits = 0;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -266,6 +251,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
     for (int it = 0; it < NQ; ++it) asm volatile("" : "+v"(wreg[it]));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the gate bits this wave wrote
     __syncthreads();                     // every wave has read its last fragments: the products go where the slices were
+    // D[(tap,co) row 4g + r][pixel i] (inline: mirrors deconv_last_fused_k's Y store)
 #pragma unroll
     for (int pi = 0; pi < 2; ++pi) {
         const int pt = pi == 0 ? w + 4 : w;
@@ -275,22 +261,24 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int wr = rt * 16 + 4 * fg + r;
-                    if (wr < 36) s_y[(pt * 16 + fi) * FB_YP + wr] = acc[pi][rt][r];
+                    if (wr < 36) s_y[(pt * 16 + fi) * EN_YP + wr] = acc[pi][rt][r];
                 }
         }
     }
     __syncthreads();
 
-    // ---- forward epilogue.  Waves 0-3: the block's 16 x 32 output pixels, deconv_last_fused_k's loop (same thread -> pixel
-    // map, same order of additions), dpre also into the patch.  Waves 4-7: dpre of the rim pixels, the same expressions.
+    // ---- forward epilogue.  Waves 0-3: the block's 16 x 32 output pixels (same thread -> pixel map, same order of additions),
+    // dpre also into the patch.  Waves 4-7: dpre of the rim pixels, the same expressions.
+    // (inline: mirrors deconv_last_fused_k's loop -- tap gather, stores, sum terms -- with the rim arm; the sigmoid, dpre and the
+    // five-sum total are ends.h's)
     const long plane = (long)OH * OW;
     float sse = 0.f, dsum[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int it = 0; it < EPI; ++it) {
         const int q = tid + 256 * it;
-        const int oy = q / (2 * FB_TB), ox = q - oy * (2 * FB_TB);
+        const int oy = q / (2 * EN_TB), ox = q - oy * (2 * EN_TB);
         int oh = 2 * a0 + oy, ow = 2 * b0 + ox;
-        int ppos = (oy + 1) * FB_PP + ox + 1;
+        int ppos = (oy + 1) * EN_PP + ox + 1;
         if (w >= 4) {
             if (it > 0 || rim_oh < 0) continue;
             oh = rim_oh; ow = rim_ow; ppos = rim_pos;
@@ -305,7 +293,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
             for (int kw = (ow + 1) & 1; kw < 3; kw += 2) {
                 const int b = (ow + 1 - kw) >> 1;
                 if (b < 0 || b >= p.IW) continue;
-                const float* yp = s_y + ((a - a0 + 1) * FB_HB + (b - b0 + 1)) * FB_YP + (kh * 3 + kw) * Cout;
+                const float* yp = s_y + ((a - a0 + 1) * FB_HB + (b - b0 + 1)) * EN_YP + (kh * 3 + kw) * Cout;
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     if (c < Cout) v[c] += yp[c];
@@ -315,7 +303,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         float d4[4] = {0.f, 0.f, 0.f, 0.f}, sg[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            sg[c] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v[c]));
+            sg[c] = en_sigmoid(v[c]);
         if (w < 4) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -329,7 +317,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
             // compiler from regrouping the chain into packed operations)
             sse = __builtin_fmaf(d, d, sse);
             asm volatile("" : "+v"(sse));
-            d4[c] = p.gscale * d * sg[c] * (1.f - sg[c]);
+            d4[c] = en_dpre(p.gscale, d, sg[c]);
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -357,36 +345,34 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         }
         lds_barrier();                   // also: the patch is complete and Y is dead (LDS only: the stores drain behind it)
         if (tid < 5) {
-            const float t = ((red5[0][tid] + red5[1][tid]) + red5[2][tid]) + red5[3][tid];
+            const float t = en_red5_total(red5, tid);
             if (tid == 0) p.ws[blockIdx.x] = t;
             else p.ws[gridDim.x + 4 * blockIdx.x + (tid - 1)] = t;
         }
     }
 
-    // ---- input gradient: conv_first_fused_k<CIN, 1, NQ> from here on, its operands already on chip
+    // ---- input gradient: the steps of conv_first_fused_k<CIN, 1, NQ> from here on, its operands already on chip
 #pragma unroll
     for (int it = 0; it < NQ; ++it) *(u32x4_t*)(s_b + (size_t)(it * 512 + tid) * 16) = wreg[it];
-    static constexpr FbOff<CIN> otab{};
+    static constexpr EnOff<CIN, 1, EN_PA, EN_PP> otab{};
     int koff[8];
 #pragma unroll
     for (int k8 = 0; k8 < 8; ++k8) koff[k8] = otab.v[(tid & 7) * 8 + k8];
-    // im2col rows: 128 rows x 8 chunks of 8 columns
+    // im2col rows: 128 rows x 8 chunks of 8 columns (inline: mirrors conv_first_fused_k's row build; elements, pack and the
+    // swizzled offset are ends.h's)
 #pragma unroll
     for (int i0 = 0; i0 < 128 * 8; i0 += 512) {
         const int i = i0 + tid;
         const int r = i >> 3, c = i & 7;
         const int oy = r >> 4, ox = r & 15;
-        const int corner = (2 * oy * FB_PP + 2 * ox) * CIN;
+        const int corner = (2 * oy * EN_PP + 2 * ox) * CIN;
         unsigned short e[8];
 #pragma unroll
-        for (int k8 = 0; k8 < 8; ++k8) {
-            const float v = koff[k8] >= 0 ? s_patch[corner + max(koff[k8], 0)] : 0.f;
-            e[k8] = f32_to_bf16(v);
-        }
+        for (int k8 = 0; k8 < 8; ++k8) e[k8] = en_col_elem(s_patch, corner, koff[k8]);
         u32x4_t pk;
-        pk[0] = (unsigned)e[0] | ((unsigned)e[1] << 16); pk[1] = (unsigned)e[2] | ((unsigned)e[3] << 16);
-        pk[2] = (unsigned)e[4] | ((unsigned)e[5] << 16); pk[3] = (unsigned)e[6] | ((unsigned)e[7] << 16);
-        *(u32x4_t*)(s_a + r * 128 + ((c ^ ((r >> 1) & 7)) * 16)) = pk;
+        pk[0] = en_pack2(e[0], e[1]); pk[1] = en_pack2(e[2], e[3]);
+        pk[2] = en_pack2(e[4], e[5]); pk[3] = en_pack2(e[6], e[7]);
+        *(u32x4_t*)(s_a + en_a_off(r, c)) = pk;
         const int a = a0 + oy, b = b0 + ox;
         if (p.col && a < p.IH && b < p.IW)
             *(u32x4_t*)(p.col + ((size_t)(n * p.IH + a) * p.IW + b) * 128 + c * 16) = pk;
@@ -394,6 +380,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
     lds_barrier();
 
     // 128 x 64 NQ x 64 on the matrix cores: wave w owns pixels 16 MT (w / NQ) .. x the channel quad w % NQ
+    // (inline: mirrors conv_first_fused_k's block; the chunk offset and the MFMA are ends.h's)
     const int wq = NQ == 4 ? (w & 3) : 0, wm = NQ == 4 ? (w >> 2) : w;
     const int col = 64 * wq + 16 * fg;
     const bool first = col < p.C1, second = col + 8 < p.C1;
@@ -404,7 +391,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         for (int h = 0; h < 4; ++h) dacc[mt][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int ch = ((4 * kk + fg) ^ fsw) * 16;
+        const int ch = en_frag_ch(kk, fg, fsw);
         u32x4_t wv[4], av[MT];
 #pragma unroll
         for (int h = 0; h < 4; ++h) wv[h] = *(const u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);
@@ -414,8 +401,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int h = 0; h < 4; ++h)
-                dacc[mt][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&wv[h], *(const bf16x8_t*)&av[mt],
-                                                                      dacc[mt][h], 0, 0, 0);
+                dacc[mt][h] = en_mma(wv[h], av[mt], dacc[mt][h]);
     }
     // epilogue from registers: lane = pixel fi of tile mt, channels 64*wq + 16*fg .. +15 (two 16-byte chunks); the gate is
     // the 16 bits of (pixel, channel group 4 wq + fg)
@@ -454,8 +440,9 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
     }
     {
         // bias gradient of the layer below: column sums of this block's stored values, pixels then wave groups
+        // (inline: mirrors conv_first_fused_k's row sums and scratch writes; the total is ends.h's)
         float* red = s_patch;                                  // the patch is dead since the last barrier
-        constexpr int RW = 64 * NQ, NGRP = NQ == 4 ? 2 : 8;
+        constexpr int RW = 64 * NQ;
 #pragma unroll
         for (int e = 0; e < 16; ++e) csum[e] = row_sum(csum[e]);
         if (fi == 0) {
@@ -464,9 +451,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         }
         lds_barrier();
         if (tid < p.C1) {
-            float t = red[tid];
-#pragma unroll
-            for (int g2 = 1; g2 < NGRP; ++g2) t += red[g2 * RW + tid];      // fixed order
+            const float t = en_colsum_total<NQ>(red, tid);
             p.colsum_ws[(size_t)blockIdx.x * p.C1 + tid] = t;
         }
     }
@@ -481,25 +466,6 @@ static int fb_shape_ok(int dtype, int N, int IH, int IW, int C1, int Cout) {
     if (fb_lds(C1) > 160 * 1024 - 256) return 0;
     if ((long)N * 2 * IH * 2 * IW * Cout >= (1l << 31) || (long)N * IH * IW * 256 >= (1l << 31)) return 0;
     return 1;
-}
-
-template <int CIN, int NQ> static int fb_launch_k(const FbArgs& a, int blocks, size_t lds, hipStream_t st) {
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        hipError_t e = hipFuncSetAttribute((const void*)deconv_last_fwd_bwd_k<CIN, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(RBVAE_E_LAUNCH, "deconv_last_fwd_bwd: %s (dynamic LDS %zu)", hipGetErrorString(e), lds);
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL((deconv_last_fwd_bwd_k<CIN, NQ>), dim3(blocks), dim3(512), lds, st, a);
-    return RBVAE_OK;
-}
-template <int NQ> static int fb_launch(const FbArgs& a, int Cout, int blocks, size_t lds, hipStream_t st) {
-    switch (Cout) {
-        case 1: return fb_launch_k<1, NQ>(a, blocks, lds, st);
-        case 2: return fb_launch_k<2, NQ>(a, blocks, lds, st);
-        case 3: return fb_launch_k<3, NQ>(a, blocks, lds, st);
-        default: return fb_launch_k<4, NQ>(a, blocks, lds, st);
-    }
 }
 
 }  // namespace rbvae
@@ -519,7 +485,7 @@ extern "C" int rbvae_deconv_last_fwd_bwd(int dtype, const void* D2, const void* 
     RBVAE_CHECK_ARG(fb_shape_ok(dtype, N, IH, IW, C1, Cout),
                     "deconv_last_fwd_bwd: shape outside the fused kernel (bf16, Cout <= 4, C1 %% 64 == 0, C1 <= 256): N=%d %dx%d "
                     "C1=%d Cout=%d", N, IH, IW, C1, Cout);
-    RBVAE_CHECK_ARG(NYP >= 9 * Cout && NYP <= FB_WROWS, "deconv_last_fwd_bwd: NYP=%d", NYP);
+    if (const int e = en_check_nyp("deconv_last_fwd_bwd", NYP, Cout)) return e;
     RBVAE_CHECK_ARG(((uintptr_t)D2 | (uintptr_t)V | (uintptr_t)W | (uintptr_t)zero_page | (uintptr_t)dpre | (uintptr_t)col |
                      (uintptr_t)dd2) % 16 == 0, "deconv_last_fwd_bwd: pointers must be 16-byte aligned");
     FbArgs a;
@@ -527,10 +493,18 @@ extern "C" int rbvae_deconv_last_fwd_bwd(int dtype, const void* D2, const void* 
     a.zero = (const unsigned char*)zero_page; a.xr = xr; a.target = target; a.tfm = FrameMap{fd1, fd2, fs0, fs1, fs2};
     a.ws = ws; a.dpre = dpre; a.col = (unsigned char*)col; a.dd2 = (unsigned char*)dd2; a.colsum_ws = colsum_ws;
     a.gscale = gscale; a.gs = gs; a.N = N; a.IH = IH; a.IW = IW; a.C1 = C1; a.NYP = NYP;
-    const int blocks = N * cdiv(IH, FB_TA) * cdiv(IW, FB_TB);
+    const int blocks = en_blocks(N, IH, IW);
     const size_t lds = fb_lds(C1);
-    const int rc = C1 > 64 ? fb_launch<4>(a, Cout, blocks, lds, (hipStream_t)stream)
-                           : fb_launch<1>(a, Cout, blocks, lds, (hipStream_t)stream);
+    const int rc = en_for_cin(Cout, [&](auto cin) -> int {
+        constexpr int CIN = decltype(cin)::value;
+        const auto launch = [&](auto nq) -> int {
+            constexpr int NQ = decltype(nq)::value;
+            if (const int e = lds_attr_grow<deconv_last_fwd_bwd_k<CIN, NQ>>("deconv_last_fwd_bwd", lds)) return e;
+            hipLaunchKernelGGL((deconv_last_fwd_bwd_k<CIN, NQ>), dim3(blocks), dim3(512), lds, (hipStream_t)stream, a);
+            return RBVAE_OK;
+        };
+        return C1 > 64 ? launch(std::integral_constant<int, 4>{}) : launch(std::integral_constant<int, 1>{});
+    });
     if (rc != RBVAE_OK) return rc;
     RBVAE_CHECK_LAUNCH("deconv_last_fwd_bwd");
     return RBVAE_OK;

@@ -272,7 +272,7 @@ template <typename T>
 static int launch_uc(const UcArgs& a, hipStream_t st) {
     const size_t lds = (size_t)ch_lds_main<T, UC_RING>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + 16;
     static_assert(ch_lds_main<float, UC_RING>() + CH_BM * 4 + CH_NSLOT_PAD * 4 + 16 <= 160 * 1024, "LDS");
-    ch_lds_attr_once<upconv_halo_k<T>>(160 * 1024);
+    lds_attr_once<upconv_halo_k<T>>(160 * 1024);
     hipLaunchKernelGGL((upconv_halo_k<T>), dim3(a.total), dim3(512), lds, st, a);
     RBVAE_CHECK_LAUNCH("upconv3x3_halo");
     return RBVAE_OK;

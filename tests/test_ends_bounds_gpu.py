@@ -14,11 +14,20 @@ Every output, workspace and slab sits inside NaN guard bands (assert_guards: no 
 written); every input inside NaN guard rows, NaN padding columns (ldo > Nout, ldy > Nout) and NaN between the frames of a
 frame-mapped buffer.  Refusals go through the argument checks that return before a launch and leave the outputs untouched.
 
-Worst |err| / bound per kernel: NOT YET MEASURED.  No device run of this file had been possible when it was written;
-every case prints its ratios (BOUNDS ... worst |err|/bound), to be recorded here from the first device run.  What is
-established without a device (test_ends_bounds_cpu.py): the gates agree with the library, an f32 emulation of every
-operation passes every bound, and every named defect is rejected -- the two-kernel arithmetic (Y rounded to bf16) lands
-about 2000 times outside the deconv_last_fused bound.
+Worst |err| / bound per kernel, the maxima over the cases of the printed BOUNDS lines from the first device run (MI355X):
+
+  conv_first_fused          out 0.996
+  deconv_last_dgrad_fused   out 0.996   colsum 0.00271
+  wgrad_first               wgrad_first_k 0.222   wgrad_first_wide_k 0.272
+  deconv_last_fused         xr 0.467   dpre 0.725   dsum 0.121   sse 0.0889
+  conv_in                   out 0.996   stats 0.0156   gn_finish 0.00487
+  col2im_sigmoid            xr 0.633   dpre 0.771   dsum 0.134   sse 0.15   sse_mean 0.0522
+  sigmoid_bwd_nhwc          0.615
+
+(the col rows are compared bit for bit and print no ratio).  What is established without a device
+(test_ends_bounds_cpu.py): the gates agree with the library, an f32 emulation of every operation passes every bound, and
+every named defect is rejected -- the two-kernel arithmetic (Y rounded to bf16) lands about 2000 times outside the
+deconv_last_fused bound.
 
 rbvae_wgrad_first at the cfg-3 size (128 x 3 x 256 x 256, ksplit 512) stays with
 test_kernels_gpu.py::test_wgrad_first_at_the_cfg3_frame_size: its float64 reference (2 097 152 pixel rows) alone costs more
