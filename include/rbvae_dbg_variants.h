@@ -9,8 +9,7 @@ extern "C" {
  * workgroups; the two-per-CU double-buffer launches and the f32 kernels have one form): 0 (default) the product dispatch
  * (the 12-wave form for K loops of at least 16 steps, the 8-wave form below), 1 the 8-wave form (every wave stages and
  * multiplies), 2 the 12-wave form (waves 0-7 multiply, waves 8-11 issue the LDS-DMA) -- the same sums in the same order, so
- * the slabs are equal bit for bit.  Measurement value: 3 the 12-wave form with a ring of four stages where at most 2560
- * pixels per K-slice leave room for the index table.  Returns the previous value. */
+ * the slabs are equal bit for bit.  Returns the previous value. */
 int rbvae_dbg_wgrad_gemm_variant(int v);
 
 /* which path rbvae_deconv_last_fwd_bwd_ok (librbvae_hip) offers its callers: 0 (default) the one-launch kernel where it

@@ -380,7 +380,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
     const int q = fi >> 2, pp = fi & 3;
     const int mt = w & 3, nt0 = (w >> 2) * 2;
     const int row0 = 8 * fg + q;
-    const int offA = en_tr_off(row0, mt, pp), offB0 = en_tr_off(row0, nt0, pp), offB1 = en_tr_off(row0, nt0 + 1, pp);
+    const int offA = tr_off_swz<128>(row0, mt, pp), offB0 = tr_off_swz<128>(row0, nt0, pp), offB1 = tr_off_swz<128>(row0, nt0 + 1, pp);
     f32x4_t acc0 = f32x4_t{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
     const unsigned l_col = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)s_col;
     const unsigned l_dy = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)s_dy[0];
@@ -430,7 +430,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 4) void wgrad_fir
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(b1l) : "v"(adb1));
             asm volatile("ds_read_b64_tr_b16 %0, %1 offset:512" : "=v"(b1h) : "v"(adb1));
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al), "+v"(ah), "+v"(b0l), "+v"(b0h), "+v"(b1l), "+v"(b1h));
-            const bf16x8_t fa = en_tr_frag(al, ah), fb0 = en_tr_frag(b0l, b0h), fb1 = en_tr_frag(b1l, b1h);
+            const bf16x8_t fa = tr_frag(al, ah), fb0 = tr_frag(b0l, b0h), fb1 = tr_frag(b1l, b1h);
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0, fa, acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1, fa, acc1, 0, 0, 0);
         }
@@ -550,7 +550,7 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
     const int qq = fi >> 2, pp = fi & 3;
     const int mt = w & 3, nt0 = (w >> 2) * 2;
     const int row0 = 8 * fg + qq;
-    const int offA = en_tr_off(row0, mt, pp), offB0 = en_tr_off(row0, nt0, pp), offB1 = en_tr_off(row0, nt0 + 1, pp);
+    const int offA = tr_off_swz<128>(row0, mt, pp), offB0 = tr_off_swz<128>(row0, nt0, pp), offB1 = tr_off_swz<128>(row0, nt0 + 1, pp);
     f32x4_t acc[4][2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { acc[q][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[q][1] = acc[q][0]; }
@@ -598,10 +598,10 @@ template <int CIN, int MODE> __global__ __launch_bounds__(512, 2) void wgrad_fir
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(b0l), "+v"(b0h), "+v"(b1l), "+v"(b1h), "+v"(al[0]), "+v"(ah[0]), "+v"(al[1]), "+v"(ah[1]), "+v"(al[2]),
                            "+v"(ah[2]), "+v"(al[3]), "+v"(ah[3]));
-            const bf16x8_t fb0 = en_tr_frag(b0l, b0h), fb1 = en_tr_frag(b1l, b1h);
+            const bf16x8_t fb0 = tr_frag(b0l, b0h), fb1 = tr_frag(b1l, b1h);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const bf16x8_t fa = en_tr_frag(al[q], ah[q]);
+                const bf16x8_t fa = tr_frag(al[q], ah[q]);
                 acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0, fa, acc[q][0], 0, 0, 0);
                 acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1, fa, acc[q][1], 0, 0, 0);
             }

@@ -114,15 +114,8 @@ __device__ __forceinline__ float en_red5_total(const float (*red5)[5], int k) {
     return ((red5[0][k] + red5[1][k]) + red5[2][k]) + red5[3][k];
 }
 
-// ---- wgrad_first_k / wgrad_first_wide_k: the transposing fragment reads of the [128 px][128 B] tr-swizzled LDS images
-// byte offset of a lane's ds_read_b64_tr_b16: row row0 = 8 fg + fi / 4, 16-column sub-tile `tile`, pp = fi % 4
-__device__ __forceinline__ int en_tr_off(int row0, int tile, int pp) {
-    return row0 * 128 + (((tile * 2 + (pp >> 1)) ^ tr_swz<128>(row0)) * 16) + (pp & 1) * 8;
-}
-// the 32-k fragment from the two reads 512 bytes (16 rows) apart
-__device__ __forceinline__ bf16x8_t en_tr_frag(s16x4_t lo, s16x4_t hi) {
-    return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
+// (wgrad_first_k / wgrad_first_wide_k take the transposing fragment reads of their [128 px][128 B] tr-swizzled LDS images from
+// mma.h: tr_off<128>, tr_frag)
 
 // ---- host
 // output extent of the 3x3 stride-2 pad-1 convolution (= input extent of the transposed one)

@@ -1,6 +1,6 @@
 // Shared device helpers of the matrix-core kernels (gfx950 only): vector types, the LDS-DMA wrapper, the LDS-only and
-// counted-vmcnt barriers, DPP row sums, static_for, the MFMA dispatch, the transposing-read swizzle, the ReLU-gate test
-// and the frame map.  Everything is __forceinline__: a kernel that takes a helper from here compiles to the code it had
+// counted-vmcnt barriers, DPP row sums, static_for, the MFMA dispatch, the transposing-read swizzle, lane offset and fragment
+// pack, the ReLU-gate test and the frame map.  Everything is __forceinline__: a kernel that takes a helper from here compiles to the code it had
 // with a private copy (tools/isa_diff.py proves it).  New kernels take these; they do not copy them.
 #pragma once
 #include "common.h"
@@ -88,6 +88,24 @@ template <> struct Mma<float> {
 template <int RB> __device__ __forceinline__ int tr_swz(int row) {
     if constexpr (RB >= 256) return ((row & 3) | (((row >> 3) & 1) << 2)) << 1;   // 8 chunk pairs
     else return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1;                // 128-B rows: 4 pairs
+}
+
+// Transposing fragment reads (ds_read_b64_tr_b16) of an image whose ROW is the reduction index: lane (fg, q, pp) = (lane >> 4,
+// (lane & 15) >> 2, lane & 3) addresses row 8 fg + q (+ 4 for the second read), elements 4 pp .. + 3 of a 16-column sub-tile.
+// The lane's byte offset, two forms because no single one leaves every taker's listing alone ("Shared steps of the
+// weight-gradient kernels"):
+//   tr_off_swz  image at byte 0, sub-tile `tile`, chunks swizzled by tr_swz<RB>(row) (wgrad_gemm_k's and wgrad_row_k's first
+//               operand, both wgrad_first kernels);
+//   tr_off      image at byte `base`; `chunk` = (tile * 2 + (pp >> 1)) ^ swizzle is formed at the call (second operands and
+//               patches with a swizzle of their own; wgrad_halo_k's S tile).  tr_off_swz written as a call of tr_off changes
+//               the wgrad_first kernels, so it spells the sum out.
+// tr_frag: the 32-k MFMA operand from the two reads.
+template <int RB> __device__ __forceinline__ int tr_off(int base, int row, int chunk, int pp) { return base + row * RB + chunk * 16 + (pp & 1) * 8; }
+template <int RB> __device__ __forceinline__ int tr_off_swz(int row, int tile, int pp) {
+    return row * RB + (((tile * 2 + (pp >> 1)) ^ tr_swz<RB>(row)) * 16) + (pp & 1) * 8;
+}
+__device__ __forceinline__ bf16x8_t tr_frag(s16x4_t lo, s16x4_t hi) {
+    return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
 // ReLU gate: element e of a stored activation is > 0 (NaN excluded)

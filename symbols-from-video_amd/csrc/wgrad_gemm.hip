@@ -14,8 +14,7 @@
 // (ROLES: waves 8-11 issue the LDS-DMA, waves 0-7 only multiply; see the kernel).  grid = (co tiles, ci tiles, taps * ksplit); each
 // K-slice writes its own f32 slab (summed later in a fixed order by
 // rbvae_permute_reduce, so gradients are bitwise reproducible -- no float atomics).
-#include "mma.h"
-#include <type_traits>
+#include "wgrad.h"
 
 namespace rbvae {
 
@@ -93,16 +92,13 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
     const int gx = (p.Co + BM - 1) / BM, gy = (p.Ci + BN - 1) / BN;
     int ks, wg;
     if (p.xcd_order) {
-        // Workgroups are dealt to the 8 XCDs round-robin by id; XCD x takes the x-th eighth of the (K-slice, tile)
-        // items in slice-major order, so its workgroups share one or two pixel slices of Dy / In and re-read them from
-        // that XCD's L2 (with the K-slice as the fastest digit every XCD walks every slice).  Placement is a speed
-        // matter only: every item is computed whichever XCD takes it.
-        const int ntiles = gx * gy * p.taps, total = ntiles * p.ksplit, per = (total + 7) >> 3;
-        const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-        const int item = x * per + q;
-        if (q >= per || item >= total) return;         // the grid is 8 * per workgroups (uniform exit, before any barrier)
-        ks = item / ntiles;
-        wg = item - ks * ntiles;
+        // wgrad.h's slice-major order: an XCD's workgroups share one or two pixel slices of Dy / In and re-read them from that
+        // XCD's L2 (with the K-slice as the fastest digit every XCD walks every slice)
+        const int ntiles = gx * gy * p.taps;
+        const WgItem it = wg_item(blockIdx.x, ntiles * p.ksplit);
+        if (!it.live) return;
+        ks = it.item / ntiles;
+        wg = it.item - ks * ntiles;
     } else {
         wg = blockIdx.x;
         ks = wg % p.ksplit; wg /= p.ksplit;
@@ -131,9 +127,8 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
     __syncthreads();
     WG_STAMP(1);
 
-    // staging roles.  One instruction = 1 KiB = (1024/RB) image rows.
-    constexpr int A_LPR = RBA / 16, B_LPR = RBB / 16;     // lanes (chunks) per row
-    constexpr int A_RPI = 64 / A_LPR, B_RPI = 64 / B_LPR; // rows per instruction
+    // staging roles.  One instruction = one piece of 1 KiB = (1024/RB) image rows; a piece's row, chunk and validity and the
+    // stage bodies are wgrad.h's, the same for the producer waves' pieces pw + 4 j (4 KiB apart) and the 8-wave form's w N + i
     if constexpr (ROLES) {
         if (w >= 8) {
             // ================= producer waves: pw = w - 8 issues pieces pw + 4 j of every stage =================
@@ -146,10 +141,10 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
             const unsigned char* acur[PA];
 #pragma unroll
             for (int j = 0; j < PA; ++j) {
-                const int r = (pw + 4 * j) * A_RPI + lane / A_LPR;
-                const int c = (lane % A_LPR) ^ tr_swz<RBA>(r);
+                const int r = wg_piece_row<RBA>(pw + 4 * j, lane);
+                const int c = wg_piece_chunk<RBA, SWZ>(r, lane);
                 a_row[j] = r;
-                a_cval[j] = co0 + c * (16 / ES) < p.Co;
+                a_cval[j] = wg_piece_cval<ES>(co0, c, p.Co);
                 acur[j] = p.Dy + ((size_t)(pbeg + r) * p.ldy + co0) * ES + c * 16;
             }
             int b_row[PB];
@@ -157,10 +152,10 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
             const unsigned char* bbase[PB];
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
-                const int r = (pw + 4 * j) * B_RPI + lane / B_LPR;
-                const int c = (lane % B_LPR) ^ tr_swz<RBB>(r);
+                const int r = wg_piece_row<RBB>(pw + 4 * j, lane);
+                const int c = wg_piece_chunk<RBB, SWZ>(r, lane);
                 b_row[j] = r;
-                b_cval[j] = ci0 + c * (16 / ES) < p.Ci;
+                b_cval[j] = wg_piece_cval<ES>(ci0, c, p.Ci);
                 bbase[j] = p.In + (size_t)ci0 * ES + c * 16;
             }
             const size_t a_stride = (size_t)WG_BK * p.ldy * ES, ldi_b = (size_t)p.ldi * ES;
@@ -168,21 +163,8 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
             auto stage = [&]() {
                 unsigned char* la = smem + pbuf * STAGE + pw * 1024;
                 const int base = pstep * WG_BK;
-#pragma unroll
-                for (int j = 0; j < PA; ++j) {
-                    const bool v = a_cval[j] && base + a_row[j] < npix;
-                    glds16(v ? acur[j] : p.zero, la + j * 4096);
-                    acur[j] += a_stride;
-                }
-                unsigned char* lb = la + A_BYTES;
-                int src[PB];                               // all of a stage's indices first: no LDS wait between the pieces
-#pragma unroll
-                for (int j = 0; j < PB; ++j) src[j] = s_idx[base + b_row[j]];
-#pragma unroll
-                for (int j = 0; j < PB; ++j) {
-                    const bool v = b_cval[j] && src[j] >= 0;
-                    glds16(v ? bbase[j] + (size_t)src[j] * ldi_b : p.zero, lb + j * 4096);
-                }
+                wg_stage_rows<PA, 4096>(la, acur, a_cval, a_row, base, npix, a_stride, p.zero);
+                wg_stage_gather<PB, 4096, true>(la + A_BYTES, bbase, b_cval, b_row, s_idx, base, ldi_b, p.zero);
                 ++pstep;
                 pbuf = (pbuf + 1 == WG_NS) ? 0 : pbuf + 1;
             };
@@ -204,22 +186,23 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
     bool a_cval[A_INSTR];
 #pragma unroll
     for (int i = 0; i < A_INSTR; ++i) {
-        const int r = (w * A_INSTR + i) * A_RPI + lane / A_LPR;
-        const int c = (lane % A_LPR) ^ (SWZ ? tr_swz<RBA>(r) : 0);
+        const int r = wg_piece_row<RBA>(w * A_INSTR + i, lane);
+        const int c = wg_piece_chunk<RBA, SWZ>(r, lane);
         a_row[i] = r;
         a_coff[i] = c * 16;
-        a_cval[i] = co0 + c * (16 / ES) < p.Co;
+        a_cval[i] = wg_piece_cval<ES>(co0, c, p.Co);
     }
     const bool b_wave = (w * B_INSTR) < B_TOT;            // does this wave stage part of B?
     int b_row[B_INSTR], b_coff[B_INSTR];
     bool b_cval[B_INSTR];
 #pragma unroll
     for (int i = 0; i < B_INSTR; ++i) {
-        const int r = (w * B_INSTR + i) * B_RPI + lane / B_LPR;
-        const int c = (lane % B_LPR) ^ (SWZ ? tr_swz<RBB>(r & (WG_BK - 1)) : 0);
+        const int r = wg_piece_row<RBB>(w * B_INSTR + i, lane);
+        // (inline: mirrors wg_piece_chunk of wgrad.h, which changes four f32 instances here)
+        const int c = (lane % (RBB / 16)) ^ (SWZ ? tr_swz<RBB>(r & (WG_BK - 1)) : 0);
         b_row[i] = r & (WG_BK - 1);
         b_coff[i] = c * 16;
-        b_cval[i] = b_wave && ci0 + c * (16 / ES) < p.Ci;
+        b_cval[i] = b_wave && wg_piece_cval<ES>(ci0, c, p.Ci);
     }
     // producer state: A rows advance by a constant stride per K step (one 64-bit add each); B rows are
     // gathered through the index table in LDS
@@ -236,27 +219,18 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
     auto stage_next = [&]() {
         unsigned char* la = smem + pbuf * STAGE + (w * A_INSTR) * 1024;
         const int base = pstep * WG_BK;
-#pragma unroll
-        for (int i = 0; i < A_INSTR; ++i) {
-            const bool v = a_cval[i] && base + a_row[i] < npix;
-            glds16(v ? acur[i] : p.zero, la + i * 1024);
-            acur[i] += a_stride;
-        }
+        wg_stage_rows<A_INSTR, 1024>(la, acur, a_cval, a_row, base, npix, a_stride, p.zero);
         if (b_wave) {
             unsigned char* lb = smem + pbuf * STAGE + A_BYTES + (w * B_INSTR) * 1024;
-#pragma unroll
-            for (int i = 0; i < B_INSTR; ++i) {
-                const int src = s_idx[base + b_row[i]];
-                const bool v = b_cval[i] && src >= 0;
-                glds16(v ? bbase[i] + (size_t)src * ldi_b : p.zero, lb + i * 1024);
-            }
+            wg_stage_gather<B_INSTR, 1024, false>(lb, bbase, b_cval, b_row, s_idx, base, ldi_b, p.zero);
         }
         ++pstep;
         pbuf = (pbuf + 1 == WG_NS) ? 0 : pbuf + 1;
     };
     WG_STAMP(2);
-    const int wr = w >> 2, wc = w & 3;
-    const int fi = lane & 15, fg = lane >> 4;
+    const int wr = w >> 2, wc = w & 3;                    // (inline: mirrors wgrad_row_k's MFMA-wave decode)
+    const WgLane ln = wg_lane(lane);
+    const int fi = ln.fi, fg = ln.fg;
     f32x4_t acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -267,18 +241,11 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
     int offA[MT], offB[NT];
     if constexpr (ES == 2) {
         // transposed read: lane (g, q, pp) addresses row 8g+4h+q, elements cb+4pp..+3 of a 16-channel block
-        const int q = fi >> 2, pp = fi & 3;
-        const int row = 8 * fg + q;                       // + 4h
+        const int pp = ln.pp, row = 8 * fg + ln.q;        // + 4h
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int chunk = ((wr * MT + mt) * 2 + (pp >> 1)) ^ tr_swz<RBA>(row);
-            offA[mt] = row * RBA + chunk * 16 + (pp & 1) * 8;
-        }
+        for (int mt = 0; mt < MT; ++mt) offA[mt] = tr_off_swz<RBA>(row, wr * MT + mt, pp);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int chunk = ((wc * NT + nt) * 2 + (pp >> 1)) ^ tr_swz<RBB>(row);
-            offB[nt] = A_BYTES + row * RBB + chunk * 16 + (pp & 1) * 8;
-        }
+        for (int nt = 0; nt < NT; ++nt) offB[nt] = tr_off<RBB>(A_BYTES, row, ((wc * NT + nt) * 2 + (pp >> 1)) ^ tr_swz<RBB>(row), pp);
     } else {
         // f32: lane (i, g) reads element (row 4s+g, channel cb+i)
 #pragma unroll
@@ -338,11 +305,9 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
                                "+v"(alo[3]), "+v"(ahi[3]), "+v"(blo[0]), "+v"(bhi[0])
                              : "n"(YOUNGER));
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                fa[mt] = bf16x8_t{alo[mt][0], alo[mt][1], alo[mt][2], alo[mt][3], ahi[mt][0], ahi[mt][1], ahi[mt][2], ahi[mt][3]};
+            for (int mt = 0; mt < MT; ++mt) fa[mt] = tr_frag(alo[mt], ahi[mt]);
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                fb[nt] = bf16x8_t{blo[nt][0], blo[nt][1], blo[nt][2], blo[nt][3], bhi[nt][0], bhi[nt][1], bhi[nt][2], bhi[nt][3]};
+            for (int nt = 0; nt < NT; ++nt) fb[nt] = tr_frag(blo[nt], bhi[nt]);
         };
         auto mma_half = [&](const bf16x8_t (&fa)[MT], const bf16x8_t (&fb)[NT]) {
 #pragma unroll
@@ -423,7 +388,7 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
 
     WG_STAMP(3);
     // D[row = ci 4g+r][col = co i]: lane owns 4 consecutive ci of one co -> one 16-B store
-    float* slab = p.dW + (size_t)ks * p.Co * p.taps * p.Ci;
+    float* slab = wg_slab(p.dW, ks, p.Co, p.taps, p.Ci);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int co = co0 + (wr * MT + mt) * 16 + fi;
@@ -432,7 +397,7 @@ __global__ __launch_bounds__(ROLES ? 768 : 512, WG_NS == 2 ? 2 : 1) void wgrad_g
         for (int nt = 0; nt < NT; ++nt) {
             const int ci = ci0 + (wc * NT + nt) * 16 + 4 * fg;
             if (ci >= p.Ci) continue;
-            *(f32x4_t*)(slab + ((size_t)co * p.taps + tap) * p.Ci + ci) = acc[mt][nt];
+            *(f32x4_t*)(slab + wg_slab_off(co, p.taps, tap, p.Ci, ci)) = acc[mt][nt];
         }
     }
 #if WG_STAMPS
@@ -461,12 +426,7 @@ static int launch_wg_ns(const WgArgs& a, hipStream_t st) {
     constexpr int BK = (ES == 2) ? 64 : 32;
     constexpr size_t ring = (size_t)NS * BK * (BM + 64 * NT) * ES;
     const size_t lds = ring + (size_t)a.Pper * sizeof(int);            // + this launch's index table
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_gemm_k<T, NT, NS, BM, ROLES>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(ring + WG_MAXP * sizeof(int)));
-        attr_set = true;
-    }
+    lds_attr_once<wgrad_gemm_k<T, NT, NS, BM, ROLES>>((int)(ring + WG_MAXP * sizeof(int)));
     long blocks = (long)cdiv(a.Co, BM) * cdiv(a.Ci, 64 * NT) * a.taps * a.ksplit;
     if (a.xcd_order) blocks = 8 * ((blocks + 7) / 8);
     hipLaunchKernelGGL((wgrad_gemm_k<T, NT, NS, BM, ROLES>), dim3((unsigned)blocks), dim3(ROLES ? 768 : 512), lds, st, a);
@@ -475,8 +435,7 @@ static int launch_wg_ns(const WgArgs& a, hipStream_t st) {
 }
 
 // Which form the one-workgroup-per-CU bf16 launches take.  Written only by librbvae_dbg's rbvae_dbg_wgrad_gemm_variant
-// (bit-identity tests, A/B timing): 0 the product dispatch, 1 the 8-wave form, 2 the 12-wave form with wave roles, 3 the
-// 12-wave form with a ring of four stages where the index table leaves room.
+// (bit-identity tests, A/B timing): 0 the product dispatch, 1 the 8-wave form, 2 the 12-wave form with wave roles.
 int wgrad_gemm_variant = 0;
 // Product dispatch: wave roles for K loops of at least this many steps (the 4096-pixel layers at the bench shape: 22 steps,
 // 24.0 / 31.0 -> 21.0 / 24.8 us per launch in the step); the 8-9-step launches (conv1 / last deconv weight gradients, NT = 1)
@@ -490,15 +449,10 @@ static int launch_wg(const WgArgs& a, hipStream_t st) {
     // more workgroups than CUs: two per CU (double buffer) when two rings + index tables fit the 160 KB LDS
     const long blocks = (long)cdiv(a.Co, BM) * cdiv(a.Ci, 64 * NT) * a.taps * a.ksplit;
     const size_t lds2 = (size_t)2 * BK * (BM + 64 * NT) * ES + (size_t)a.Pper * sizeof(int);
-    constexpr int force = 0;
-    const bool two = force ? force == 2 : (blocks > 256 && 2 * lds2 <= 160 * 1024);
+    const bool two = blocks > 256 && 2 * lds2 <= 160 * 1024;
     if constexpr (ES == 2) {
-        if (force == 4 && a.Pper <= 2560) return launch_wg_ns<T, NT, 4>(a, st);
         const int v = wgrad_gemm_variant;
-        if (!two && (v == 0 ? a.Pper >= WG_ROLES_MIN_STEPS * BK : v >= 2)) {
-            if (v == 3 && a.Pper <= 2560) return launch_wg_ns<T, NT, 4, BM, true>(a, st);
-            return launch_wg_ns<T, NT, 3, BM, true>(a, st);
-        }
+        if (!two && (v == 0 ? a.Pper >= WG_ROLES_MIN_STEPS * BK : v >= 2)) return launch_wg_ns<T, NT, 3, BM, true>(a, st);
     }
     return two ? launch_wg_ns<T, NT, 2, BM>(a, st) : launch_wg_ns<T, NT, 3, BM>(a, st);
 }
@@ -554,8 +508,7 @@ int rbvae_wgrad_gemm(int dtype, const void* Dy, const void* In, float* dW_slabs,
     // XCD-ordered workgroups: the same step time (0.4454 on vs 0.4456 ms off, same GPU, 4 runs each -- the K step is bound
     // by the CU's intake, not by where the rows come from) but a third less traffic behind the L2s: 66.9 vs 103.1 MB
     // fetched by the 252-workgroup launch, 68.4 vs 86.3 (216), 21.1 vs 25.9 (108) (FETCH_SIZE, tools/pmc_traffic_env.sh)
-    constexpr int xcd = 1;
-    a.xcd_order = xcd && ksplit > 1;
+    a.xcd_order = ksplit > 1;
     RBVAE_CHECK_ARG(a.Pper <= WG_MAXP, "wgrad_gemm: %d pixels per K-slice exceed %d: raise ksplit (>= %d)", a.Pper,
                     WG_MAXP, cdiv(P, WG_MAXP));
     hipStream_t st = (hipStream_t)stream;

@@ -25,9 +25,7 @@
 // Workgroup -> (tile, K-slice): XCD x (= workgroup id % 8) takes the K-slices x, x + 8, .. with all their channel tiles, so
 // the 16 tile workgroups of a 256 x 256 layer that walk the same pixels share them in ONE L2.
 // Each K-slice writes its own f32 slab [a][t][b] (rbvae_wgrad_gemm's layout: the same fixed-order reduction jobs follow).
-#include "mma.h"
-#include <stdlib.h>
-#include <type_traits>
+#include "wgrad.h"
 
 #ifndef WH_ABL          // timing ablations (results wrong on purpose): 1 no LDS-DMA, 2 no fragment reads / MFMAs
 #define WH_ABL 0
@@ -120,23 +118,21 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
     };
 
     // ---- consumer roles: wave w owns b sub-tile w % 4 of the taps w / 4 + 2 j (waves 0-3: five taps, 4-7: four)
-    const int fi = lane & 15, fg = lane >> 4;
+    const int fi = lane & 15, fg = lane >> 4;            // (inline: mirrors wg_lane of wgrad.h)
     const int q = fi >> 2, pp = fi & 3;
     const int th = w >> 2, bs = w & 3;
     int offA[4];
     {
         const int row = 8 * fg + q;                      // + 4 for the second read
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const int chunk = (mt * 2 + (pp >> 1)) ^ tr_swz<128>(row);
-            offA[mt] = row * 128 + chunk * 16 + (pp & 1) * 8;
-        }
+        for (int mt = 0; mt < 4; ++mt) offA[mt] = tr_off<128>(0, row, (mt * 2 + (pp >> 1)) ^ tr_swz<128>(row), pp);
     }
     int offBl[WH_UNITS], offBh[WH_UNITS];               // pixel (rr = fg, cc = q) and (rr = fg, cc = q + 4) of unit j's tap
 #pragma unroll
     for (int j = 0; j < WH_UNITS; ++j) {
         const int tap = min(th + 2 * j, 8), kh = tap / 3, kw = tap - 3 * kh;
         const int sl = wh_plane(kh & 1, kw & 1) + (fg + (kh >> 1)) * WH_PW + (kw >> 1) + q, sh = sl + 4;
+        // (inline: mirrors tr_off<128>(WH_S_BYTES, slot, chunk, pp) of mma.h)
         offBl[j] = WH_S_BYTES + sl * 128 + (((bs * 2 + (pp >> 1)) ^ wh_swz_g(sl)) * 16) + (pp & 1) * 8;
         offBh[j] = WH_S_BYTES + sh * 128 + (((bs * 2 + (pp >> 1)) ^ wh_swz_g(sh)) * 16) + (pp & 1) * 8;
     }
@@ -176,11 +172,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
                        "+v"(bl[4]), "+v"(bh[4])
                      : "n"(YOUNGER));
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-            fa[mt] = bf16x8_t{al[mt][0], al[mt][1], al[mt][2], al[mt][3], ah[mt][0], ah[mt][1], ah[mt][2], ah[mt][3]};
+        for (int mt = 0; mt < 4; ++mt) fa[mt] = tr_frag(al[mt], ah[mt]);
 #pragma unroll
-        for (int j = 0; j < WH_UNITS; ++j)
-            fb[j] = bf16x8_t{bl[j][0], bl[j][1], bl[j][2], bl[j][3], bh[j][0], bh[j][1], bh[j][2], bh[j][3]};
+        for (int j = 0; j < WH_UNITS; ++j) fb[j] = tr_frag(bl[j], bh[j]);
     };
     auto mma = [&](const bf16x8_t (&fa)[4], const bf16x8_t (&fb)[WH_UNITS]) {
 #pragma unroll
@@ -253,7 +247,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
     }
 
     // ---- slab: D[row = b 4 fg + r][col = a fi]: a lane owns 4 consecutive b of one a -> one 16-byte store
-    float* slab = p.dW + (size_t)ks * p.Ca * 9 * p.Cb;
+    float* slab = wg_slab(p.dW, ks, p.Ca, 9, p.Cb);
 #pragma unroll
     for (int j = 0; j < WH_UNITS; ++j) {
         const int tap = th + 2 * j;
@@ -261,14 +255,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_k(const WhArgs p) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             const int a = a0 + mt * 16 + fi, b = b0 + bs * 16 + 4 * fg;
-            *(f32x4_t*)(slab + ((size_t)a * 9 + tap) * p.Cb + b) = acc[j][mt];
+            *(f32x4_t*)(slab + wg_slab_off(a, 9, tap, p.Cb, b)) = acc[j][mt];
         }
     }
-}
-
-static int wh_ok(int dtype, int Nimg, int OH, int OW, int Ca, int Cb) {
-    return dtype == RBVAE_BF16 && Nimg >= 1 && OH >= 1 && OW >= 1 && Ca >= 64 && Cb >= 64 && Ca % 64 == 0 && Cb % 64 == 0 &&
-           (long)Nimg * OH * OW * 4 < (1l << 31);
 }
 
 }  // namespace rbvae
@@ -277,19 +266,14 @@ using namespace rbvae;
 
 extern "C" {
 
-int rbvae_wgrad3x3s2_halo_ok(int dtype, int Nimg, int OH, int OW, int Ca, int Cb) { return wh_ok(dtype, Nimg, OH, OW, Ca, Cb); }
+int rbvae_wgrad3x3s2_halo_ok(int dtype, int Nimg, int OH, int OW, int Ca, int Cb) { return wg3x3_ok(64, dtype, Nimg, OH, OW, Ca, Cb); }
 
 /* 4 x 8 pixel blocks the K loop walks (the caller sizes ksplit against it) */
 int rbvae_wgrad3x3s2_halo_blocks(int Nimg, int OH, int OW) { return Nimg * ((OH + WH_BH - 1) / WH_BH) * ((OW + WH_BW - 1) / WH_BW); }
 
 int rbvae_wgrad3x3s2_halo(int dtype, const void* S, const void* G, float* dW_slabs, const void* zero_page, int Nimg, int OH,
                           int OW, int Ca, int Cb, int lds_, int ldg, int ksplit, void* stream) {
-    RBVAE_CHECK_ARG(S && G && dW_slabs && zero_page, "wgrad3x3s2_halo: null pointer");
-    RBVAE_CHECK_ARG(wh_ok(dtype, Nimg, OH, OW, Ca, Cb), "wgrad3x3s2_halo: shape not covered (dtype %d, %d x %d x %d, %d x %d channels): "
-                    "query rbvae_wgrad3x3s2_halo_ok", dtype, Nimg, OH, OW, Ca, Cb);
-    RBVAE_CHECK_ARG(lds_ >= Ca && ldg >= Cb && lds_ % 8 == 0 && ldg % 8 == 0, "wgrad3x3s2_halo: leading dimensions lds=%d ldg=%d", lds_, ldg);
-    RBVAE_CHECK_ARG(((uintptr_t)S | (uintptr_t)G | (uintptr_t)dW_slabs | (uintptr_t)zero_page) % 16 == 0,
-                    "wgrad3x3s2_halo: pointers must be 16-byte aligned");
+    if (int rc = wg3x3_check("wgrad3x3s2_halo", 64, dtype, S, G, dW_slabs, zero_page, Nimg, OH, OW, Ca, Cb, lds_, ldg)) return rc;
     WhArgs a;
     a.S = (const unsigned char*)S; a.G = (const unsigned char*)G; a.dW = dW_slabs; a.zero = (const unsigned char*)zero_page;
     a.Nimg = Nimg; a.OH = OH; a.OW = OW; a.Ca = Ca; a.Cb = Cb; a.lds = lds_; a.ldg = ldg;
@@ -297,11 +281,7 @@ int rbvae_wgrad3x3s2_halo(int dtype, const void* S, const void* G, float* dW_sla
     RBVAE_CHECK_ARG(ksplit >= 1 && ksplit <= a.nblk, "wgrad3x3s2_halo: ksplit=%d (1 .. %d blocks)", ksplit, a.nblk);
     a.per = (a.nblk + ksplit - 1) / ksplit;
     a.ksplit = ksplit;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_halo_k, hipFuncAttributeMaxDynamicSharedMemorySize, WH_RING * WH_STAGE);
-        attr_set = true;
-    }
+    lds_attr_once<wgrad_halo_k>(WH_RING * WH_STAGE);
     // K-slices in groups of 8 (one per XCD); workgroups of the padding K-slices return at once
     const long blocks = (long)(Ca / 64) * (Cb / 64) * 8 * ((ksplit + 7) / 8);
     hipLaunchKernelGGL(wgrad_halo_k, dim3((unsigned)blocks), dim3(512), WH_RING * WH_STAGE, (hipStream_t)stream, a);

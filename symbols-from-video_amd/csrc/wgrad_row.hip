@@ -34,8 +34,7 @@
 // Workgroup -> (tile, K-slice): XCD x (= workgroup id % 8) takes a contiguous eighth of the (K-slice, tile) items in
 // slice-major order: the 12 tiles of a K-slice share its pixels in that XCD's L2.  Each K-slice writes its own f32 slab [a][t][b] (rbvae_wgrad_gemm's layout: the
 // same fixed-order reduction jobs follow; bitwise reproducible, no float atomics).
-#include "mma.h"
-#include <type_traits>
+#include "wgrad.h"
 
 #ifndef WR_ABL          // timing ablations (results wrong on purpose; RBVAE_ABLATION builds only): 1 no LDS-DMA, 2 no fragment reads / MFMAs, 3 see stage(), 5 no fragment reads, 6 one MFMA wave per SIMD
 #define WR_ABL 0
@@ -82,14 +81,12 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int na = p.Ca >> 7, nb = p.Cb >> 7, ntile = na * nb * 3;
-    // Workgroups are dealt to the 8 XCDs round-robin by id; XCD x takes the x-th eighth of the (K-slice, tile) items in
-    // slice-major order (wgrad_gemm.hip's order): its <= 32 workgroups cover 3-4 K-slices, whose 12 tiles share the slice's
-    // pixels in that XCD's L2.  Placement is a speed matter only.
-    const int total = ntile * p.ksplit, per = (total + 7) >> 3;
-    const int item = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per || item >= total) return;      // the grid is 8 * per workgroups (uniform exit, before any barrier)
-    const int ks = item / ntile;
-    int tile = item - ks * ntile;
+    // wgrad.h's slice-major order: an XCD's <= 32 workgroups cover 3-4 K-slices, whose 12 tiles share the slice's pixels in
+    // that XCD's L2
+    const WgItem it = wg_item(blockIdx.x, ntile * p.ksplit);
+    if (!it.live) return;
+    const int ks = it.item / ntile;
+    int tile = it.item - ks * ntile;
     const int kh = tile % 3; tile /= 3;
     const int a0 = (tile / nb) * 128, b0 = (tile % nb) * 128;
     // balanced K-slices: the first nblk % ksplit slices take one block more
@@ -186,14 +183,13 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
     }
 
     // ================= MFMA waves: wave (wr, wc) owns a sub-tiles 4 wr .. + 3, b sub-tiles 2 wc, 2 wc + 1 of the three taps =================
-    const int fi = lane & 15, fg = lane >> 4;
-    const int q = fi >> 2, pp = fi & 3;
-    const int wr = w >> 2, wc = w & 3;
+    const WgLane ln = wg_lane(lane);
+    const int fi = ln.fi, fg = ln.fg, q = ln.q, pp = ln.pp;
+    const int wr = w >> 2, wc = w & 3;                   // (inline: mirrors wgrad_gemm_k's MFMA-wave decode)
     int offA;                                            // a sub-tile 4 wr; sub-tile 4 wr + mt: chunk index ^ 2 mt = byte address ^ 32 mt
     {
         const int row = 8 * fg + q;                      // + 4 for the second read, + 32 for the second half
-        const int chunk = ((wr * 4) * 2 + (pp >> 1)) ^ tr_swz<256>(row);
-        offA = row * 256 + chunk * 16 + (pp & 1) * 8;
+        offA = tr_off_swz<256>(row, wr * 4, pp);
     }
     int offB[3];                                         // [kw]: pixel k = 8 fg + q of the first half, b sub-tile 2 wc
 #pragma unroll                                           // (sub-tile 2 wc + 1: chunk index ^ 2 = byte address ^ 32; pixel k + 4 and the second
@@ -202,7 +198,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
         const int rr = k / W, cc = k % W;
         const int jj = kw == 0 ? cc : (kw == 1 ? W + 1 + cc : cc + 1);
         const int chunk = ((wc * 2) * 2 + (pp >> 1)) ^ (wr_swz_g<W>(rr, jj) << 1);
-        offB[kw] = WR_A_BYTES + (rr * SPR + jj) * 256 + chunk * 16 + (pp & 1) * 8;
+        offB[kw] = tr_off<256>(WR_A_BYTES, rr * SPR + jj, chunk, pp);
     }
 
     f32x4_t acc[3][4][2];
@@ -263,10 +259,10 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
         constexpr int M0 = decltype(m0_tag)::value, NM = decltype(nm_tag)::value;
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            const bf16x8_t fb = {bl[nt][0], bl[nt][1], bl[nt][2], bl[nt][3], bh[nt][0], bh[nt][1], bh[nt][2], bh[nt][3]};
+            const bf16x8_t fb = tr_frag(bl[nt], bh[nt]);
 #pragma unroll
             for (int mt = M0; mt < M0 + NM; ++mt) {
-                const bf16x8_t fa = {al[mt][0], al[mt][1], al[mt][2], al[mt][3], ah[mt][0], ah[mt][1], ah[mt][2], ah[mt][3]};
+                const bf16x8_t fa = tr_frag(al[mt], ah[mt]);
                 acc[kw][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb, fa, acc[kw][mt][nt], 0, 0, 0);
             }
         }
@@ -347,7 +343,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
     }
 
     // ---- slab: D[row = b 4 fg + r][col = a fi]: a lane owns 4 consecutive b of one a -> one 16-byte store
-    float* slab = p.dW + (size_t)ks * p.Ca * 9 * p.Cb;
+    float* slab = wg_slab(p.dW, ks, p.Ca, 9, p.Cb);
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
@@ -356,6 +352,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const int b = b0 + (wc * 2 + nt) * 16 + 4 * fg;
+                // (inline: mirrors wg_slab_off of wgrad.h; kh * 3 and kw are added one by one in 64 bits here)
                 *(f32x4_t*)(slab + ((size_t)a * 9 + kh * 3 + kw) * p.Cb + b) = acc[kw][mt][nt];
             }
         }
@@ -371,14 +368,15 @@ __global__ __launch_bounds__(768, 1) void wgrad_row_k(const WrArgs p) {
 
 static int wr_width(int OW) { return ((OW + 7) / 8) * 8 == ((OW + 3) / 4) * 4 ? 8 : 4; }
 
-static int wr_ok(int dtype, int Nimg, int OH, int OW, int Ca, int Cb) {
-    return dtype == RBVAE_BF16 && Nimg >= 1 && OH >= 1 && OW >= 1 && Ca >= 128 && Cb >= 128 && Ca % 128 == 0 && Cb % 128 == 0 &&
-           (long)Nimg * OH * OW * 4 < (1l << 31);       /* pixel rows; the byte sizes are checked against the leading dimensions at launch */
-}
-
 static int wr_blocks(int Nimg, int OH, int OW) {
     const int W = wr_width(OW);
     return ((OW + W - 1) / W) * ((Nimg * OH + 64 / W - 1) / (64 / W));
+}
+
+template <int W> static void wr_launch(const WrArgs& a, long blocks, hipStream_t st) {
+    constexpr int LDS = WR_RING * (WR_A_BYTES + (64 / W) * (2 * W + 1) * 256);
+    lds_attr_once<wgrad_row_k<W>>(LDS);
+    hipLaunchKernelGGL(wgrad_row_k<W>, dim3((unsigned)blocks), dim3(768), LDS, st, a);
 }
 
 }  // namespace rbvae
@@ -398,19 +396,14 @@ int rbvae_dbg_wr_stamps(unsigned long long* buf, void* stream) {
 }
 #endif
 
-int rbvae_wgrad3x3s2_row_ok(int dtype, int Nimg, int OH, int OW, int Ca, int Cb) { return wr_ok(dtype, Nimg, OH, OW, Ca, Cb); }
+int rbvae_wgrad3x3s2_row_ok(int dtype, int Nimg, int OH, int OW, int Ca, int Cb) { return wg3x3_ok(128, dtype, Nimg, OH, OW, Ca, Cb); }
 
 /* 64-pixel blocks the K loop walks (the caller sizes ksplit against it) */
 int rbvae_wgrad3x3s2_row_blocks(int Nimg, int OH, int OW) { return wr_blocks(Nimg, OH, OW); }
 
 int rbvae_wgrad3x3s2_row(int dtype, const void* S, const void* G, float* dW_slabs, const void* zero_page, int Nimg, int OH,
                          int OW, int Ca, int Cb, int lds_, int ldg, int ksplit, void* stream) {
-    RBVAE_CHECK_ARG(S && G && dW_slabs && zero_page, "wgrad3x3s2_row: null pointer");
-    RBVAE_CHECK_ARG(wr_ok(dtype, Nimg, OH, OW, Ca, Cb), "wgrad3x3s2_row: shape not covered (dtype %d, %d x %d x %d, %d x %d channels): "
-                    "query rbvae_wgrad3x3s2_row_ok", dtype, Nimg, OH, OW, Ca, Cb);
-    RBVAE_CHECK_ARG(lds_ >= Ca && ldg >= Cb && lds_ % 8 == 0 && ldg % 8 == 0, "wgrad3x3s2_row: leading dimensions lds=%d ldg=%d", lds_, ldg);
-    RBVAE_CHECK_ARG(((uintptr_t)S | (uintptr_t)G | (uintptr_t)dW_slabs | (uintptr_t)zero_page) % 16 == 0,
-                    "wgrad3x3s2_row: pointers must be 16-byte aligned");
+    if (int rc = wg3x3_check("wgrad3x3s2_row", 128, dtype, S, G, dW_slabs, zero_page, Nimg, OH, OW, Ca, Cb, lds_, ldg)) return rc;
     RBVAE_CHECK_ARG(((long)Nimg * OH * 4 * OW + 2 * OW + 1) * ldg * 2 < (1l << 31) && (long)Nimg * OH * OW * lds_ * 2 < (1l << 31),
                     "wgrad3x3s2_row: operands of 2 GiB or more (32-bit buffer offsets)");
     WrArgs a;
@@ -426,24 +419,7 @@ int rbvae_wgrad3x3s2_row(int dtype, const void* S, const void* G, float* dW_slab
     a.stamps = g_wr_stamps;
     const int ntile = (Ca / 128) * (Cb / 128) * 3;
     const long blocks = 8 * (((long)ntile * ksplit + 7) / 8);
-    hipStream_t st = (hipStream_t)stream;
-    if (W == 8) {
-        constexpr int LDS = WR_RING * (WR_A_BYTES + 8 * 17 * 256);
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)wgrad_row_k<8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(wgrad_row_k<8>, dim3((unsigned)blocks), dim3(768), LDS, st, a);
-    } else {
-        constexpr int LDS = WR_RING * (WR_A_BYTES + 16 * 9 * 256);
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)wgrad_row_k<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(wgrad_row_k<4>, dim3((unsigned)blocks), dim3(768), LDS, st, a);
-    }
+    if (W == 8) wr_launch<8>(a, blocks, (hipStream_t)stream); else wr_launch<4>(a, blocks, (hipStream_t)stream);
     RBVAE_CHECK_LAUNCH("wgrad3x3s2_row");
     return RBVAE_OK;
 }

@@ -525,8 +525,17 @@ class Engine:
         """wgrad GEMM into K-slice slabs; their fixed-order reduction into the torch layout is a job.
         geom = (Nimg, OH, OW, IH, IW) of a 3x3 stride-2 layer (Dy rows at OH x OW, In rows at IH x IW): with the nine taps
         in one workgroup (csrc/wgrad_halo.hip) when the launch gives every workgroup enough pixel blocks."""
-        if (geom is not None and self.wgrad_halo and self.dt == BF16 and self.k == 3 and taps == 9 and idx is not None
-                and geom[3] == 2 * geom[1] and geom[4] == 2 * geom[2] and Co % 64 == 0 and Ci % 64 == 0
+        # a 3x3 stride-2 layer in bf16 with its gather table, In rows at twice the Dy extent: what both one-launch kernels need
+        s2 = (geom is not None and self.dt == BF16 and self.k == 3 and taps == 9 and idx is not None
+              and geom[3] == 2 * geom[1] and geom[4] == 2 * geom[2])
+
+        def run(kernel, ks, fn, *args):
+            slabs = self._buf(("slabs", tag), ks * Co * taps * Ci)
+            self.last_wgrad_kernel = kernel
+            L.call(fn, self.dt, Dy, In, slabs, *args, ks)
+            self._wgrad_reduce(slabs, out, Co, Ci, taps, ks, dims, strides)
+
+        if (s2 and self.wgrad_halo and Co % 64 == 0 and Ci % 64 == 0
                 and L.query("rbvae_wgrad3x3s2_halo_ok", self.dt, geom[0], geom[1], geom[2], Co, Ci)):
             nimg, oh, ow = geom[:3]
             nblk = L.query("rbvae_wgrad3x3s2_halo_blocks", nimg, oh, ow)
@@ -538,13 +547,8 @@ class Engine:
             # by every tile: the LDS-DMA alone takes 173 us (11 TB/s through the L2s), the MFMAs + fragment reads alone 137,
             # together 245 against rbvae_wgrad_gemm's 172 -- narrow layers only
             if nblk // ks >= self._wh_min_steps and ntile <= self._wh_max_tiles:
-                slabs = self._buf(("slabs", tag), ks * Co * taps * Ci)
-                self.last_wgrad_kernel = "wgrad_halo_k"
-                L.call("rbvae_wgrad3x3s2_halo", self.dt, Dy, In, slabs, self.zero, nimg, oh, ow, Co, Ci, ldy, ldi, ks)
-                self._wgrad_reduce(slabs, out, Co, Ci, taps, ks, dims, strides)
-                return
-        if (geom is not None and self.wgrad_row and self.dt == BF16 and self.k == 3 and taps == 9 and idx is not None
-                and geom[3] == 2 * geom[1] and geom[4] == 2 * geom[2]
+                return run("wgrad_halo_k", ks, "rbvae_wgrad3x3s2_halo", self.zero, nimg, oh, ow, Co, Ci, ldy, ldi)
+        if (s2 and self.wgrad_row
                 and L.query("rbvae_wgrad3x3s2_row_ok", self.dt, geom[0], geom[1], geom[2], Co, Ci)
                 and L.query("rbvae_wgrad3x3s2_row_blocks", geom[0], geom[1], geom[2]) >= self._wr_min_blocks):
             # wide layers: the three taps of one kernel row per workgroup (csrc/wgrad_row.hip) -- 50 KB of operands per
@@ -556,11 +560,7 @@ class Engine:
             # blocks, at most ~_wr_slab_mb of f32 slabs
             ks = max(1, min(self._wg_cus // ntile, nblk // self._wr_min_steps, (self._wr_slab_mb << 20) // (Co * taps * Ci * 4),
                             int(round(math.sqrt(self._wr_ks_coef * nblk)))))
-            slabs = self._buf(("slabs", tag), ks * Co * taps * Ci)
-            self.last_wgrad_kernel = "wgrad_row_k"
-            L.call("rbvae_wgrad3x3s2_row", self.dt, Dy, In, slabs, self.zero, nimg, oh, ow, Co, Ci, ldy, ldi, ks)
-            self._wgrad_reduce(slabs, out, Co, Ci, taps, ks, dims, strides)
-            return
+            return run("wgrad_row_k", ks, "rbvae_wgrad3x3s2_row", self.zero, nimg, oh, ow, Co, Ci, ldy, ldi)
         blocks = -(-Co // 128) * -(-Ci // (128 if Ci > 64 else 64)) * taps
         # K-slices: one round of workgroups on the 256 CUs, each with >= 256 pixels, and at most ~16 MB of f32
         # slabs to reduce afterwards
@@ -575,10 +575,7 @@ class Engine:
             # 0.4659 (3) / 0.472 (2) ms per step
             ks = min(ks, self._ks_small)
         ks = max(ks, -(-P // 4096))   # the kernel keeps a K-slice's gather indices in LDS
-        slabs = self._buf(("slabs", tag), ks * Co * taps * Ci)
-        self.last_wgrad_kernel = "wgrad_gemm_k<%d>" % (2 if Ci > 64 else 1)
-        L.call("rbvae_wgrad_gemm", self.dt, Dy, In, slabs, idx, self.zero, P, In.numel() // ldi, Co, Ci, ldy, ldi, taps, ks)
-        self._wgrad_reduce(slabs, out, Co, Ci, taps, ks, dims, strides)
+        run("wgrad_gemm_k<%d>" % (2 if Ci > 64 else 1), ks, "rbvae_wgrad_gemm", idx, self.zero, P, In.numel() // ldi, Co, Ci, ldy, ldi, taps)
 
     def _wgrad_reduce(self, slabs, out, Co, Ci, taps, ks, dims, strides):
         if (taps > 1 and taps <= 16 and tuple(dims) == (Co, Ci, taps) and tuple(strides) == (taps * Ci, 1, Ci)
