@@ -41,14 +41,17 @@ constexpr int CH_NA = 6;                                      // register-staged
 constexpr int CH_MT = 4, CH_NTW = 4;                         // 16 x 16 MFMA tiles per wave: 64 pixels x 64 channels
 constexpr int CH_LOADS = 2;                                   // weight LDS-DMA instructions per wave and step (8 waves)
 
-__device__ __forceinline__ unsigned ch_plane_off(int chunk) { return (unsigned)(chunk * CH_PLANE + (chunk >> 1) * 32); }
+// chunk plane `chunk` of a patch image whose planes hold `plane` bytes (+ a 32-byte stagger per chunk pair); deconv_halo_k's
+// planes depend on its strip geometry
+__device__ __forceinline__ unsigned ch_plane_off(int chunk, int plane = CH_PLANE) { return (unsigned)(chunk * plane + (chunk >> 1) * 32); }
 
 // ---- staging of conv_halo_k and upconv_halo_k (512 threads).  Patch: piece i of a thread = (slot (tid >> 3) + 64 i, chunk
 // tid & 7): 8 lanes read one pixel's 128-byte slice (coalesced) and write it to 8 chunk planes.
-// source pixel row of piece i from the slot table: -1 = zeros (padding), -2 = no such slot
-__device__ __forceinline__ int ch_piece_pix(const int* s_pix, int tid, int i) {
-    const int slot = (tid >> 3) + 64 * i;
-    return slot < CH_NSLOT_PAD ? s_pix[slot] : -2;
+// source pixel row of piece i from the slot table: -1 = zeros (padding), -2 = no such slot (SPP slots per staging pass of a
+// table of NSLOT: deconv_halo_k's depend on its waves and strip geometry)
+template <int SPP = 64, int NSLOT = CH_NSLOT_PAD> __device__ __forceinline__ int ch_piece_pix(const int* s_pix, int tid, int i) {
+    const int slot = (tid >> 3) + SPP * i;
+    return slot < NSLOT ? s_pix[slot] : -2;
 }
 // the 16 bytes of slice kc a piece loads: chunk `chunk` of pixel row pv, or of the zero page
 template <int ES>
@@ -71,7 +74,7 @@ template <int YOUNGER> __device__ __forceinline__ void ch_a_landed(u32x4_t (&ar)
 // uniform base (tile, tap, slice: scalar registers) + this 32-bit per-lane offset (row r, swizzled chunk): with per-tap 64-bit
 // lane pointers the unrolled slice body kept 18 of them live and spilled.  TAPS = tap tiles per output channel in W.
 template <int ES, int TAPS> __device__ __forceinline__ unsigned ch_blane(int r, int schunk, int Kc) {
-    return (unsigned)(r * TAPS * Kc) * ES + (unsigned)((schunk ^ ((r >> 1) & 7)) * 16);
+    return (unsigned)(r * TAPS * Kc) * ES + (unsigned)swz16(r, schunk);
 }
 // tap tile J of slice kc in W (wtile: the workgroup's first tap tile)
 template <int ES, int J> __device__ __forceinline__ const unsigned char* ch_tap_src(const unsigned char* wtile, int Kc, int kc) {
@@ -85,8 +88,8 @@ __device__ __forceinline__ void ch_tile_issue(const unsigned char* src, const un
 
 // ---- fragment reads and MFMA groups (inside the slice loops: every caller's listing is text-identical to its inline form)
 // LDS address of a lane's patch fragments: chunk plane fg of patch buffer 0; the caller adds its slot (row * CH_PW + column) * 16
-__device__ __forceinline__ unsigned ch_aplane(unsigned lds0, int fg) {
-    return lds0 + (unsigned)fg * CH_PLANE + (unsigned)(fg >> 1) * 32;
+__device__ __forceinline__ unsigned ch_aplane(unsigned lds0, int fg, int plane = CH_PLANE) {
+    return lds0 + (unsigned)fg * plane + (unsigned)(fg >> 1) * 32;
 }
 // ... and of its weight fragment in ring slot 0: row `row` of the tap tile, 16-byte chunk `chunk` (swizzled by the caller:
 // XOR (fi >> 1) & 7)
@@ -108,19 +111,7 @@ __device__ __forceinline__ void ch_read_half(const unsigned (&ta)[CH_MT], unsign
     for (int nt = 0; nt < CH_NTW; ++nt)
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[nt]) : "v"(ab_), "n"(BOFF + nt * 2048));
 }
-// the eight fragments have landed: at most YOUNGER LDS operations are still outstanding
-template <int YOUNGER> __device__ __forceinline__ void ch_landed(u32x4_t (&fa)[CH_MT], u32x4_t (&fb)[CH_NTW]) {
-    asm volatile("s_waitcnt lgkmcnt(%8)"
-                 : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3])
-                 : "n"(YOUNGER));
-}
-template <typename T>
-__device__ __forceinline__ void ch_mma_half(f32x4_t (&acc)[CH_MT][CH_NTW], const u32x4_t (&fa)[CH_MT], const u32x4_t (&fb)[CH_NTW]) {
-#pragma unroll
-    for (int mt = 0; mt < CH_MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < CH_NTW; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
-}
+// (their counted wait and the 4 x 4 MFMA group are mma.h's frag_landed<YOUNGER> and mma_group<T>)
 
 // ---- epilogue
 // two accumulators + bias -> one word of two bf16 (the lower index in the low half).  The sums are formed HERE: with epilogue.h's
@@ -145,13 +136,6 @@ template <typename T, int RING> constexpr int ch_lds_main() {
     constexpr int ring = 2 * CH_ABUF + RING * CH_BBYTES;
     constexpr int epi = CH_BM * (CH_BN * (int)sizeof(T) + 16);
     return ring > epi ? ring : epi;
-}
-// row pitches and pointer alignment of the wrapper named `who` (ptrs: every pointer of the call OR-ed together)
-static inline int ch_check_rows(const char* who, int ES, int Kc, int Nout, int lda, int ldo, uintptr_t ptrs) {
-    RBVAE_CHECK_ARG(lda >= Kc && (lda * ES) % 16 == 0 && ldo >= Nout && (ldo * ES) % 16 == 0,
-                    "%s: leading dimensions lda=%d ldo=%d", who, lda, ldo);
-    RBVAE_CHECK_ARG(ptrs % 16 == 0, "%s: pointers must be 16-byte aligned", who);
-    return RBVAE_OK;
 }
 
 // conv_halo_ws.hip: the persistent bf16 kernel (covers: operands below 2 GiB -- 32-bit buffer offsets --, Kc % 64 == 0,

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    // One 32-k half of a step (ch_read_half, ch_landed, ch_mma_half).  The tap and the ring slot are compile-time constants
+    // One 32-k half of a step (ch_read_half, frag_landed, mma_group).  The tap and the ring slot are compile-time constants
     // (the nine taps of a slice are unrolled).
     unsigned ta[MT];                         // patch read addresses of the slice being read (buffer folded in)
     auto set_slice = [&](int kc) {
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
     auto mma_half_stage = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW], int kcn, auto i_tag) {
         constexpr int I = decltype(i_tag)::value;
         const u32x4_t v = gn_piece(areg[I], kcn, pixr[I]);
-        ch_mma_half<T>(acc, fa, fb);
+        mma_group<T>(acc, fa, fb);
         if constexpr (GN && ES == 2) {
 #pragma unroll
             for (int k = 0; k < MT * NTW; ++k) {
@@ -247,14 +247,14 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
             constexpr int nj = (j + 1) % 9;                  // tap of the next step
             using NJ = std::integral_constant<int, nj>;
             read_half(j_tag, K1{}, fa1, fb1);
-            ch_landed<MT + NTW>(fa0, fb0);
+            frag_landed<MT + NTW>(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            ch_mma_half<T>(acc, fa0, fb0);
+            mma_group<T>(acc, fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            ch_landed<0>(fa1, fb1);
+            frag_landed<0>(fa1, fb1);
             if constexpr (j == 8 && !more) {                 // the very last step reads nothing ahead
                 __builtin_amdgcn_sched_barrier(0);
-                ch_mma_half<T>(acc, fa1, fb1);
+                mma_group<T>(acc, fa1, fb1);
             } else {
                 const int kn = j == 8 ? kc + 1 : kc;         // slice of the next step
                 // does a slice follow the NEXT step's slice?  (compile-time inside a slice; at the hand-over to the
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(512) void conv_halo_k(const ChArgs p) {
                 if constexpr (nj >= 3 && nj < 3 + CH_NA && more) mma_half_stage(fa1, fb1, kn + 1, std::integral_constant<int, nj - 3>{});
                 else
 #endif
-                    ch_mma_half<T>(acc, fa1, fb1);
+                    mma_group<T>(acc, fa1, fb1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
@@ -536,7 +536,7 @@ extern "C" int rbvae_conv3x3_halo(int dtype, const void* A, const void* W, void*
     RBVAE_CHECK_ARG(rbvae_conv3x3_halo_ok(dtype, IH, IW, OH, OW, Kc, Nout),
                     "conv3x3_halo: shape not covered (dtype %d, %dx%d -> %dx%d, Kc %d, Nout %d)", dtype, IH, IW, OH, OW, Kc, Nout);
     const int ES = dtype == RBVAE_F32 ? 4 : 2;
-    if (const int e = ch_check_rows("conv3x3_halo", ES, Kc, Nout, lda, ldo,
+    if (const int e = epi_check_rows("conv3x3_halo", ES, Kc, Nout, lda, ldo,
                                     (uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)addend | (uintptr_t)bias))
         return e;
     RBVAE_CHECK_ARG(Nimg > 0 && (long)Nimg * IH * IW < (1l << 30) && (long)Nimg * OH * OW < (1l << 30),

@@ -356,7 +356,7 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
         ch_read_half<kk * CH_KKOFF + ((j / 3) * CH_PW + (j % 3)) * 16, 0>(ta, kk == 0 ? offB0 : offB1, rs, fa, fb);
     };
     // (a lambda around the shared step: called directly from the slice body it changes both instances' register allocation)
-    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) { ch_mma_half<bf16_t>(acc, fa, fb); };
+    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) { mma_group<bf16_t>(acc, fa, fb); };
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
     u32x4_t xa[MT], xb[NTW], ya[MT], yb[NTW];
@@ -380,12 +380,12 @@ __global__ __launch_bounds__(768, 1) void conv_halo_ws_k(const ChArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             mma_half(ya, yb);
             __builtin_amdgcn_sched_barrier(0);
-            ch_landed<0>(xa, xb);
+            frag_landed<0>(xa, xb);
             read_half(j_tag, K1{}, rs, ya, yb);
             __builtin_amdgcn_sched_barrier(0);
             mma_half(xa, xb);
             __builtin_amdgcn_sched_barrier(0);
-            ch_landed<0>(ya, yb);
+            frag_landed<0>(ya, yb);
         });
     };
 

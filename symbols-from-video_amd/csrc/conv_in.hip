@@ -52,7 +52,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
             const int r = q * 8 + srow;
             const int ct = r >> 4, j = r & 15;
             const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
-            const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + en_swz16(r, schunk) : p.zero;
+            const unsigned char* src = ch < p.Nout ? p.W + (size_t)ch * 128 + swz16(r, schunk) : p.zero;
             glds16(src, s_b + (size_t)(r - srow) * 128);
         }
     }
@@ -124,7 +124,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, NQ == 1 ? 8 : 4) vo
         for (int h = 0; h < 4; ++h) acc[mt][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int ch = en_frag_ch(kk, fg, fsw);
+        const int ch = frag_ch(kk, fg, fsw);
         u32x4_t wv[4], av[MT];
 #pragma unroll
         for (int h = 0; h < 4; ++h) wv[h] = *(const u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);

@@ -71,7 +71,7 @@ __host__ __device__ constexpr int cs_pp_before(int j) { int s = 0; for (int k = 
 
 template <int BN> constexpr int cs_lds_main() {
     constexpr int ring = 2 * CS_PATCH + CS_RING * BN * 64;
-    constexpr int epi = CS_BM * (BN * 2 + 16) + 16 * BN * 4;      // output tile + column-sum scratch
+    constexpr int epi = CS_BM * StoreRoles<bf16_t, BN, 512, CS_BM>::PITCH + 16 * BN * 4;      // output tile + column-sum scratch
     return ring > epi ? ring : epi;
 }
 
@@ -203,7 +203,8 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    // fragment reads (inline asm: invisible to the compiler's wait-count pass; isa_check proves the counted waits)
+    // fragment reads (inline asm: invisible to the compiler's wait-count pass; isa_check proves the counted waits, mma.h's
+    // frag_landed<0>)
     auto read_unit = [&](auto j_tag, unsigned pbuf, unsigned rslot, u32x4_t (&fa)[MT], u32x4_t (&fb)[NT]) {
         constexpr int j = decltype(j_tag)::value, kh = j / 3, kw = j % 3;
         constexpr bool codd = kw != 1;
@@ -218,23 +219,11 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
         for (int mt = 0; mt < MT; ++mt)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[mt]) : "v"(aa), "n"(aimm + mt * pitch * 16));
     };
-    auto landed = [&](u32x4_t (&fa)[MT], u32x4_t (&fb)[NT]) {
-        if constexpr (MT == 4)
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-        else
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-    };
     // the MFMAs of output rows m0 .. m0 + MT / 2 - 1 of a unit (weights as the row operand: a lane owns 4 consecutive output
     // channels of one pixel)
     auto mma_half = [&](auto m0_tag, const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NT]) {
         constexpr int M0 = decltype(m0_tag)::value;
-#pragma unroll
-        for (int mt = M0; mt < M0 + MT / 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&fb[nt], *(const bf16x8_t*)&fa[mt],
-                                                                      acc[mt][nt], 0, 0, 0);
+        mma_rows<bf16_t, M0, M0 + MT / 2>(acc, fa, fb);
     };
     using MLO = std::integral_constant<int, 0>;
     using MHI = std::integral_constant<int, MT / 2>;
@@ -261,14 +250,14 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
                 mma_half(MHI{}, ya, yb);
                 __builtin_amdgcn_sched_barrier(0);
-                landed(xa, xb);
+                frag_landed<0>(xa, xb);
                 mma_half(MLO{}, xa, xb);
             } else {
                 read_unit(j_tag, pbuf, rslot, ya, yb);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_half(MHI{}, xa, xb);
                 __builtin_amdgcn_sched_barrier(0);
-                landed(ya, yb);
+                frag_landed<0>(ya, yb);
                 mma_half(MLO{}, ya, yb);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -296,10 +285,8 @@ __global__ __launch_bounds__(768, 1) void conv_s2_k(const CsArgs p) {
     lds_barrier();                           // (the producer waves have left: the barrier counts the MFMA waves only)
 
     // ---- epilogue: bias, ReLU, scale -> bf16 tile in LDS -> dropout / gate -> 16-byte NHWC stores, column sums
-    constexpr int PITCH = BN * 2 + 16;
-    constexpr int CPR = BN / 8;                  // 16-byte chunks per tile row
-    constexpr int RL = 512 / CPR;                // row lanes of the store phase
-    constexpr int ITERS = CS_BM / RL;
+    using SR = StoreRoles<bf16_t, BN, 512, CS_BM>;            // (the eight MFMA waves)
+    constexpr int PITCH = SR::PITCH, CPR = SR::CPR, RL = SR::RL, ITERS = SR::ITERS;
     unsigned char* tl = smem;
     float* red = (float*)(smem + CS_BM * PITCH);            // [RL][BN]
 #pragma unroll
@@ -372,11 +359,7 @@ template <int BN>
 static int launch_cs(const CsArgs& a, hipStream_t st) {
     constexpr size_t lds = (size_t)cs_lds_main<BN>() + CS_BM * 4 + 16;
     static_assert(lds <= 160 * 1024, "LDS carve");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_s2_k<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    lds_attr_once<conv_s2_k<BN>>((int)lds);
     hipLaunchKernelGGL((conv_s2_k<BN>), dim3(a.total), dim3(768), lds, st, a);
     RBVAE_CHECK_LAUNCH("conv3x3s2_halo");
     return RBVAE_OK;
@@ -403,10 +386,10 @@ int rbvae_conv3x3s2_halo(int dtype, const void* A, const void* W, void* Out, con
     const int bn = cs_bn(dtype, Nimg, IH, IW, Kc, Nout);
     RBVAE_CHECK_ARG(bn, "conv3x3s2_halo: shape not covered (dtype %d, %d x %d x %d, Kc %d, Nout %d): query rbvae_conv3x3s2_halo_ok",
                     dtype, Nimg, IH, IW, Kc, Nout);
-    RBVAE_CHECK_ARG(lda >= Kc && lda % 8 == 0 && ldo >= Nout && ldo % 8 == 0, "conv3x3s2_halo: leading dimensions lda=%d ldo=%d", lda, ldo);
+    if (const int e = epi_check_pitch("conv3x3s2_halo", 2, Kc, Nout, lda, ldo)) return e;
     RBVAE_CHECK_ARG((long)Nimg * IH * IW * lda * 2 < (1l << 31), "conv3x3s2_halo: input of 2 GiB or more (32-bit buffer offsets)");
-    RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)gate | (uintptr_t)bias) % 16 == 0,
-                    "conv3x3s2_halo: pointers must be 16-byte aligned");
+    if (const int e = epi_check_align("conv3x3s2_halo", (uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)gate | (uintptr_t)bias))
+        return e;
     CsArgs a;
     if (const int e = epi_drop_args("conv3x3s2_halo", drop_mode, mask, drop_p, &a.drop_thresh)) return e;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;

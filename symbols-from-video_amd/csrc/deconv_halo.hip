@@ -22,7 +22,7 @@
 // wave behind one barrier.  8 waves as 4 (pixel rows) x 2 (channel halves).  Epilogue class by class through one LDS tile:
 // bias, ReLU, scale, keyed / explicit dropout, ReLU gate of the layer below, per-tile column sums (bias gradients) --
 // element for element the arithmetic of rbvae_gather_gemm's epilogue (same dropout element indices).
-#include "epilogue.h"
+#include "conv_halo.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -72,12 +72,11 @@ constexpr int DH_BN = 64;
 constexpr int DH_TAPB = DH_BN * 128;          // one tap's weight tile
 constexpr int DH_STAGE = 2 * DH_TAPB;         // a step's stage: two taps
 
-__device__ __forceinline__ unsigned dh_plane_off(int chunk, int plane) { return (unsigned)(chunk * plane + (chunk >> 1) * 32); }
-
 template <typename T, int SC, int WAVES> constexpr int dh_lds_main() {
-    constexpr int ES = sizeof(T), BM = 32 * WAVES;
+    constexpr int BM = 32 * WAVES;
     constexpr int ring = 2 * DhGeom<SC, BM>::ABUF + (WAVES == 8 ? 3 : 2) * DH_STAGE;
-    constexpr int epi = BM * (DH_BN * ES + 16) + (64 * WAVES / (DH_BN / (16 / ES))) * DH_BN * 4;
+    using SR = StoreRoles<T, DH_BN, 64 * WAVES, BM>;
+    constexpr int epi = BM * SR::PITCH + SR::RL * DH_BN * 4;      // class tile + column-sum scratch
     return ring > epi ? ring : epi;
 }
 
@@ -102,18 +101,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifndef DH_STAGGER
-#define DH_STAGGER 0
-#endif
-#if DH_STAGGER
-    // Two workgroups share a CU and every workgroup does the same work, so left alone they run in phase: both in the MFMA
-    // loop, then both in the (HBM-bound) epilogue.  The second workgroup of each CU in the launch's first round starts
-    // half a tile late; the phases then stay apart for the rest of the launch.  Speed only: every tile is computed whatever
-    // the placement.
-    if (WAVES == 4 && p.total >= 1024 && blockIdx.x >= 256 && blockIdx.x < 512) {
-        for (int i = 0; i < DH_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     const int item = xcd_item(blockIdx.x, p.total);
     const int mtile = item / p.ntn, ntile = item - mtile * p.ntn;
     const int n0 = ntile * DH_BN;
@@ -167,17 +154,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     // at once cost 28 registers beside 128 of accumulators and 48 of fragments, and the kernel spilled
     constexpr int NB0 = (NA + 1) / 2, NB1 = NA - NB0;
     u32x4_t areg[NB0];
-    auto piece_pix = [&](int i) {                      // -1: zero (padding), -2: no such slot (LDS read: only behind a barrier)
-        const int slot = (tid >> 3) + SPP * i;
-        return slot < G::NSLOT_PAD ? s_pix[slot] : -2;
-    };
     auto a_load = [&](int kc, auto b_tag, u32x4_t (&ar)[NB0]) {
         constexpr int b = decltype(b_tag)::value, i0 = b ? NB0 : 0, n = b ? NB1 : NB0;
 #pragma unroll
         for (int i = 0; i < n; ++i) {
-            const int pv = piece_pix(i0 + i);
+            const int pv = ch_piece_pix<SPP, G::NSLOT_PAD>(s_pix, tid, i0 + i);      // (an LDS read: only behind a barrier)
+            // (inline: mirrors conv_halo.h ch_piece_src<ES>, which changes the six bf16 instances)
             const unsigned char* src = pv >= 0 ? p.A + ((size_t)pv * p.lda) * ES + (size_t)kc * 128 + chunk * 16 : zsrc;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ar[i]) : "v"(src) : "memory");
+            ar[i] = ch_piece_load(src);
         }
     };
     auto a_landed = [](auto younger_tag, u32x4_t (&ar)[NB0]) {
@@ -190,7 +174,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     };
     auto a_write = [&](int buf, auto b_tag, u32x4_t (&ar)[NB0]) {
         constexpr int b = decltype(b_tag)::value, i0 = b ? NB0 : 0, n = b ? NB1 : NB0;
-        const unsigned base = lds0 + (unsigned)buf * G::ABUF + dh_plane_off(chunk, G::PLANE) + (unsigned)(tid >> 3) * 16;
+        const unsigned base = lds0 + (unsigned)buf * G::ABUF + ch_plane_off(chunk, G::PLANE) + (unsigned)(tid >> 3) * 16;
 #pragma unroll
         for (int i = 0; i < n; ++i)
             if ((tid >> 3) + SPP * (i0 + i) < G::NSLOT_PAD)
@@ -206,7 +190,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
         const int brow = ((w * LOADS + i) & 7) * 8 + srow;
-        blane[i] = (unsigned)(brow * 9 * p.Kc) * ES + (unsigned)((schunk ^ ((brow >> 1) & 7)) * 16);
+        blane[i] = ch_blane<ES, 9>(brow, schunk, p.Kc);
     }
     const unsigned char* wtile = p.W + ((size_t)n0 * 9 * p.Kc) * ES;
     const int nkc = p.Kc / KE;
@@ -215,8 +199,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
         constexpr int s = decltype(s_tag)::value;
         unsigned char* lb = smem + A_BYTES + pslot * DH_STAGE + (w * LOADS) * 1024;
         constexpr int t0 = 2 * s, t1 = s < 4 ? 2 * s + 1 : 8;         // step 4 has one tap: its second half repeats it
-        const unsigned char* src0 = wtile + ((size_t)DH_WIDX[t0] * p.Kc) * ES + (size_t)kc * 128;
-        const unsigned char* src1 = wtile + ((size_t)DH_WIDX[t1] * p.Kc) * ES + (size_t)kc * 128;
+        const unsigned char* src0 = ch_tap_src<ES, DH_WIDX[t0]>(wtile, p.Kc, kc);
+        const unsigned char* src1 = ch_tap_src<ES, DH_WIDX[t1]>(wtile, p.Kc, kc);
 #pragma unroll
         for (int i = 0; i < LOADS; ++i) glds16((((w * LOADS + i) >> 3) ? src1 : src0) + blane[i], lb + i * 1024);
         pslot = (pslot + 1 == RING) ? 0 : pslot + 1;
@@ -232,11 +216,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
         const int i = t / SC, c = t - i * SC;
         const int gg = min(g0 + i, p.grows - 1);
         const int pr = i + (gg / p.TH - s0);
-        ta[mt] = lds0 + (unsigned)fg * G::PLANE + (unsigned)(fg >> 1) * 32 + (unsigned)(pr * G::PW + c) * 16;
+        ta[mt] = ch_aplane(lds0, fg, G::PLANE) + (unsigned)(pr * G::PW + c) * 16;
     }
     const int fsw = (fi >> 1) & 7;
-    const unsigned offB0 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((0 + fg) ^ fsw) * 16);
-    const unsigned offB1 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)(((4 + fg) ^ fsw) * 16);
+    const unsigned offB0 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)frag_ch(0, fg, fsw);
+    const unsigned offB1 = lds0 + A_BYTES + (unsigned)(wc * NTW * 16 + fi) * 128 + (unsigned)frag_ch(1, fg, fsw);
 
     f32x4_t acc[4][MT][NTW];
 #pragma unroll
@@ -271,21 +255,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
         for (int nt = 0; nt < NTW; ++nt)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[nt]) : "v"(ab_), "n"(boff + nt * 2048));
     };
-    auto landed = [&](auto younger_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
-        constexpr int YOUNGER = decltype(younger_tag)::value;
-        asm volatile("s_waitcnt lgkmcnt(%6)"
-                     : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1])
-                     : "n"(YOUNGER));
-    };
     auto mma_half = [&](auto h_tag, const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) {
-        constexpr int cls = DH_CLS[decltype(h_tag)::value >> 1];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[cls][mt][nt], fb[nt], fa[mt]);
+        mma_group<T>(acc[DH_CLS[decltype(h_tag)::value >> 1]], fa, fb);
     };
-    using Younger = std::integral_constant<int, MT + NTW>;
-    using None = std::integral_constant<int, 0>;
 
     // ---- prologue: patch of slice 0, the first AHEAD weight stages
     b_issue(0, std::integral_constant<int, 0>{});
@@ -320,12 +292,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
             auto& fa_n = cur0 ? fa1 : fa0;
             auto& fb_n = cur0 ? fb1 : fb0;
             if constexpr (last_of_slice && !more) {
-                landed(None{}, fa_c, fb_c);
+                frag_landed<0>(fa_c, fb_c);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_half(h_tag, fa_c, fb_c);
             } else if constexpr (!boundary) {
                 read_half(HN{}, fa_n, fb_n);
-                landed(Younger{}, fa_c, fb_c);
+                frag_landed<MT + NTW>(fa_c, fb_c);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_half(h_tag, fa_c, fb_c);
                 __builtin_amdgcn_sched_barrier(0);
@@ -333,12 +305,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
                 constexpr int ns = last_of_slice ? 0 : DH_STEP_OF[t] + 1;       // step being opened
                 const int kn = last_of_slice ? kc + 1 : kc;
                 const bool moren = last_of_slice ? kn + 1 < nkc : more;          // a slice follows the opened step's slice
-                landed(None{}, fa_c, fb_c);
+                frag_landed<0>(fa_c, fb_c);
                 // the opened step's stage has landed; younger: the stage behind it (none behind the very last step), and
                 // when steps 2 / 3 open the patch batch issued behind it
                 constexpr int young = (more || last_of_slice) ? AHEAD - 1 : (AHEAD - 1 < 4 - ns ? AHEAD - 1 : 4 - ns);
-                if (last_of_slice && !moren && AHEAD - 1 > 4) wait_vm_lgkm_barrier<0>();      // (never: AHEAD <= 2)
-                else if constexpr (ns == 2 && more) wait_vm_lgkm_barrier<young * LOADS + NB0>();
+                if constexpr (ns == 2 && more) wait_vm_lgkm_barrier<young * LOADS + NB0>();
                 else if constexpr (ns == 3 && more) wait_vm_lgkm_barrier<young * LOADS + NB1>();
                 else wait_vm_lgkm_barrier<young * LOADS>();
                 cslot = (cslot + 1 == RING) ? 0 : cslot + 1;
@@ -385,10 +356,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void deconv_halo_k(
     // ---- epilogue.  As many of the four class tiles as fit go to LDS at once (bf16: all four), then every store of the
     // round is issued back to back with the ReLU-gate chunks fetched ahead of them: with one class per barrier pair a CU
     // had 32 KB of stores in flight and the phase ran latency-bound at half the HBM write rate.
-    constexpr int PITCH = DH_BN * ES + 16;
-    constexpr int CPR = DH_BN / EC;              // 16-B chunks per tile row
-    constexpr int RL = THREADS / CPR;            // row lanes of the store phase
-    constexpr int ITERS = DH_BM / RL;
+    using SR = StoreRoles<T, DH_BN, THREADS, DH_BM>;
+    constexpr int PITCH = SR::PITCH, CPR = SR::CPR, RL = SR::RL, ITERS = SR::ITERS;
     constexpr int RED_BYTES = RL * DH_BN * 4;
     constexpr int FIT = (MAIN - RED_BYTES) / (DH_BM * PITCH);
     constexpr int CPRD = FIT >= 4 ? 4 : FIT >= 2 ? 2 : 1;       // classes per round
@@ -493,15 +462,16 @@ static int launch_dh(const DhArgs& a, hipStream_t st) {
     using G = DhGeom<SC, 32 * WAVES>;
     const size_t lds = (size_t)dh_lds_main<T, SC, WAVES>() + 32 * WAVES * 4 + G::NSLOT_PAD * 4 + (G::MAXROWS + 2) * 4 + 16;
     if (lds > (WAVES == 4 ? 80 : 160) * 1024) return fail(RBVAE_E_UNSUPPORTED, "deconv3x3s2_halo: %zu bytes of LDS", lds);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)deconv_halo_k<T, SC, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (WAVES == 4 ? 80 : 160) * 1024);
-        attr_set = true;
-    }
+    lds_attr_once<deconv_halo_k<T, SC, WAVES>>((WAVES == 4 ? 80 : 160) * 1024);
     hipLaunchKernelGGL((deconv_halo_k<T, SC, WAVES>), dim3(a.total), dim3(64 * WAVES), lds, st, a);
     RBVAE_CHECK_LAUNCH("deconv3x3s2_halo");
     return RBVAE_OK;
+}
+
+// the instance for tile rows bm (128: 4 waves, 256: 8) and strip columns sc (16 / 8 / 4)
+template <typename T> static int dispatch_dh(const DhArgs& a, hipStream_t st, int bm, int sc) {
+    if (bm == 128) return sc == 16 ? launch_dh<T, 16, 4>(a, st) : sc == 8 ? launch_dh<T, 8, 4>(a, st) : launch_dh<T, 4, 4>(a, st);
+    return sc == 16 ? launch_dh<T, 16, 8>(a, st) : sc == 8 ? launch_dh<T, 8, 8>(a, st) : launch_dh<T, 4, 8>(a, st);
 }
 
 static int dh_strip_cols(int TW) { return TW % 16 == 0 ? 16 : TW % 8 == 0 ? 8 : TW % 4 == 0 ? 4 : 0; }
@@ -517,9 +487,8 @@ static int dh_tile_rows(int dtype, int Nimg, int TH, int TW, int Kc, int Nout) {
     const int sc = dh_strip_cols(TW);
     if (!sc) return 0;
     if ((long)Nimg * (TW / sc) >= (1l << 19)) return 0;          // strip index in 19 bits of the patch-row table
-    constexpr int force = 0;
-    if (force != 256 && dh_max_patch_rows(TH, 128 / sc) <= 176 / (sc + 1)) return 128;
-    if (force != 128 && dh_max_patch_rows(TH, 256 / sc) <= (sc == 16 ? 320 : sc == 8 ? 352 : 416) / (sc + 1)) return 256;
+    if (dh_max_patch_rows(TH, 128 / sc) <= 176 / (sc + 1)) return 128;
+    if (dh_max_patch_rows(TH, 256 / sc) <= (sc == 16 ? 320 : sc == 8 ? 352 : 416) / (sc + 1)) return 256;
     return 0;
 }
 
@@ -552,11 +521,11 @@ extern "C" int rbvae_deconv3x3s2_halo(int dtype, const void* A, const void* W, v
     RBVAE_CHECK_ARG(bm != 0, "deconv3x3s2_halo: shape not covered (dtype %d, %d x %dx%d, Kc %d, Nout %d)", dtype, Nimg, TH, TW,
                     Kc, Nout);
     const int ES = dtype == RBVAE_F32 ? 4 : 2;
-    RBVAE_CHECK_ARG(lda >= Kc && (lda * ES) % 16 == 0 && ldo >= Nout && (ldo * ES) % 16 == 0,
-                    "deconv3x3s2_halo: leading dimensions lda=%d ldo=%d", lda, ldo);
+    if (const int e = epi_check_pitch("deconv3x3s2_halo", ES, Kc, Nout, lda, ldo)) return e;
     RBVAE_CHECK_ARG((long)Nimg * TH * TW * 4 < (1l << 30), "deconv3x3s2_halo: more than 2^30 output pixel rows");
-    RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)gate | (uintptr_t)bias) % 16 == 0,
-                    "deconv3x3s2_halo: pointers must be 16-byte aligned");
+    if (const int e = epi_check_align("deconv3x3s2_halo", (uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page |
+                                                              (uintptr_t)gate | (uintptr_t)bias))
+        return e;
     DhArgs a;
     if (const int e = epi_drop_args("deconv3x3s2_halo", drop_mode, mask, drop_p, &a.drop_thresh)) return e;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
@@ -571,10 +540,5 @@ extern "C" int rbvae_deconv3x3s2_halo(int dtype, const void* A, const void* W, v
     a.ntn = Nout / DH_BN;
     a.total = a.mtiles * a.ntn;
     hipStream_t st = (hipStream_t)stream;
-#define DH_DISPATCH(TT)                                                                                                   \
-    if (bm == 128) return sc == 16 ? launch_dh<TT, 16, 4>(a, st) : sc == 8 ? launch_dh<TT, 8, 4>(a, st) : launch_dh<TT, 4, 4>(a, st); \
-    return sc == 16 ? launch_dh<TT, 16, 8>(a, st) : sc == 8 ? launch_dh<TT, 8, 8>(a, st) : launch_dh<TT, 4, 8>(a, st);
-    if (dtype == RBVAE_F32) { DH_DISPATCH(float) }
-    DH_DISPATCH(bf16_t)
-#undef DH_DISPATCH
+    return dtype == RBVAE_F32 ? dispatch_dh<float>(a, st, bm, sc) : dispatch_dh<bf16_t>(a, st, bm, sc);
 }

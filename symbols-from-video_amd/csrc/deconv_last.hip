@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256, 3) void deconv_last_fused_k(const DlArgs p) {
         const int q = w + 4 * i;
         const bool is_w = q >= PIX_I;
         const int r = (is_w ? q - PIX_I : q) * 8 + srow;
-        const int sw = en_swz16(r, schunk);
+        const int sw = swz16(r, schunk);
         const unsigned char* src = p.zero;
         unsigned inc = 0;
         if (is_w) {
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256, 3) void deconv_last_fused_k(const DlArgs p) {
             for (int q = w; q < PIX_I + WTS_I; q += 4) {
                 const bool is_w = q >= PIX_I;
                 const int r = (is_w ? q - PIX_I : q) * 8 + srow;
-                const int sw = en_swz16(r, schunk);
+                const int sw = swz16(r, schunk);
                 const unsigned char* src = p.zero;
                 if (is_w) {
                     if (r < p.NYP) src = p.V + ((size_t)r * p.C1) * 2 + s * 128 + sw;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 3) void deconv_last_fused_k(const DlArgs p) {
         }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            const int ch = en_frag_ch(kk, fg, fsw);
+            const int ch = frag_ch(kk, fg, fsw);
             u32x4_t wf[3], pf[3];
 #pragma unroll
             for (int rt = 0; rt < 3; ++rt) wf[rt] = en_frag_asm(lds_wts + (unsigned)((buf * EN_WROWS + rt * 16 + fi) * 128 + ch));

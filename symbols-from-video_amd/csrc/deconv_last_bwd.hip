@@ -107,7 +107,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         const int r = idx >> 3, sc = idx & 7;
         const int ct = r >> 4, j = r & 15;
         const int ch = 64 * (ct >> 2) + 16 * (j >> 2) + 4 * (ct & 3) + (j & 3);
-        wreg[it] = *(const u32x4_t*)(ch < p.C1 ? p.W + (size_t)ch * 128 + en_swz16(r, sc) : p.zero);
+        wreg[it] = *(const u32x4_t*)(ch < p.C1 ? p.W + (size_t)ch * 128 + swz16(r, sc) : p.zero);
     }
     // the patch starts as zeros: output pixels outside the image and channels never written read as padding
     for (int i = tid; i < FB_PATCH_BYTES / 4; i += 512) s_patch[i] = 0.f;
@@ -152,7 +152,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
             const int q = w + 8 * i;
             const bool is_w = q >= PIX_I;
             const int r = (is_w ? q - PIX_I : q) * 8 + srow;
-            const int sw = en_swz16(r, schunk);
+            const int sw = swz16(r, schunk);
             const unsigned char* src = p.zero;
             unsigned inc = 0;
             if (is_w) {
@@ -207,7 +207,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            const int ch = en_frag_ch(kk, fg, fsw);
+            const int ch = frag_ch(kk, fg, fsw);
             u32x4_t wf[3], pf[2];
 #pragma unroll
             for (int rt = 0; rt < 3; ++rt) wf[rt] = en_frag_asm(lds_wts + (unsigned)((buf * EN_WROWS + rt * 16 + fi) * 128 + ch));
@@ -391,7 +391,7 @@ template <int CIN, int NQ> __global__ __launch_bounds__(512, 4) void deconv_last
         for (int h = 0; h < 4; ++h) dacc[mt][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int ch = en_frag_ch(kk, fg, fsw);
+        const int ch = frag_ch(kk, fg, fsw);
         u32x4_t wv[4], av[MT];
 #pragma unroll
         for (int h = 0; h < 4; ++h) wv[h] = *(const u32x4_t*)(s_b + ((4 * wq + h) * 16 + fi) * 128 + ch);

@@ -68,12 +68,10 @@ __device__ __forceinline__ const unsigned char* en_row_src(const unsigned char* 
 }
 // The [rows][128 B] LDS images the b128 fragment reads take (im2col rows, weight rows, d2 / V slices) keep 16-byte chunk c of
 // row r at chunk c ^ ((r >> 1) & 7): its byte offset in the row (an LDS-DMA writes a row's chunks in lane order, so the lane
-// swizzles its SOURCE chunk with the same expression), ...
-__device__ __forceinline__ int en_swz16(int r, int c) { return (c ^ ((r >> 1) & 7)) * 16; }
+// swizzles its SOURCE chunk with the same expression): mma.h's swz16(r, c); ...
 // ... in the image, ...
-__device__ __forceinline__ int en_a_off(int r, int c) { return r * 128 + en_swz16(r, c); }
-// ... and the offset of a lane's fragment chunk in 32-k half kk: chunk 4 kk + fg of its row, fsw = (fi >> 1) & 7
-__device__ __forceinline__ int en_frag_ch(int kk, int fg, int fsw) { return ((4 * kk + fg) ^ fsw) * 16; }
+__device__ __forceinline__ int en_a_off(int r, int c) { return r * 128 + swz16(r, c); }
+// ... and the offset of a lane's fragment chunk in a 32-k half: mma.h's frag_ch(kk, fg, fsw)
 // a fragment by asm, at an LDS address: behind LDS-DMA in flight a C++ read would make the compiler drain all of it; the
 // caller's tied s_waitcnt covers the read
 __device__ __forceinline__ u32x4_t en_frag_asm(unsigned ad) {

@@ -20,7 +20,8 @@
 // kernel instance: where some instance changes with every form tried, that kernel keeps the step as inline text, with a
 // comment naming the helper and the instance (DESIGN.md lists these sites).  A new kernel starts from the helpers.
 //
-// Host part: epi_drop_args, the dropout argument check and threshold of the C-ABI wrappers.
+// Host part: epi_drop_args, the dropout argument check and threshold of the C-ABI wrappers; epi_check_rows and its halves,
+// their pitch / alignment check (also the halo stride-1 wrappers').
 #pragma once
 #include "mma.h"
 
@@ -34,6 +35,21 @@ static inline int epi_drop_args(const char* who, int drop_mode, const void* mask
     RBVAE_CHECK_ARG(drop_mode != 1 || (drop_p >= 0 && drop_p < 1), "%s: drop_p=%g outside [0, 1)", who, (double)drop_p);
     *drop_thresh = (unsigned)((double)drop_p * 4294967296.0);
     return RBVAE_OK;
+}
+// Row pitches and pointer alignment of the wrapper named `who` (ptrs: every pointer of the call OR-ed together).  Two halves,
+// called one by one where a wrapper has other checks between them (a caller sees the messages in the old order), and both.
+static inline int epi_check_pitch(const char* who, int ES, int Kc, int Nout, int lda, int ldo) {
+    RBVAE_CHECK_ARG(lda >= Kc && ((long)lda * ES) % 16 == 0 && ldo >= Nout && ((long)ldo * ES) % 16 == 0,
+                    "%s: leading dimensions lda=%d ldo=%d", who, lda, ldo);
+    return RBVAE_OK;
+}
+static inline int epi_check_align(const char* who, uintptr_t ptrs) {
+    RBVAE_CHECK_ARG(ptrs % 16 == 0, "%s: pointers must be 16-byte aligned", who);
+    return RBVAE_OK;
+}
+static inline int epi_check_rows(const char* who, int ES, int Kc, int Nout, int lda, int ldo, uintptr_t ptrs) {
+    if (const int e = epi_check_pitch(who, ES, Kc, Nout, lda, ldo)) return e;
+    return epi_check_align(who, ptrs);
 }
 
 // ---- device ---------------------------------------------------------------------------------------------------------

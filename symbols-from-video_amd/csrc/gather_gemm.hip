@@ -55,25 +55,12 @@ struct GgArgs {
     const unsigned long long* seed_dev;   // optional device step counter mixed into seed
     float* colsum_ws;          // optional [nclass * m-tiles][Nout]: per-tile column sums of the stored values
     int nclass;
-    int dephase;               // 8-wave kernels: the two waves of a SIMD stage at different points of the step
-    int xcd_order;             // 1: the N tiles and tap classes of one M tile run back to back on ONE XCD (see the kernel)
     int sh_thw, sh_tw;         // log2(TH*TW), log2(TW) when those are powers of two, else -1 (row index -> (n, a, b) by shifts)
     unsigned long long* stamps; // debug (rbvae_dbg_gg_stamps): [workgroup][8] phase time stamps (100 MHz), or null
     TapClass cls[4];
 };
 
 constexpr int GG_BM = 128;
-
-// build-time experiment switches (tools/ab_variants.sh builds one library per setting for same-box A/B runs).
-// Measured on the bench step, same GPU, 3 runs each: both cut the workgroup's setup / store phases by 0.3-0.9 us
-// in the phase stamps yet left the step 0.5-1 % SLOWER (more live registers around the K loop), so both are off.
-#ifndef GG_BIAS_LDS
-#define GG_BIAS_LDS 0      // 1: stage the tile's bias in LDS during the table setup
-#endif
-#ifndef GG_PREFETCH
-#define GG_PREFETCH 0      // 1: fetch the store phase's gate / residual chunks before the register phase;
-                           // 2: the gate chunks after it (accumulators dead): 0.4648 vs 0.4666 ms/step, same GPU, 3 runs: noise
-#endif
 
 // tile row m -> (image n, grid row a, grid column b); integer divisions only when the grid is not a power of two
 // (the setup phases of a workgroup were ~2 us of mostly these divisions, against a 1.6 us single-slice K loop)
@@ -121,7 +108,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     constexpr int EC = 16 / ES;                  // elements per 16-B chunk
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
     constexpr int STAGE = A_BYTES + B_BYTES;
-    constexpr int PITCH = BN * ES + 16;          // epilogue tile row pitch
+    using SR = StoreRoles<T, BN, THREADS, BM>;     // the store phase: tile row pitch, chunks per row, row lanes, passes
+    constexpr int PITCH = SR::PITCH;
     // wave grid WR x WC over the 128 x BN tile; a wave owns MT x NTW MFMA tiles (16 x 16 each)
     constexpr int WR = 2, WC = WAVES / 2;
     constexpr int MT = (BM / 16) / WR, NTW = (2 * NT) / WC;
@@ -132,42 +120,19 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* s_orow = (int*)(smem + RING);           // [128]
     int* s_tap = s_orow + BM;                 // [16][4]: widx, dh, dw of this class
-    float* s_bias = (float*)(s_tap + 64);        // [BN]: this tile's bias (0 without one), loaded while the tables are built
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave id, provably uniform (scalar LDS addressing)
-#ifndef GG_SMALL_PRIO
-#define GG_SMALL_PRIO 0      // measured 0.516 (off) vs 0.522 ms/step (on), same GPU: off
-#endif
-#if GG_SMALL_PRIO
-    // a launch of a few dozen workgroups is a latency-bound link of the main chain (the fc products); beside a
-    // full-grid kernel of the side stream its waves take the issue slots first
-    if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(2);
-#endif
     GG_STAMP(0);
-    // Tile of this workgroup.  xcd_order (RBVAE_GG_XCD=1, off): the gridDim.y * gridDim.z workgroups that read the SAME
-    // gathered rows (the N tiles and tap classes of one M tile) take consecutive ids of one XCD.  Measured on the bench
-    // step, same GPU, 4 runs each: 0.452 ms (off) vs 0.462 ms (on), and FETCH_SIZE of the parity-class launches
-    // unchanged (40.5 vs 39.8 MB: their reads are the input once per launch plus the 33.5 MB ReLU gate of the
-    // backward one, not re-fetches) -- the plain order spreads the 1/2/2/4-tap classes over the CUs more evenly.
-    unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (p.xcd_order) {
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned nsub = gridDim.y * gridDim.z, r = lin >> 3;
-        const unsigned g = r / nsub, sub = r - g * nsub;
-        bx = g * 8 + (lin & 7);
-        by = sub % gridDim.y;
-        bz = sub / gridDim.y;
-    }
+    // Tile of this workgroup.  (Giving the gridDim.y * gridDim.z workgroups that read the SAME gathered rows consecutive ids of
+    // one XCD measured slower, DESIGN.md section 5: the plain order spreads the 1/2/2/4-tap classes over the CUs more evenly.)
+    const unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     const TapClass& tc = p.cls[bz];
     const int Mc = p.Nimg * p.TH * p.TW;
     const int m0 = bx * BM, n0 = by * BN;
     const int ntaps = tc.ntaps;
 
     // output row of every tile row (for the store phase) and the class's tap table
-#if GG_BIAS_LDS
-    for (int i = tid; i < BN; i += THREADS) s_bias[i] = (p.bias && n0 + i < p.Nout) ? p.bias[n0 + i] : 0.f;
-#endif
     if (tid < BM) {
         const int m = m0 + tid;
         int o = -1;
@@ -196,7 +161,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     for (int i = 0; i < A_INSTR; ++i) {
         const int r = (w * A_INSTR + i) * 8 + srow;
         const int m = m0 + r;
-        a_sw[i] = (unsigned)((schunk ^ ((r >> 1) & 7)) * 16);
+        a_sw[i] = (unsigned)((schunk ^ ((r >> 1) & 7)) * 16);      // (inline: mirrors mma.h swz16, as bptr below: the helper changes six instances)
         if (m < Mc) {
             split_row(p, m, an[i], aa[i], ab[i]);
         } else {
@@ -262,7 +227,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     int offA[2], offB[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int ch = ((4 * kk + fg) ^ fsw) * 16;
+        const int ch = frag_ch(kk, fg, fsw);
         offA[kk] = (wr * MT * 16 + fi) * 128 + ch;
         offB[kk] = A_BYTES + (wc * NTW * 16 + fi) * 128 + ch;
     }
@@ -279,8 +244,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     // s_waitcnt lgkmcnt(0) in front of every MFMA group -- it waited for the reads of the NEXT half it had
     // just issued, so the LDS and the matrix pipe took turns (measured 1130 cycles per slice against 512 of
     // MFMA).  The asm reads are invisible to its wait-count pass; each group is guarded by a "+v"-tied
-    // s_waitcnt, and tools/check_tr_asm.py proves on the ISA that nothing touches a fragment register
-    // between a read and its wait.
+    // s_waitcnt (mma.h: frag_landed<YOUNGER>, at most YOUNGER LDS reads still outstanding), and tools/check_tr_asm.py
+    // proves on the ISA that nothing touches a fragment register between a read and its wait.
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     constexpr int RPH = MT + NTW;                 // LDS reads of one half
     static_assert(RPH <= 15, "lgkmcnt is a 4-bit counter");
@@ -293,45 +258,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
         for (int nt = 0; nt < NTW; ++nt)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[nt]) : "v"(ab_), "n"(nt * 2048));
     };
-    // wait until at most YOUNGER LDS reads are outstanding (in-order return): the guarded fragments landed
-    auto landed = [&](auto younger_tag, u32x4_t (&fa)[MT], u32x4_t (&fb)[NTW]) {
-        constexpr int YOUNGER = decltype(younger_tag)::value;
-        static_assert((MT == 4 && (NTW == 1 || NTW == 2 || NTW == 4)) || (MT == 2 && (NTW == 1 || NTW == 2)) || (MT == 8 && NTW == 2), "operand list below");
-        if constexpr (MT == 8)
-            asm volatile("s_waitcnt lgkmcnt(%10)"
-                         : "+v"(fa[0]), "+v"(fa[1 % MT]), "+v"(fa[2 % MT]), "+v"(fa[3 % MT]), "+v"(fa[4 % MT]), "+v"(fa[5 % MT]),
-                           "+v"(fa[6 % MT]), "+v"(fa[7 % MT]), "+v"(fb[0]), "+v"(fb[1 % NTW])
-                         : "n"(YOUNGER));
-        else if constexpr (MT == 2 && NTW == 1)
-            asm volatile("s_waitcnt lgkmcnt(%3)"
-                         : "+v"(fa[0]), "+v"(fa[MT - 1]), "+v"(fb[0])
-                         : "n"(YOUNGER));
-        else if constexpr (MT == 2)
-            asm volatile("s_waitcnt lgkmcnt(%4)"
-                         : "+v"(fa[0]), "+v"(fa[MT - 1]), "+v"(fb[0]), "+v"(fb[NTW - 1])
-                         : "n"(YOUNGER));
-        else if constexpr (NTW == 1)
-            asm volatile("s_waitcnt lgkmcnt(%5)"
-                         : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2 % MT]), "+v"(fa[3 % MT]), "+v"(fb[0])
-                         : "n"(YOUNGER));
-        else if constexpr (NTW == 2)
-            asm volatile("s_waitcnt lgkmcnt(%6)"
-                         : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2 % MT]), "+v"(fa[3 % MT]), "+v"(fb[0]), "+v"(fb[1 % NTW])
-                         : "n"(YOUNGER));
-        else
-            asm volatile("s_waitcnt lgkmcnt(%8)"
-                         : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2 % MT]), "+v"(fa[3 % MT]), "+v"(fb[0]), "+v"(fb[1 % NTW]),
-                           "+v"(fb[2 % NTW]), "+v"(fb[NTW - 1])
-                         : "n"(YOUNGER));
-    };
-    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
-    };
-    using Younger = std::integral_constant<int, RPH>;
-    using None = std::integral_constant<int, 0>;
+    // (a lambda: called directly, mma_group changes eight instances, <., 1, 4, 3> and <., 4, 8, 2|3|4>)
+    auto mma_half = [&](const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NTW]) { mma_group<T>(acc, fa, fb); };
     u32x4_t fa0[MT], fb0[NTW], fa1[MT], fb1[NTW];
     GG_STAMP(2);
     if constexpr (GG_NS == 1) {
@@ -341,11 +269,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
             wait_vm_lgkm_barrier<0>();
             // one fragment set, reused by both halves (registers, see the launch bounds)
             read_half(lds0, 0, fa0, fb0);
-            landed(None{}, fa0, fb0);
+            frag_landed<0>(fa0, fb0);
             mma_half(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
             read_half(lds0, 1, fa0, fb0);
-            landed(None{}, fa0, fb0);
+            frag_landed<0>(fa0, fb0);
             mma_half(fa0, fb0);
         }
     } else {
@@ -363,17 +291,17 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
         // Waves w and w+4 share a SIMD and leave every barrier together.  Issuing an LDS-DMA piece holds a
         // wave for ~60-180 cycles, so the two take turns: the low wave stages the next slice right after the
         // barrier while its partner multiplies, the high wave stages after that MFMA group.
-        const bool late = WAVES == 8 && w >= 4 && p.dephase;
+        const bool late = WAVES == 8 && w >= 4;
         // every step but the last: multiply slice s while slice s+1's first half is read behind it
         for (int s = 0; s + 1 < nsteps; ++s) {
             const unsigned lcur = lds0 + cbuf * STAGE;
             cbuf = (cbuf + 1 == GG_NS) ? 0 : cbuf + 1;
             read_half(lcur, 1, fa1, fb1);
-            landed(Younger{}, fa0, fb0);                 // half 0 landed, half 1 in flight
+            frag_landed<RPH>(fa0, fb0);                 // half 0 landed, half 1 in flight
             __builtin_amdgcn_sched_barrier(0);
             mma_half(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            landed(None{}, fa1, fb1);                    // issued a whole MFMA group ago (one wait site per set)
+            frag_landed<0>(fa1, fb1);                    // issued a whole MFMA group ago (one wait site per set)
             // slice s+1 landed (GG_NS-2 younger ones may stay in flight); after the barrier every wave
             // holds both halves of slice s in registers, so its buffer can be refilled
             if (GG_NS > 2 && nsteps - s - 2 >= GG_NS - 2) wait_vm_lgkm_barrier<(GG_NS > 2 ? GG_NS - 2 : 0) * LOADS>();
@@ -390,11 +318,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
         {
             const unsigned lcur = lds0 + cbuf * STAGE;
             read_half(lcur, 1, fa1, fb1);
-            landed(Younger{}, fa0, fb0);
+            frag_landed<RPH>(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
             mma_half(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            landed(None{}, fa1, fb1);
+            frag_landed<0>(fa1, fb1);
             __builtin_amdgcn_sched_barrier(0);
             mma_half(fa1, fb1);
         }
@@ -402,26 +330,15 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
     GG_STAMP(3);
     __syncthreads();
 
-    // ---- store roles, and the global operands of the store phase (saved-activation gate, residual) fetched now,
-    // so their latency runs under the register phase and the LDS round trip instead of once per store pass
-    constexpr int CPR = BN / EC;                 // 16-B chunks per tile row
-    constexpr int RL = THREADS / CPR;            // row lanes of the store phase
-    constexpr int ITERS = BM / RL;            // store passes: pass `it` handles tile row it * RL + rl
-    constexpr bool PREFETCH = GG_PREFETCH && ITERS <= 8;
-    constexpr bool PF_LATE = GG_PREFETCH == 2;   // gate chunks fetched after the register phase (accumulators dead)
+    // ---- store roles
+    constexpr int CPR = SR::CPR, RL = SR::RL, ITERS = SR::ITERS;       // pass `it` handles tile row it * RL + rl
     const int sch = tid % CPR, rl = tid / CPR;
     const int scol = n0 + sch * EC;
     int orow_[ITERS];
-    u32x4_t gv[PREFETCH ? ITERS : 1], av[PREFETCH ? ITERS : 1];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int o = s_orow[it * RL + rl];
         orow_[it] = scol < p.Nout ? o : -1;
-        if constexpr (PREFETCH && !PF_LATE) {
-            const size_t off = ((size_t)(orow_[it] < 0 ? 0 : orow_[it]) * p.ldo + (orow_[it] < 0 ? 0 : scol)) * ES;
-            if (p.gate) gv[it] = *(const u32x4_t*)(p.gate + off);
-            if (p.addend) av[it] = *(const u32x4_t*)(p.addend + off);
-        }
     }
 
     // ---- epilogue, register phase: bias, relu, scale; lane owns pixel fi, channels 4*fg..+3
@@ -429,17 +346,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
         const int cb = (wc * NTW + nt) * 16 + 4 * fg;        // tile-local channel
-#if GG_BIAS_LDS
-        const float4 b4 = *(const float4*)(s_bias + cb);
-        const float bz[4] = {b4.x, b4.y, b4.z, b4.w};
-#else
         float bz[4] = {0.f, 0.f, 0.f, 0.f};
         if (p.bias && n0 + cb < p.Nout) {
             const float4 b4 = *(const float4*)(p.bias + n0 + cb);
             bz[0] = b4.x; bz[1] = b4.y; bz[2] = b4.z; bz[3] = b4.w;
         }
-        (void)s_bias;
-#endif
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int row = (wr * MT + mt) * 16 + fi;
@@ -447,17 +358,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = epi_act(acc[mt][nt][r], bz[r], p.relu, p.scale);
             epi_stage<T>(tile + row * PITCH + cb * ES, v[0], v[1], v[2], v[3]);
-        }
-    }
-    if constexpr (PREFETCH && PF_LATE) {
-        // all store passes' gate chunks in flight at once, while the tile makes its LDS round trip: fetched at their use
-        // each pass waits for its own load AND (vmcnt counts stores too) for the previous pass's stores
-        if (p.gate) {
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it) {
-                const size_t off = ((size_t)(orow_[it] < 0 ? 0 : orow_[it]) * p.ldo + (orow_[it] < 0 ? 0 : scol)) * ES;
-                gv[it] = *(const u32x4_t*)(p.gate + off);
-            }
         }
     }
     __syncthreads();
@@ -491,17 +391,13 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
                     if (!mk[e]) ev[e] = 0;
             }
             if (p.addend) {
-                u32x4_t a4;
-                if constexpr (PREFETCH && !PF_LATE) a4 = av[it];
-                else a4 = *(const u32x4_t*)(p.addend + ((size_t)orow * p.ldo + col) * ES);
+                const u32x4_t a4 = *(const u32x4_t*)(p.addend + ((size_t)orow * p.ldo + col) * ES);
                 const T* ae = (const T*)&a4;
 #pragma unroll
                 for (int e = 0; e < EC; ++e) Elem<T>::store(ev + e, Elem<T>::load(ev + e) + Elem<T>::load(ae + e));
             }
             if (p.gate) {
-                u32x4_t g4;
-                if constexpr (PREFETCH) g4 = gv[it];
-                else g4 = *(const u32x4_t*)(p.gate + ((size_t)orow * p.ldo + col) * ES);
+                const u32x4_t g4 = *(const u32x4_t*)(p.gate + ((size_t)orow * p.ldo + col) * ES);
 #pragma unroll
                 for (int e = 0; e < EC; ++e)
                     if (!elem_pos<T>((const unsigned char*)&g4, e)) ev[e] = 0;
@@ -540,17 +436,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void gather_gemm_k(const GgArgs p)
 template <typename T, int NT, int WAVES, int NS, int OCC = 1, int BM = GG_BM>
 static int launch_gg(const GgArgs& a, hipStream_t st) {
     constexpr int BN = NT * 32;
-    constexpr int ES = sizeof(T);
     const int Mc = a.Nimg * a.TH * a.TW;
     const size_t ring = (size_t)NS * (BM * 128 + BN * 128);
-    const size_t tile = (size_t)BM * (BN * ES + 16);
-    const size_t lds = (ring > tile ? ring : tile) + BM * sizeof(int) + 64 * sizeof(int) + BN * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)gather_gemm_k<T, NT, WAVES, NS, OCC, BM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-        attr_set = true;
-    }
+    const size_t tile = (size_t)BM * StoreRoles<T, BN, WAVES * 64, BM>::PITCH;
+    const size_t lds = (ring > tile ? ring : tile) + BM * sizeof(int) + 64 * sizeof(int);
+    lds_attr_once<gather_gemm_k<T, NT, WAVES, NS, OCC, BM>>((int)lds);
     dim3 grid(cdiv(Mc, BM), cdiv(a.Nout, BN), a.nclass);
     hipLaunchKernelGGL((gather_gemm_k<T, NT, WAVES, NS, OCC, BM>), grid, dim3(WAVES * 64), lds, st, a);
     RBVAE_CHECK_LAUNCH("gather_gemm");
@@ -559,47 +449,37 @@ static int launch_gg(const GgArgs& a, hipStream_t st) {
 
 // The 64-row tile (one 4-wave workgroup per CU, 16 KB per K slice): ring depth and waves.  With three stages at most 32 KB
 // per CU is in flight, short of what keeps a CU's intake from L2 busy; GG_RING64 stages keep (GG_RING64 - 1) * 16 KB in
-// flight.  Build-time switches for same-GPU A/B runs (tools/ab_variants.sh); the measurements are in DESIGN.md section 5.
-#ifndef GG_RING64
-#define GG_RING64 6
-#endif
-#ifndef GG_WAVES64
-#define GG_WAVES64 4       // 8: two waves per SIMD, half the LDS-DMA pieces per wave
-#endif
+// flight.  Depths 3 .. 8 and the 8-wave form were measured: DESIGN.md section 5.
+constexpr int GG_RING64 = 6;
+constexpr int GG_WAVES64 = 4;
 
 template <typename T>
 static int dispatch_gg(const GgArgs& a, hipStream_t st, int max_steps) {
     const long blocks = (long)cdiv(a.Nimg * a.TH * a.TW, GG_BM) * cdiv(a.Nout, a.Nout > 64 ? 128 : 64) * a.nclass;
-    constexpr int force = 0;
-    constexpr int dbg = 0;
     int ns = max_steps <= 2 ? 1 : (blocks > 256 ? 2 : 3);
-    if (force) ns = force;
     // one workgroup per CU and a deep K (the 256-channel convolutions at 256 frames): a ring of FOUR, three slices in flight --
     // a K step of the 128 x 128 tile is ~0.27 us, two of them are less lead than an L2 miss takes (bench step -0.6 %, same box)
     if (ns == 3 && blocks > 128 && max_steps >= 8) ns = 4;
     // a deep-K product with few rows and <= 64 columns (the LDM encoder's conv_out: 16 384 rows, K = 4608, 8 columns): 64-row
-    // tiles put a workgroup on every CU instead of on half of them (55 -> 30 us)
-    if (a.Nout <= 64 && blocks <= 128 && max_steps >= 16 && sizeof(T) == 2 && !a.colsum_ws && !a.xcd_order)
-        return launch_gg<T, 2, GG_WAVES64, GG_RING64, 1, 64>(a, st);
+    // tiles put a workgroup on every CU instead of on half of them (55 -> 30 us).  The 64-row tile is built for bf16 only.
+    if constexpr (sizeof(T) == 2) {
+        if (a.Nout <= 64 && blocks <= 128 && max_steps >= 16 && !a.colsum_ws)
+            return launch_gg<T, 2, GG_WAVES64, GG_RING64, 1, 64>(a, st);
+    }
     if (a.Nout <= 64) return ns == 1 ? launch_gg<T, 2, 4, 1>(a, st) : launch_gg<T, 2, 4, 2>(a, st);
     // deep-K problems with too few 128x128 tiles for the 256 CUs: narrower tiles (more workgroups, shorter steps)
-    constexpr int small = 2;
-    if (ns == 3 && !force && !dbg && small) {
+    if (ns == 3) {
         // 64 x 64 tiles for the 64-block problems (conv3 forward, first deconv's input gradient at 256 frames): the same
         // 256 workgroups as 128 x 32 tiles at 16 KB instead of 20 KB of operands per K step.  The fused column sums keep
-        // the 128-row tiles (their partial-sum rows are counted in 128-row tiles by the callers); xcd_order too.
-        constexpr int sq = 1;
-        if (sq && small >= 2 && blocks <= 64 && !a.colsum_ws && !a.xcd_order && sizeof(T) == 2)
-            return launch_gg<T, 2, GG_WAVES64, GG_RING64, 1, 64>(a, st);
-        if (small >= 2 && blocks <= 64) return launch_gg<T, 1, 4, 3>(a, st);
+        // the 128-row tiles (their partial-sum rows are counted in 128-row tiles by the callers).
+        if constexpr (sizeof(T) == 2) {
+            if (blocks <= 64 && !a.colsum_ws) return launch_gg<T, 2, GG_WAVES64, GG_RING64, 1, 64>(a, st);
+        }
+        if (blocks <= 64) return launch_gg<T, 1, 4, 3>(a, st);
         if (blocks <= 128) return launch_gg<T, 2, 4, 3>(a, st);
     }
-    constexpr int one = 1;
-    if (ns == 1 && one >= 1 && blocks > 512) return launch_gg<T, 2, 4, 1, 4>(a, st);
-    // few 128-wide tiles (the fc products at 256 frames: 64): 128 x 32 tiles put a workgroup on every CU
-    if (ns == 1 && one >= 2 && blocks <= 64) return launch_gg<T, 1, 4, 1>(a, st);
+    if (ns == 1 && blocks > 512) return launch_gg<T, 2, 4, 1, 4>(a, st);
     if (ns == 1) return launch_gg<T, 4, 4, 1>(a, st);
-    if (ns >= 2 && (dbg == 5 || dbg == 6)) return dbg == 5 ? launch_gg<T, 2, 4, 3>(a, st) : launch_gg<T, 2, 4, 2>(a, st);
     // (128 x 256 tiles -- <8, 8, 2>, the gathered rows read once instead of twice -- measured 37.2 us against 34.6 us for
     // the 1024-workgroup parity-class launches: one 8-wave workgroup per CU and two uneven rounds cost more than the
     // 25 % smaller ingest gains)
@@ -607,7 +487,6 @@ static int dispatch_gg(const GgArgs& a, hipStream_t st, int max_steps) {
     // rounds: native 4x88x160 step 2.26-2.28 ms against 2.22, same GPU, alternating: two 128-row workgroups per CU hide each
     // other's barriers and epilogues better than the 25 % smaller ingest of the tall tile gains)
     if (ns == 2) return launch_gg<T, 4, 8, 2>(a, st);
-    if (dbg == 4) return launch_gg<T, 4, 4, 3>(a, st);       // 4 waves, 64x64 wave tiles (less LDS traffic)
     if (ns >= 4) return launch_gg<T, 4, 8, 4>(a, st);
     return launch_gg<T, 4, 8, 3>(a, st);
 }
@@ -639,14 +518,13 @@ extern "C" int rbvae_gather_gemm(int dtype, const void* A, const void* W, void* 
     const int KE = 128 / ES;
     RBVAE_CHECK_ARG(Kc > 0 && Kc % KE == 0, "gather_gemm: Kc=%d must be a multiple of %d", Kc, KE);
     RBVAE_CHECK_ARG(Nout > 0 && Nout % 8 == 0, "gather_gemm: Nout=%d must be a multiple of 8", Nout);
-    RBVAE_CHECK_ARG(lda >= Kc && (lda * ES) % 16 == 0 && ldo >= Nout && (ldo * ES) % 16 == 0,
-                    "gather_gemm: leading dimensions lda=%d ldo=%d", lda, ldo);
+    if (const int e = epi_check_pitch("gather_gemm", ES, Kc, Nout, lda, ldo)) return e;
     RBVAE_CHECK_ARG(nclass >= 1 && nclass <= 4, "gather_gemm: nclass=%d", nclass);
     RBVAE_CHECK_ARG(Nimg > 0 && IH > 0 && IW > 0 && TH > 0 && TW > 0 && OH > 0 && OW > 0, "gather_gemm: bad grid");
     RBVAE_CHECK_ARG((long)Nimg * TH * TW < (1l << 30) && (long)Nimg * OH * OW < (1l << 30) &&
                         (long)Nimg * IH * IW < (1l << 30), "gather_gemm: more than 2^30 pixel rows");
-    RBVAE_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)gate) % 16 == 0,
-                    "gather_gemm: pointers must be 16-byte aligned");
+    if (const int e = epi_check_align("gather_gemm", (uintptr_t)A | (uintptr_t)W | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)gate))
+        return e;
     GgArgs a;
     if (const int e = epi_drop_args("gather_gemm", drop_mode, mask, drop_p, &a.drop_thresh)) return e;
     a.A = (const unsigned char*)A; a.W = (const unsigned char*)W; a.Out = (unsigned char*)Out; a.bias = bias;
@@ -656,10 +534,6 @@ extern "C" int rbvae_gather_gemm(int dtype, const void* A, const void* W, void* 
     a.Kc = Kc; a.Nout = Nout; a.lda = lda; a.ldo = ldo; a.taps_total = taps_total;
     a.relu = relu; a.drop_mode = drop_mode; a.scale = scale; a.seed = seed; a.seed_dev = seed_dev; a.colsum_ws = colsum_ws;
     a.nclass = nclass;
-    constexpr int dephase = 1;
-    a.dephase = dephase;
-    constexpr int xcd = 0;
-    a.xcd_order = xcd && cdiv(Nimg * TH * TW, GG_BM) % 8 == 0 && (nclass > 1 || cdiv(Nout, Nout > 64 ? 128 : 64) > 1);
     a.stamps = g_gg_stamps;
     auto log2_or_neg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
     a.sh_thw = log2_or_neg(TH * TW);

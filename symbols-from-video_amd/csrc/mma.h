@@ -1,6 +1,7 @@
 // Shared device helpers of the matrix-core kernels (gfx950 only): vector types, the LDS-DMA wrapper, the LDS-only and
-// counted-vmcnt barriers, DPP row sums, static_for, the MFMA dispatch, the transposing-read swizzle, lane offset and fragment
-// pack, the ReLU-gate test and the frame map.  Everything is __forceinline__: a kernel that takes a helper from here compiles to the code it had
+// counted-vmcnt barriers, DPP row sums, static_for, the MFMA dispatch, the tied wait and MFMA group of a 32-k half, the
+// 128-byte-row swizzle, the store-phase roles, the transposing-read swizzle, lane offset and fragment pack, the ReLU-gate test
+// and the frame map.  Everything is __forceinline__: a kernel that takes a helper from here compiles to the code it had
 // with a private copy (tools/isa_diff.py proves it).  New kernels take these; they do not copy them.
 #pragma once
 #include "common.h"
@@ -81,6 +82,58 @@ template <> struct Mma<float> {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(r[q], c[q], acc, 0, 0, 0);
     }
+};
+
+// One 32-k half of a K step in registers: MT + NT fragments read by inline-asm ds_read_b128, which the compiler's wait-count
+// pass does not see.  frag_landed<YOUNGER>(fa, fb) is the counted wait that guards them: at most YOUNGER LDS operations issued
+// after them are still outstanding (in-order return), and the "+v" ties keep every use of a fragment behind the wait
+// (tools/check_tr_asm.py and the build's ISA check prove that nothing touches one between its read and its wait).  One operand
+// list per pair of array extents in use: a new tile shape adds its overload here.
+template <int YOUNGER> __device__ __forceinline__ void frag_landed(u32x4_t (&fa)[2], u32x4_t (&fb)[2]) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1]) : "n"(YOUNGER));
+}
+template <int YOUNGER> __device__ __forceinline__ void frag_landed(u32x4_t (&fa)[2], u32x4_t (&fb)[4]) {
+    asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]) : "n"(YOUNGER));
+}
+template <int YOUNGER> __device__ __forceinline__ void frag_landed(u32x4_t (&fa)[4], u32x4_t (&fb)[1]) {
+    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]) : "n"(YOUNGER));
+}
+template <int YOUNGER> __device__ __forceinline__ void frag_landed(u32x4_t (&fa)[4], u32x4_t (&fb)[2]) {
+    asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]) : "n"(YOUNGER));
+}
+template <int YOUNGER> __device__ __forceinline__ void frag_landed(u32x4_t (&fa)[4], u32x4_t (&fb)[4]) {
+    asm volatile("s_waitcnt lgkmcnt(%8)"
+                 : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3])
+                 : "n"(YOUNGER));
+}
+// the MFMAs of rows M0 .. M1 - 1 of a wave's MT x NT block of 16 x 16 tiles (weights fb as the row operand: a lane owns 4
+// consecutive output channels of one pixel); mma_group: the whole block
+template <typename T, int M0, int M1, int MT, int NT>
+__device__ __forceinline__ void mma_rows(f32x4_t (&acc)[MT][NT], const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NT]) {
+#pragma unroll
+    for (int mt = M0; mt < M1; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) Mma<T>::run(acc[mt][nt], fb[nt], fa[mt]);
+}
+template <typename T, int MT, int NT>
+__device__ __forceinline__ void mma_group(f32x4_t (&acc)[MT][NT], const u32x4_t (&fa)[MT], const u32x4_t (&fb)[NT]) {
+    mma_rows<T, 0, MT>(acc, fa, fb);
+}
+
+// byte offset of 16-byte chunk c in row r of an LDS image of 128-byte rows: the chunk index XORed with (r >> 1) & 7, on the
+// source address of the LDS-DMA that fills the image and again on the ds_read_b128 fragment read (conflict-free)
+__device__ __forceinline__ int swz16(int r, int c) { return (c ^ ((r >> 1) & 7)) * 16; }
+// ... of a lane's fragment chunk in 32-k half kk: chunk 4 kk + fg of row fi, with fsw = (fi >> 1) & 7 formed by the caller
+// (formed inside, the kernels' listings change)
+__device__ __forceinline__ int frag_ch(int kk, int fg, int fsw) { return ((4 * kk + fg) ^ fsw) * 16; }
+
+// the roles of a GEMM's store phase: the BM x BN tile of T goes through LDS (row pitch PITCH) and leaves as 16-byte chunks,
+// CPR per row; thread tid takes chunk tid % CPR of rows it * RL + tid / CPR, it < ITERS
+template <typename T, int BN, int THREADS, int BM> struct StoreRoles {
+    static constexpr int PITCH = BN * (int)sizeof(T) + 16;
+    static constexpr int CPR = BN / (16 / (int)sizeof(T));
+    static constexpr int RL = THREADS / CPR;
+    static constexpr int ITERS = BM / RL;
 };
 
 // XOR applied to the 16-B chunk index of an LDS image row (RB bytes per row) so that the transposed

@@ -177,14 +177,14 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
             constexpr int nj = (j + 1) % UC_TAPS;            // tap of the next step
             using NJ = std::integral_constant<int, nj>;
             read_half(j_tag, K1{}, fa1, fb1);
-            ch_landed<MT + NTW>(fa0, fb0);
+            frag_landed<MT + NTW>(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            ch_mma_half<T>(acc, fa0, fb0);
+            mma_group<T>(acc, fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            ch_landed<0>(fa1, fb1);
+            frag_landed<0>(fa1, fb1);
             if constexpr (j == UC_TAPS - 1 && !more) {       // the very last step reads nothing ahead
                 __builtin_amdgcn_sched_barrier(0);
-                ch_mma_half<T>(acc, fa1, fb1);
+                mma_group<T>(acc, fa1, fb1);
             } else {
                 if constexpr (more) {
                     if constexpr (j == 3) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(512) void upconv_halo_k(const UcArgs p) {
                 if constexpr (nj == 0) set_slice(kc + 1);
                 read_half(NJ{}, K0{}, fa0, fb0);
                 __builtin_amdgcn_sched_barrier(0);
-                ch_mma_half<T>(acc, fa1, fb1);
+                mma_group<T>(acc, fa1, fb1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
@@ -391,7 +391,7 @@ extern "C" int rbvae_upconv3x3_halo(int dtype, const void* A, const void* Wf, vo
                     IH, IW, Kc, Nout);
     RBVAE_CHECK_ARG(A && Wf && Out && zero_page, "upconv3x3_halo: null pointer");
     const int ES = dtype == RBVAE_F32 ? 4 : 2;
-    if (const int e = ch_check_rows("upconv3x3_halo", ES, Kc, Nout, lda, ldo,
+    if (const int e = epi_check_rows("upconv3x3_halo", ES, Kc, Nout, lda, ldo,
                                     (uintptr_t)A | (uintptr_t)Wf | (uintptr_t)Out | (uintptr_t)zero_page | (uintptr_t)addend | (uintptr_t)bias))
         return e;
     UcArgs a;

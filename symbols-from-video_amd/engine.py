@@ -421,6 +421,15 @@ class Engine:
         """bias_grad: f32 [nout] tensor that receives the column sums of the stored output (a reduce job
         over the kernel's per-tile partial sums, run with the other jobs at the end of backward)."""
         seed_dev = self.seed_dev
+
+        def colsum_rows(name, rows, nout):
+            """The kernel's partial-sum workspace [rows][nout] and the job that reduces it into bias_grad (None without one)."""
+            if bias_grad is None:
+                return None
+            ws = self._buf((name, tag), rows * nout)
+            self._jobs.add(JOB_ROWS, ws, bias_grad, (1, 1, nout), (0, 0, 1), nslab=rows, slab=nout)
+            return ws
+
         if (self.fc_gemm and cls_key == "one" and gate is None and mask is None and drop_mode == 0 and not relu
                 and scale == 1.0 and bias_grad is None and nimg <= 4096 and nout >= 1024
                 and ih * iw * th * tw * oh * ow == 1 and L.query("rbvae_fc_gemm_ok", self.dt, nimg, kc, nout, lda, ldo)):
@@ -438,10 +447,7 @@ class Engine:
             rows4 = L.query("rbvae_deconv3x3s2_halo_colsum_rows", self.dt, nimg, th, tw, kc, nout)
             wgs = (rows4 // 4) * (nout // 64)
             if wgs >= self._dh_min_wgs:
-                ws = None
-                if bias_grad is not None:
-                    ws = self._buf(("colsum_dh", tag), rows4 * nout)
-                    self._jobs.add(JOB_ROWS, ws, bias_grad, (1, 1, nout), (0, 0, 1), nslab=rows4, slab=nout)
+                ws = colsum_rows("colsum_dh", rows4, nout)
                 L.call("rbvae_deconv3x3s2_halo", self.dt, A, W, out, bias, gate, mask, self.zero, nimg, th, tw, kc, nout, lda,
                        ldo, relu, drop_mode, float(drop_p), float(scale), int(seed), seed_dev, ws)
                 return
@@ -454,10 +460,7 @@ class Engine:
             if bn:
                 mt = L.query("rbvae_conv3x3s2_halo_colsum_rows", nimg, ih, iw)
                 if mt * (nout // bn) >= self._cs_min_wgs and mt * 128 <= self._cs_max_waste * nimg * oh * ow:
-                    ws = None
-                    if bias_grad is not None:
-                        ws = self._buf(("colsum_cs", tag), mt * nout)
-                        self._jobs.add(JOB_ROWS, ws, bias_grad, (1, 1, nout), (0, 0, 1), nslab=mt, slab=nout)
+                    ws = colsum_rows("colsum_cs", mt, nout)
                     L.call("rbvae_conv3x3s2_halo", self.dt, A, W, out, bias, gate, mask, nimg, ih, iw, kc, nout, lda, ldo, relu,
                            drop_mode, float(drop_p), float(scale), int(seed), seed_dev, ws)
                     return
@@ -468,11 +471,7 @@ class Engine:
         else:
             desc, ncls = self._desc("dgrad", self._cls_dgrad), self._ncls_dgrad
         import ctypes
-        ws = colsum_ws
-        if bias_grad is not None:
-            prow = ncls * (-(-(nimg * th * tw) // 128))
-            ws = self._buf(("colsum", tag), prow * nout)
-            self._jobs.add(JOB_ROWS, ws, bias_grad, (1, 1, nout), (0, 0, 1), nslab=prow, slab=nout)
+        ws = colsum_rows("colsum", ncls * (-(-(nimg * th * tw) // 128)), nout) if bias_grad is not None else colsum_ws
         L.call("rbvae_gather_gemm", self.dt, A, W, out, bias, gate, mask, None, self.zero, nimg, ih, iw, th, tw, sa, oh, ow,
                so, kc, nout, lda, ldo, taps, ncls, ctypes.addressof(desc), relu, drop_mode, float(drop_p),
                float(scale), int(seed), seed_dev, ws)

@@ -91,7 +91,8 @@ def gg_instance(dtype, Mc, Nout, nclass, max_steps, colsum):
     return "ns3_256", (4, 8, 3, 1, 128)
 
 
-# every (dtype, branch) the build reaches through the public ABI (the `one >= 2` branch and the force / dbg ones are dead)
+# every (dtype, branch) the build reaches through the public ABI: dispatch_gg reads branch for branch like gg_instance above
+# (the 64-row tile is instantiated for bf16 only)
 GG_REACHABLE = {("bf16", "nout64_deep")} | {(d, b) for d in ("f32", "bf16") for b in (
     "nout64_ns1", "nout64", "ns3_64", "ns3_128", "ns1_512", "ns1", "ns2", "ns4", "ns3_256")} | {("bf16", "ns3_64sq")}
 
