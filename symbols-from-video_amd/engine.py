@@ -11,8 +11,10 @@ Reference path restated by the kernels this file sequences:
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import math
-import os
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -141,11 +143,38 @@ def dgrad_classes(k: int) -> Tuple[List[int], int]:
 
 ONE_TAP = [1, 0, 0, 0, 0, 0]
 
+Names = namedtuple("Names", "weight bias")      # parameter names of a layer that has no Stride2 record (conv1, last deconv)
+# A k x k stride-2 layer as the GEMMs see it: a small grid with `cs` channels and a big grid (twice the extent) with `cb`
+# channels.  An encoder Conv2d (big -> small) and a decoder ConvTranspose2d (small -> big) are the same layer: the parameter
+# `weight` is [cs][cb][k][k] in both, the forward of one is the input gradient of the other.  f = its packed copy
+# [cs][t][cb] (big -> small launches read it), d = [cb][t][cs] (small -> big); big / small = the two grids (h, w)
+Stride2 = namedtuple("Stride2", "weight bias f d cs cb big small")
+
+
 class Saved:
     """Activations one forward call keeps for its backward."""
     __slots__ = ("N", "S", "T", "hw", "train", "tau", "tau_dev", "hard", "col1", "x_in", "fm_in", "a1", "a2", "a3", "e", "hs_enc", "hp_enc",
                  "acts_enc", "cs_enc", "y", "z", "hs_dec", "hp_dec", "acts_dec", "cs_dec", "ds_pad", "f", "d1", "d2",
                  "xr", "gate_scale", "dpre3", "b3_parts", "dd2_fused")
+
+
+class _Pass:
+    """What the stages of one forward() / backward() call share: the frame counts, the row counts of the three grids, views
+    into the flat buffers and the persistent temporaries of this frame count.  A stage hangs what later stages read on it."""
+
+    def __init__(self, eng: "Engine", sv: Saved, flat: torch.Tensor, gflat: Optional[torch.Tensor] = None):
+        self.eng, self.sv, self.flat, self.gflat = eng, sv, flat, gflat
+        self.N, self.S, self.T = sv.N, sv.S, sv.T
+        self.H, self.W = sv.hw
+        self.P1, self.P2, self.P3 = (sv.N * h * w for h, w in (eng.g1, eng.g2, eng.g3))
+        self.P = lambda name: eng.layout.view(flat, name)         # a parameter / its gradient by name
+        self.G = lambda name: eng.layout.view(gflat, name)
+
+    def tmp(self, tag, *shape, dtype=None):
+        return self.eng._buf((self.N, tag), math.prod(shape), dtype or self.eng.tdt).view(*shape)
+
+    def fm(self, ch):       # the caller's frame_map, or the dense one of frames with `ch` channels
+        return self.frame_map if self.frame_map is not None else (0, 0, 0, 0, ch * self.H * self.W)
 
 
 class Engine:
@@ -169,7 +198,7 @@ class Engine:
         self.layout = ParamLayout(self.v, in_ch, out_ch, latent, self.hw)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         k = self.v.kernel
-        self.k = k
+        self.k, self.kk = k, k * k
         H, W = self.hw
         self.g1 = (conv_out(H, k), conv_out(W, k))
         self.g2 = (conv_out(self.g1[0], k), conv_out(self.g1[1], k))
@@ -181,9 +210,10 @@ class Engine:
         self.NY = _ru(k * k * out_ch, 8)               # per-tap product width of the last deconv
         self.Lp = _ru(latent, self.ke)
         self.zero = torch.zeros(256, dtype=torch.uint8, device=self.device)
-        self._cls_conv = conv_classes(k)
-        self._cls_dgrad, self._ncls_dgrad = dgrad_classes(k)
-        self._desc_cache: Dict[Tuple, object] = {}
+        carr = lambda ints: (ctypes.c_int * len(ints))(*ints)
+        dg, ncls_dg = dgrad_classes(k)
+        # gather_gemm class descriptors by _gemm's cls_key: (C int array, number of classes)
+        self._descs = {"one": (carr(ONE_TAP), 1), "conv": (carr(conv_classes(k)), 1), "dgrad": (carr(dg), ncls_dg)}
         self._idx_cache: Dict[Tuple, torch.Tensor] = {}
         self.seed_dev = None           # optional device step counter (int64 tensor) for graph-replayed steps
         self._pack_tab: Dict = {}      # uploaded JobTables of pack() (keyed by the flat buffer) and update_jobs() (by its arguments)
@@ -191,11 +221,10 @@ class Engine:
         self._bwd_tab: Dict = {}       # uploaded reduce-job JobTables, keyed by their signature
         self._tables: Dict[int, JobTable] = {}     # every uploaded JobTable by the address of its device rows (which it holds)
         self._jobs: Optional[JobList] = None
-        self._wg_cus = 256
         self.last_wgrad_kernel = None  # kernel family the last _wgrad() call launched (bench.py's roofline leg keys its timers by it)
         self._job_blocks = 256      # workgroups per job of a batched job launch (at most)
-        self.sized_jobs = 2         # job tables launched with exactly the workgroups they can use: 0 none, 1 the update table, 2 all
-        self.table_launch = True    # sized launches through rbvae_run_jobs_table (LDS from the rows); False: rbvae_run_jobs_sized
+        # the engine's uploaded job tables are launched with exactly the workgroups they can use ...
+        self.table_launch = True    # ... through rbvae_run_jobs_table (LDS from the rows); False: rbvae_run_jobs_sized
         # ... their heaviest jobs' workgroups first (rbvae_job_launch_order): 0 none, 1 the update table, 2 all.  The reduce
         # launches keep the map's order: heaviest first gives them nothing at the bench shape and costs the native step 12 us
         # ("Update launch")
@@ -209,13 +238,11 @@ class Engine:
         # side work (graph capture hands the forking node's queue to the branch created first; created second, the main
         # chain paid a cross-queue hand-off of ~10 us at every fork).
         self.overlap = True
-        self._ks_small = 3
-        self.fc_gemm = True               # dedicated kernel for the K = 64 fc products
+        # dedicated kernel for the K = 64 fc products (bench.py's roofline leg reads this to label the fc launches)
+        self.fc_gemm = True
         # halo-resident kernel for the transposed 3x3 / stride-2 launches (csrc/deconv_halo.hip) from this many workgroups up
         self.deconv_halo = True
         self._dh_min_wgs = 1024
-        # nine-taps-per-workgroup weight gradient of the 3x3 stride-2 layers (csrc/wgrad_halo.hip) when every workgroup
-        # gets at least this many 4 x 8 pixel blocks
         # halo-resident kernel for the 3x3 stride-2 forward-type launches (csrc/conv_s2.hip) from this many workgroups up, when
         # its 8 x 16-pixel tiles cover at most this many times the image's pixels (measured, tools/time_conv_s2.py: 128 images
         # 88 x 160 -> 44 x 80, 256 channels: 662 vs 844 us for the gather GEMM; the native 44 x 80 -> 22 x 40 layer, whose 22 x 40
@@ -223,6 +250,8 @@ class Engine:
         self.conv_s2_halo = True
         self._cs_min_wgs = 512
         self._cs_max_waste = 1.15
+        # nine-taps-per-workgroup weight gradient of the 3x3 stride-2 layers (csrc/wgrad_halo.hip) when every workgroup
+        # gets at least this many 4 x 8 pixel blocks
         self.wgrad_halo = True
         self._wh_min_steps = 8
         self._wh_max_tiles = 2
@@ -241,28 +270,21 @@ class Engine:
         # (rbvae_wgrad_first, csrc/conv_first.hip) when every workgroup gets at least this many 8 x 16 pixel blocks
         self.wgrad_first = True
         self._wf_min_steps = 8
-        self.lstm_pair_bwd = True   # both stacks' BPTT in one launch
-        self.keep_dz = False                # also store the codes' gradient
         # The fc products on either side of the LSTM stacks (M = frames, 32 outputs, K = thousands) run K-split over
         # several workgroup groups, and the LSTM kernels sum the slabs while staging their input (one group: 32 CUs busy at
         # 256 frames).  Needs the wavefront LSTM kernels (latent <= 32).  16 groups for the large fc layers (at F3 = 56 320 /
         # 65 536 four groups were 64 workgroups streaming 21-42 MB: 31-36 us per launch at 0.6 TB/s), else the largest of
         # 16 / 8 / 4 that divides F3 into whole K units
         ks_unit = 32 if dtype == "bf16" else 16
-        wave_ok = latent <= 32 and self.v.lstm_layers * _ru(4 * latent, 64) <= 1024 and not self.v.simple_order
+        # ... and write the bf16 / padded copy of their output that the next GEMM reads (rbvae_cast_pad otherwise), run the
+        # binarisation inside their launch and, where a pass runs both stacks, go as one launch (each if the call's T fits)
+        self.wave_ok = latent <= 32 and self.v.lstm_layers * _ru(4 * latent, 64) <= 1024 and not self.v.simple_order
         self.fc_split = 1
-        if wave_ok and self.F3 >= 2048:
+        if self.wave_ok and self.F3 >= 2048:
             for want in ((16, 8, 4) if self.F3 >= 16384 else (4,)):
                 if self.F3 % (want * ks_unit) == 0:
                     self.fc_split = want
                     break
-        # ... and write the bf16 / padded copy of their output that the next GEMM reads (rbvae_cast_pad otherwise)
-        self.lstm_cast = wave_ok
-        # ... and, in forward passes that run both stacks, go as one launch with the binarisation between them
-        self.lstm_pair = wave_ok
-        self.bin_bwd_fused = wave_ok
-        self.deconv_fused = True
-        self.conv_first_fused = True
         # last deconv forward + loss + input gradient as one launch (csrc/deconv_last_bwd.hip) where forward() is told that
         # backward() will take dpre3 from it; off: rbvae_deconv_last_fused, then rbvae_deconv_last_dgrad_fused in backward()
         self.deconv_last_bwd_fused = True
@@ -288,6 +310,15 @@ class Engine:
         nl, Ld = self.v.lstm_layers, self.latent
         self.wT_enc = torch.zeros(nl, 2, Ld, 4 * Ld, dtype=torch.float32, device=self.device)   # [k][gate row]
         self.wT_dec = torch.zeros(nl, 2, Ld, 4 * Ld, dtype=torch.float32, device=self.device)
+        # the layer records: geometry and operands written once, read by every launch of the layer (_down, _up, _wgrad_s2)
+        i0, i1, i2 = self.layout.conv_idx
+        nm = lambda stem, i: Names(f"{stem}.{i}.weight", f"{stem}.{i}.bias")
+        self.conv1, self.deconv2 = nm("encoder_cnn.conv", i0), nm("decoder_cnn.deconv", i2)
+        self.conv2 = Stride2(*nm("encoder_cnn.conv", i1), self.W2f, self.W2d, c2, c1, self.g1, self.g2)
+        self.conv3 = Stride2(*nm("encoder_cnn.conv", i2), self.W3f, self.W3d, c3, c2, self.g2, self.g3)
+        self.deconv0 = Stride2(*nm("decoder_cnn.deconv", i0), self.V1f, self.V1d, c3, c2, self.g2, self.g3)
+        self.deconv1 = Stride2(*nm("decoder_cnn.deconv", i1), self.V2f, self.V2d, c2, c1, self.g1, self.g2)
+        self.stride2 = (self.conv2, self.conv3, self.deconv0, self.deconv1)
 
     def _upload(self, jl: JobList) -> JobTable:
         t = JobTable(jl, self.device, self._job_blocks)
@@ -301,9 +332,9 @@ class Engine:
     def run_table(self, tab: torch.Tensor, n: int, kind: int = 2):
         """One batched job launch of `tab` (n rows): sized (exactly the workgroups it can use, and through
         rbvae_run_jobs_table the LDS its rows need and the heaviest jobs first) when it is one of the engine's uploaded
-        tables and sized_jobs covers its kind (1 = the optimiser update table, 2 = the pack / reduce tables)."""
+        tables; jobs_heavy_first is asked per kind (1 = the optimiser update table, 2 = the pack / reduce tables)."""
         t = self._tables.get(tab.data_ptr())
-        if t is None or self.sized_jobs < kind:
+        if t is None:
             L.call("rbvae_run_jobs", tab, n, self._job_blocks)
         elif self.table_launch:
             t.run(self.jobs_heavy_first >= kind)
@@ -366,21 +397,16 @@ class Engine:
     def _pack_jobs(self, flat: torch.Tensor) -> JobList:
         lay, dt = self.layout, self.dt
         c1, c2, c3 = self.v.channels
-        kk = self.k * self.k
+        kk = self.kk
         g3 = self.g3[0] * self.g3[1]
-        i0, i1, i2 = lay.conv_idx
         P = lambda name: lay.view(flat, name)
         jl = JobList()
         pk = lambda src, dst, dims, strides, d=None: jl.add(JOB_PACK, src, dst, dims, strides, dtype=dt if d is None else d)
         # conv1 [c1][cin][kk] -> [c1][t*cin + ci]
-        pk(P(f"encoder_cnn.conv.{i0}.weight"), self.W1p, (c1, self.in_ch, kk), (self.K1, 1, self.in_ch))
-        for name, wf, wd, co, ci in ((f"encoder_cnn.conv.{i1}.weight", self.W2f, self.W2d, c2, c1),
-                                     (f"encoder_cnn.conv.{i2}.weight", self.W3f, self.W3d, c3, c2),
-                                     (f"decoder_cnn.deconv.{i0}.weight", self.V1f, self.V1d, c3, c2),
-                                     (f"decoder_cnn.deconv.{i1}.weight", self.V2f, self.V2d, c2, c1)):
-            w = P(name)                                               # [co][ci][kk]
-            jl.add_conv_pack(w, wf, wd, co, ci, kk, dt)               # [co][t][ci] and [ci][t][co]
-        v3 = P(f"decoder_cnn.deconv.{i2}.weight")                     # [c1][out][kk]
+        pk(P(self.conv1.weight), self.W1p, (c1, self.in_ch, kk), (self.K1, 1, self.in_ch))
+        for ly in self.stride2:                                       # [cs][cb][kk] -> [cs][t][cb] and [cb][t][cs]
+            jl.add_conv_pack(P(ly.weight), ly.f, ly.d, ly.cs, ly.cb, kk, dt)
+        v3 = P(self.deconv2.weight)                                   # [c1][out][kk]
         pk(v3, self.V3p, (c1, self.out_ch, kk), (1, c1, self.out_ch * c1))       # [(t*out+co)][c1]
         pk(v3, self.V3f, (c1, self.out_ch, kk), (self.K3, 1, self.out_ch))       # [c1][t*out+co]
         wfc = P("encoder_cnn.fc.weight")                              # [L][c3][g3]
@@ -398,14 +424,6 @@ class Engine:
         return jl
 
     # ---- helpers ---------------------------------------------------------------
-    def _desc(self, key, ints):
-        d = self._desc_cache.get(key)
-        if d is None:
-            import ctypes
-            d = (ctypes.c_int * len(ints))(*ints)
-            self._desc_cache[key] = d
-        return d
-
     def _buf(self, tag, numel, dtype=torch.float32):
         """Persistent temporary (same address every step, so uploaded job tables stay valid)."""
         key = (tag, numel, dtype)
@@ -464,13 +482,7 @@ class Engine:
                     L.call("rbvae_conv3x3s2_halo", self.dt, A, W, out, bias, gate, mask, nimg, ih, iw, kc, nout, lda, ldo, relu,
                            drop_mode, float(drop_p), float(scale), int(seed), seed_dev, ws)
                     return
-        if cls_key == "one":
-            desc, ncls = self._desc("one", ONE_TAP), 1
-        elif cls_key == "conv":
-            desc, ncls = self._desc("conv", self._cls_conv), 1
-        else:
-            desc, ncls = self._desc("dgrad", self._cls_dgrad), self._ncls_dgrad
-        import ctypes
+        desc, ncls = self._descs[cls_key]
         ws = colsum_rows("colsum", ncls * (-(-(nimg * th * tw) // 128)), nout) if bias_grad is not None else colsum_ws
         L.call("rbvae_gather_gemm", self.dt, A, W, out, bias, gate, mask, None, self.zero, nimg, ih, iw, th, tw, sa, oh, ow,
                so, kc, nout, lda, ldo, taps, ncls, ctypes.addressof(desc), relu, drop_mode, float(drop_p),
@@ -497,9 +509,8 @@ class Engine:
     def prepare(self, N: int):
         """Build every device table a pass over N frames reads from more than one stream (the gather-index tables
         of the weight-gradient GEMMs), on the current stream, before any side stream is forked."""
-        (h1, w1), (h2, w2), (h3, w3) = self.g1, self.g2, self.g3
-        self._conv_idx(N, h1, w1, h2, w2)
-        self._conv_idx(N, h2, w2, h3, w3)
+        for ly in (self.conv2, self.conv3):
+            self._conv_idx(N, *ly.big, *ly.small)
 
     def _wf_ksplit(self, N, Cin, IH, IW, Nout):
         """K-slices of rbvae_wgrad_first for this layer, or 0 when the im2col-row path stays (f32, a shape outside the
@@ -520,7 +531,7 @@ class Engine:
         L.call("rbvae_wgrad_first", self.dt, mode, x, *fm, Dy, slabs, self.zero, N, Cin, IH, IW, Nout, ldy, ks)
         self._wgrad_reduce(slabs, out, Nout, 64, 1, ks, dims, strides)
 
-    def _wgrad(self, Dy, In, idx, P, Co, Ci, ldy, ldi, taps, out, dims, strides, tag=None, geom=None):
+    def _wgrad(self, Dy, In, idx, P, Co, Ci, ldy, ldi, taps, out, dims, strides, tag=None, geom=None, cus=256):
         """wgrad GEMM into K-slice slabs; their fixed-order reduction into the torch layout is a job.
         geom = (Nimg, OH, OW, IH, IW) of a 3x3 stride-2 layer (Dy rows at OH x OW, In rows at IH x IW): with the nine taps
         in one workgroup (csrc/wgrad_halo.hip) when the launch gives every workgroup enough pixel blocks."""
@@ -540,7 +551,7 @@ class Engine:
             nblk = L.query("rbvae_wgrad3x3s2_halo_blocks", nimg, oh, ow)
             ntile = (Co // 64) * (Ci // 64)
             # K-slices: one round of workgroups on the CUs this launch can count on; at most ~40 MB of f32 slabs
-            ks = max(1, min(self._wg_cus // ntile, nblk, (40 << 20) // (Co * taps * Ci * 4)))
+            ks = max(1, min(cus // ntile, nblk, (40 << 20) // (Co * taps * Ci * 4)))
             # measured (tools/time_wgrad_halo.py): 64 x 64 channels 178 -> 71 us (cfg 3 conv2: the HBM time of its operands)
             # and 52 -> 27 us (conv3).  With 16 channel tiles per pixel block (256 x 256) a block's 32 KB stage is re-fetched
             # by every tile: the LDS-DMA alone takes 173 us (11 TB/s through the L2s), the MFMAs + fragment reads alone 137,
@@ -557,22 +568,22 @@ class Engine:
             ntile = (Co // 128) * (Ci // 128) * 3
             # K-slices: one round of workgroups on the CUs this launch can count on, every workgroup >= _wr_min_steps
             # blocks, at most ~_wr_slab_mb of f32 slabs
-            ks = max(1, min(self._wg_cus // ntile, nblk // self._wr_min_steps, (self._wr_slab_mb << 20) // (Co * taps * Ci * 4),
+            ks = max(1, min(cus // ntile, nblk // self._wr_min_steps, (self._wr_slab_mb << 20) // (Co * taps * Ci * 4),
                             int(round(math.sqrt(self._wr_ks_coef * nblk)))))
             return run("wgrad_row_k", ks, "rbvae_wgrad3x3s2_row", self.zero, nimg, oh, ow, Co, Ci, ldy, ldi)
         blocks = -(-Co // 128) * -(-Ci // (128 if Ci > 64 else 64)) * taps
         # K-slices: one round of workgroups on the 256 CUs, each with >= 256 pixels, and at most ~16 MB of f32
         # slabs to reduce afterwards
-        # (self._wg_cus: the CUs this launch can count on -- beside the LSTM backward kernels, which hold one CU per
+        # (cus: the CUs this launch can count on -- beside the LSTM backward kernels, which hold one CU per
         # sequence and whose registers leave no room for a second workgroup there, a 252-workgroup grid ran in two
         # rounds: 31 -> 43 us)
-        ks = max(1, min(self._wg_cus // max(blocks, 1), P // 256 if P >= 256 else 1,
+        ks = max(1, min(cus // max(blocks, 1), P // 256 if P >= 256 else 1,
                         max(1, (4 << 20) // (Co * taps * Ci))))
-        if self._ks_small and blocks >= 8 and P <= 4096:
+        if blocks >= 8 and P <= 4096:
             # the 4096-pixel layers (conv3 / first deconv at the bench shape): 3 K-slices of 22 steps instead of 7 of 9
             # -- 7 MB of slabs per weight instead of 16.5 MB; same GPU, 2 runs each: 0.4738 (7) / 0.4665 (4) /
             # 0.4659 (3) / 0.472 (2) ms per step
-            ks = min(ks, self._ks_small)
+            ks = min(ks, 3)
         ks = max(ks, -(-P // 4096))   # the kernel keeps a K-slice's gather indices in LDS
         run("wgrad_gemm_k<%d>" % (2 if Ci > 64 else 1), ks, "rbvae_wgrad_gemm", idx, self.zero, P, In.numel() // ldi, Co, Ci, ldy, ldi, taps)
 
@@ -605,7 +616,6 @@ class Engine:
         return True
 
     def _on_side(self):
-        import contextlib
         return torch.cuda.stream(self._side) if self.overlap else contextlib.nullcontext()
 
     def _join(self):
@@ -623,12 +633,60 @@ class Engine:
     def _E(self, *shape, dtype=None):
         return torch.empty(*shape, dtype=dtype or self.tdt, device=self.device)
 
+    # ---- a layer's launches: every argument of _gemm / _wgrad that belongs to the layer comes from its record ----------
+    # (reached as self._gemm / self._wgrad at call time: bench.py's roofline leg replaces both on the instance)
+    def _one(self, A, W, out, bias, gate, mask, rows, kc, nout, **kw):
+        """One-tap product out[rows][nout] = A[rows][kc] . W[nout][kc]^T, dense rows."""
+        self._gemm(A, W, out, bias, gate, mask, rows, 1, 1, 1, 1, 1, 1, 1, 1, kc, nout, kc, nout, 1, "one", **kw)
+
+    def _down(self, ly: Stride2, N, A, out, bias, gate, mask, **kw):
+        """big -> small grid (the encoder's forward, the decoder's input gradients)."""
+        (bh, bw), (sh, sw) = ly.big, ly.small
+        self._gemm(A, ly.f, out, bias, gate, mask, N, bh, bw, sh, sw, 2, sh, sw, 1, ly.cb, ly.cs, ly.cb, ly.cs, self.kk,
+                   "conv", **kw)
+
+    def _up(self, ly: Stride2, N, A, out, bias, gate, mask, **kw):
+        """small -> big grid (the decoder's forward, the encoder's input gradients)."""
+        (bh, bw), (sh, sw) = ly.big, ly.small
+        self._gemm(A, ly.d, out, bias, gate, mask, N, sh, sw, sh, sw, 1, bh, bw, 2, ly.cs, ly.cb, ly.cs, ly.cb, self.kk,
+                   "dgrad", **kw)
+
+    def _wgrad_s2(self, ly: Stride2, p: _Pass, small, big, tag, cus=256):
+        """The layer's weight gradient from its small-grid and its big-grid tensor."""
+        (bh, bw), (sh, sw) = ly.big, ly.small
+        kk, cs, cb = self.kk, ly.cs, ly.cb
+        self._wgrad(small, big, self._conv_idx(p.N, bh, bw, sh, sw), p.N * sh * sw, cs, cb, cs, cb, kk, p.G(ly.weight),
+                    (cs, cb, kk), (kk * cb, 1, cb), tag=(p.N, tag), geom=(p.N, sh, sw, bh, bw), cus=cus)
+
+    def _site(self, p: _Pass, j):
+        """(keep-mask, epilogue keywords) of dropout site j = 1 .. 4: drop_mode 0 none, 1 hash keyed seed * 8 + j, 2 the mask."""
+        m, mk = (0, None) if p.drop == 0 else (2, p.masks[j - 1]) if p.masks is not None else (1, None)
+        return mk, dict(drop_mode=m, drop_p=p.drop, scale=p.sv.gate_scale, seed=p.seed * 8 + j)
+
+    def _lstm_fwd(self, p: _Pass, stack, parts=None, cast=None):
+        """One stack forward; stack = (weights, packed weights, hs, hp, acts, cs).  parts: its input as the fc's K-slabs,
+        summed while staging; cast: the padded storage-dtype copy of its output -- both are the wavefront kernel's."""
+        dims = (p.S, p.T, self.latent, self.v.lstm_layers)
+        if parts is None and cast is None:
+            L.call("rbvae_lstm_fwd", *stack, *dims)
+        else:
+            L.call("rbvae_lstm_fwd_ex", *stack, *dims,
+                   *((None, 1, 0) if parts is None else (parts, self.fc_split, p.N * self.latent)),
+                   *((None, 0, 0) if cast is None else (cast, self.dt, self.Lp)))
+
+    def _lstm_bwd(self, p: _Pass, w, wT, acts, cs, dh, dG, d_in, nparts=1):
+        """One stack's BPTT; nparts > 1: dh as that many K-slabs (the wavefront kernel sums them)."""
+        dims = (p.S, p.T, self.latent, self.v.lstm_layers)
+        if nparts > 1:
+            L.call("rbvae_lstm_bwd_ex", w, acts, cs, dh, nparts, p.N * self.latent, dG, d_in, None, 0, 0, None, *dims)
+        else:
+            L.call("rbvae_lstm_bwd", w, wT, acts, cs, dh, dG, d_in, *dims)
+
     # ---- forward ---------------------------------------------------------------
-    def forward(self, flat: torch.Tensor, x: torch.Tensor, U: torch.Tensor, tau: float, hard: bool,
-                noise_ratio: float, train: bool, masks: Optional[Sequence[torch.Tensor]] = None,
-                seed: int = 0, need_grad: bool = True, encode_only: bool = False,
-                target: Optional[torch.Tensor] = None, recon_gscale: float = 0.0, kl_p: Optional[float] = None,
-                after_hs=None, defer_losses: bool = False,
+    def forward(self, flat: torch.Tensor, x: torch.Tensor, U: torch.Tensor, tau: float, hard: bool, noise_ratio: float,
+                train: bool, masks: Optional[Sequence[torch.Tensor]] = None, seed: int = 0, need_grad: bool = True,
+                encode_only: bool = False, target: Optional[torch.Tensor] = None, recon_gscale: float = 0.0,
+                kl_p: Optional[float] = None, after_hs=None, defer_losses: bool = False,
                 frame_map: Optional[Tuple[int, int, int, int, int]] = None, tau_dev: Optional[torch.Tensor] = None,
                 bwd_from_dpre: bool = False):
         """x: [S,T,C,H,W] f32 NCHW frames; U: [S*T, L] uniform noise.
@@ -650,223 +708,201 @@ class Engine:
         if (H, W) != self.hw or C != self.in_ch:
             raise RuntimeError(f"input frames {tuple(x.shape[2:])} do not match the model's "
                                f"({self.in_ch}, {self.hw[0]}, {self.hw[1]})")
-        N = S * T
-        k, kk = self.k, self.k * self.k
-        c1, c2, c3 = v.channels
-        (h1, w1), (h2, w2), (h3, w3) = self.g1, self.g2, self.g3
-        Ld, lay = self.latent, self.layout
-        i0, i1, i2 = lay.conv_idx
-        P = lambda name: lay.view(flat, name)
-        x = x.contiguous()
         drop = v.dropout if train else 0.0
-        dscale = 1.0 / (1.0 - drop) if drop > 0 else 1.0
-
-        def dm(j):      # (drop_mode, mask) of dropout site j
-            if drop == 0:
-                return 0, None
-            return (2, masks[j]) if masks is not None else (1, None)
-
         sv = Saved()
-        sv.N, sv.S, sv.T, sv.hw, sv.train, sv.tau, sv.hard = N, S, T, (H, W), train, tau, hard
-        sv.tau_dev = tau_dev
-        sv.gate_scale = dscale
+        sv.N, sv.S, sv.T, sv.hw, sv.train, sv.tau, sv.tau_dev, sv.hard = S * T, S, T, (H, W), train, tau, tau_dev, hard
+        sv.gate_scale = 1.0 / (1.0 - drop) if drop > 0 else 1.0
         sv.dd2_fused = None
-        # encoder CNN
-        sv.a1 = self._E(N * h1 * w1, c1)
-        m, mk = dm(0)
-        fm = frame_map if frame_map is not None else (0, 0, 0, 0, C * H * W)
-        fused1 = bool(self.conv_first_fused and k == 3 and self.K1 == 64 and m != 2
+        p = _Pass(self, sv, flat)
+        p.drop, p.masks, p.seed, p.frame_map = drop, masks, seed, frame_map
+        p.U, p.r, p.kl_p, p.defer_losses = U, (noise_ratio if v.noise_ratio_arg else 1.0), kl_p, defer_losses
+        # the encoder stack's launch is followed by this: the side stream picks up there; after_hs itself is issued behind
+        # the main stream's continuation (end of forward())
+        fork = self._fork if after_hs is not None else (lambda: None)
+        self._fwd_encoder(p, x.contiguous())
+        decode = v.simple_order or not encode_only
+        hs, kl = self._fwd_latent(p, need_grad, decode, fork)
+        if not decode:
+            return {"z": sv.z.view(S, T, self.latent), "hs": hs, "saved": sv}
+        self._fwd_decoder(p)
+        mse, sse = self._fwd_last(p, target, recon_gscale, need_grad, bwd_from_dpre)
+        if after_hs is not None and not v.simple_order:
+            with self._on_side():
+                after_hs(hs)
+        return {"xr": sv.xr, "hs": hs, "z": sv.z.view(S, T, self.latent), "e": sv.e, "kl": kl, "mse": mse, "sse": sse,
+                "saved": sv}
+
+    def _fwd_encoder(self, p: _Pass, x):
+        """frames -> a1 -> a2 -> a3."""
+        sv, N, H, W, C, k = p.sv, p.N, p.H, p.W, self.in_ch, self.k
+        c1, c2, c3 = self.v.channels
+        sv.a1 = self._E(p.P1, c1)
+        mk, kw = self._site(p, 1)
+        sv.x_in, sv.fm_in = x, p.fm(C)
+        fused1 = bool(k == 3 and self.K1 == 64 and kw["drop_mode"] != 2
                       and L.query("rbvae_conv_first_fused_ok", self.dt, C, H, W, c1, N))
         # the im2col rows are written for the weight gradient unless it rebuilds them from the frames (rbvae_wgrad_first)
-        keep_col = not (fused1 and train and self._wf_ksplit(N, C, H, W, c1))
-        sv.col1 = self._E(N * h1 * w1, self.K1) if keep_col else None
-        sv.x_in, sv.fm_in = x, fm
+        keep_col = not (fused1 and sv.train and self._wf_ksplit(N, C, H, W, c1))
+        sv.col1 = self._E(p.P1, self.K1) if keep_col else None
         if fused1:
             # im2col + GEMM + bias/ReLU/dropout of the first conv in one kernel (csrc/conv_first.hip)
-            L.call("rbvae_conv_first_fused", self.dt, x, *fm, self.W1p, P(f"encoder_cnn.conv.{i0}.bias"), self.zero,
-                   sv.col1, sv.a1, N, C, H, W, c1, c1, 1, m, float(drop), float(dscale), int(seed * 8 + 1), self.seed_dev)
+            L.call("rbvae_conv_first_fused", self.dt, x, *sv.fm_in, self.W1p, p.P(self.conv1.bias), self.zero, sv.col1, sv.a1,
+                   N, C, H, W, c1, c1, 1, kw["drop_mode"], float(p.drop), float(sv.gate_scale), int(kw["seed"]), self.seed_dev)
         else:
-            L.call("rbvae_im2col_frames", self.dt, x, *fm, H * W, W, 1, N, C, H, W, h1, w1, k, k, 2, 1, self.K1, sv.col1)
-            self._gemm(sv.col1, self.W1p, sv.a1, P(f"encoder_cnn.conv.{i0}.bias"), None, mk, N * h1 * w1, 1, 1, 1, 1, 1,
-                       1, 1, 1, self.K1, c1, self.K1, c1, 1, "one", relu=1, drop_mode=m, drop_p=drop, scale=dscale,
-                       seed=seed * 8 + 1)
-        sv.a2 = self._E(N * h2 * w2, c2)
-        m, mk = dm(1)
-        self._gemm(sv.a1, self.W2f, sv.a2, P(f"encoder_cnn.conv.{i1}.bias"), None, mk, N, h1, w1, h2, w2, 2, h2, w2,
-                   1, c1, c2, c1, c2, kk, "conv", relu=1, drop_mode=m, drop_p=drop, scale=dscale, seed=seed * 8 + 2)
-        sv.a3 = self._E(N * h3 * w3, c3)
-        self._gemm(sv.a2, self.W3f, sv.a3, P(f"encoder_cnn.conv.{i2}.bias"), None, None, N, h2, w2, h3, w3, 2, h3,
-                   w3, 1, c2, c3, c2, c3, kk, "conv", relu=1 if v.simple_order else 0)
-        # fc -> logits e [N][L]
+            L.call("rbvae_im2col_frames", self.dt, x, *sv.fm_in, H * W, W, 1, N, C, H, W, *self.g1, k, k, 2, 1, self.K1, sv.col1)
+            self._one(sv.col1, self.W1p, sv.a1, p.P(self.conv1.bias), None, mk, p.P1, self.K1, c1, relu=1, **kw)
+        sv.a2 = self._E(p.P2, c2)
+        mk, kw = self._site(p, 2)
+        self._down(self.conv2, N, sv.a1, sv.a2, p.P(self.conv2.bias), None, mk, relu=1, **kw)
+        sv.a3 = self._E(p.P3, c3)
+        self._down(self.conv3, N, sv.a2, sv.a3, p.P(self.conv3.bias), None, None, relu=1 if self.v.simple_order else 0)
+
+    def _fwd_latent(self, p: _Pass, need_grad, decode, fork):
+        """a3 -> fc logits e -> LSTM stacks and binarisation in the variant's order -> ds_pad, the decoder fc's padded input
+        (decode False: stops at the codes).  Returns (h_seq, kl)."""
+        v, sv, N, S, T, Ld, f32 = self.v, p.sv, p.N, p.S, p.T, self.latent, torch.float32
         nl = v.lstm_layers
-        sv.hs_enc = self._E(nl + 1, S, T, Ld, dtype=torch.float32)
-        sv.hs_dec = self._E(nl + 1, S, T, Ld, dtype=torch.float32)
-        sv.e = self._E(N, Ld, dtype=torch.float32) if v.simple_order else sv.hs_enc[0].view(N, Ld)
-        e_parts = None
+        sv.hs_enc = self._E(nl + 1, S, T, Ld, dtype=f32)
+        sv.hs_dec = self._E(nl + 1, S, T, Ld, dtype=f32)
+        sv.e = self._E(N, Ld, dtype=f32) if v.simple_order else sv.hs_enc[0].view(N, Ld)
         # the slab input / cast output exist in the wavefront kernel only, whose LDS need grows with T: asked per call of
         # the query the C dispatcher uses itself (long sequences take the plain kernels, the unsplit fc and rbvae_cast_pad)
-        fwd_wave = self.lstm_cast and bool(L.query("rbvae_lstm_fwd_wave_ok", T, Ld, nl))
-        if self.fc_split > 1 and fwd_wave:
-            e_parts = self._buf((N, "e_parts"), self.fc_split * N * Ld)
-            L.call("rbvae_skinny_linear_parts", self.dt, sv.a3, self.Wfc, P("encoder_cnn.fc.bias"), e_parts, N, Ld,
-                   self.F3, self.F3, self.F3, Ld, self.fc_split)
+        p.fwd_wave = self.wave_ok and bool(L.query("rbvae_lstm_fwd_wave_ok", T, Ld, nl))
+        parts = (self.fc_split,) if self.fc_split > 1 and p.fwd_wave else ()       # the logits as K-slabs, or whole
+        p.e_parts = self._buf((N, "e_parts"), self.fc_split * N * Ld) if parts else None
+        L.call("rbvae_skinny_linear_parts" if parts else "rbvae_skinny_linear", self.dt, sv.a3, self.Wfc,
+               p.P("encoder_cnn.fc.bias"), p.e_parts if parts else sv.e, N, Ld, self.F3, self.F3, self.F3, Ld, *parts)
+        keep = (lambda w: self._E(nl, S, T, w, dtype=f32)) if need_grad else (lambda w: None)     # what only backward() reads
+        sv.hp_enc, sv.cs_enc, sv.acts_enc, sv.hp_dec, sv.cs_dec, sv.acts_dec = (keep(w) for w in (Ld, Ld, 4 * Ld) * 2)
+        sv.y = self._E(N, Ld, dtype=f32)
+        sv.ds_pad = self._E(N, self.Lp) if decode else None
+        p.enc = (p.P("encoder_rnn.lstm.weight_ih_l0"), self.wT_enc, sv.hs_enc, sv.hp_enc, sv.acts_enc, sv.cs_enc)
+        p.dec = (p.P("decoder_rnn.lstm.weight_ih_l0"), self.wT_dec, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec)
+        # what the binarisation launches share: eps, hard, the KL term's p / eps / switch, the noise key (the closure must
+        # not hold p: a cycle would keep a captured pass's tensors alive until the collector runs)
+        tail = (int(p.seed) * 8 + 5, self.seed_dev)
+        p.bin = lambda klp, kl_eps, on: (v.eps, int(sv.hard), float(klp), kl_eps, on, *tail)
+        if v.simple_order:
+            hs, kl, padded = self._fwd_latent_simple(p), (self._E(1, dtype=f32) if p.kl_p is not None else None), False
+        elif decode and self.wave_ok and bool(L.query("rbvae_lstm_pair_fwd_ok", T, Ld, nl)):
+            hs, kl, padded = *self._fwd_latent_pair(p, fork), True
         else:
-            L.call("rbvae_skinny_linear", self.dt, sv.a3, self.Wfc, P("encoder_cnn.fc.bias"), sv.e, N, Ld, self.F3,
-                   self.F3, self.F3, Ld)
-        keep = need_grad
-        if keep:
-            sv.hp_enc = self._E(nl, S, T, Ld, dtype=torch.float32)
-            sv.cs_enc = self._E(nl, S, T, Ld, dtype=torch.float32)
-            sv.acts_enc = self._E(nl, S, T, 4 * Ld, dtype=torch.float32)
-            sv.hp_dec, sv.cs_dec, sv.acts_dec = (torch.empty_like(sv.hp_enc), torch.empty_like(sv.cs_enc),
-                                                 torch.empty_like(sv.acts_enc))
-        else:
-            sv.hp_enc = sv.cs_enc = sv.acts_enc = sv.hp_dec = sv.cs_dec = sv.acts_dec = None
-        sv.y = self._E(N, Ld, dtype=torch.float32)
-        r = noise_ratio if v.noise_ratio_arg else 1.0
+            hs, kl, padded = *self._fwd_latent_stacks(p, decode, fork), p.fwd_wave
+        if decode and not padded:       # no LSTM launch wrote ds_pad itself
+            L.call("rbvae_cast_pad", self.dt, sv.hs_dec[nl], sv.ds_pad, N, Ld, self.Lp)
+        return hs, kl
+
+    def _fwd_latent_pair(self, p: _Pass, fork):
+        """encoder stack -> binarise (+ KL sums) -> decoder stack as one wavefront launch."""
+        sv, N, S, T, Ld, nl, kl_p = p.sv, p.N, p.S, p.T, self.latent, self.v.lstm_layers, p.kl_p
+        hs, sv.z, kl = sv.hs_enc[nl], sv.hs_dec[0].view(N, Ld), None
+        parts = self._E(S, dtype=torch.float32) if kl_p is not None else None
+        (wenc, wTe, *enc), (wdec, wTd, *dec) = p.enc, p.dec
+        L.call("rbvae_lstm_pair_fwd", wenc, wTe, wdec, wTd, *enc, *dec, p.e_parts, self.fc_split, N * Ld, p.U, sv.y,
+               parts, float(sv.tau), sv.tau_dev, float(p.r), *p.bin(kl_p if kl_p is not None else 0.5, 1e-8, 1),
+               sv.ds_pad, self.dt, self.Lp, S, T, Ld, nl)
+        if kl_p is not None:
+            kl = (parts, S, 1.0 / N) if p.defer_losses else (parts.sum() * (1.0 / N)).reshape(1)
+        fork()
+        return hs, kl
+
+    def _fwd_latent_stacks(self, p: _Pass, decode, fork):
+        """encoder stack, binarise (+ KL), decoder stack as launches of their own (sequences the pair kernel refuses)."""
+        sv, N, Ld, nl, kl_p, U = p.sv, p.N, self.latent, self.v.lstm_layers, p.kl_p, p.U
         kl = self._E(1, dtype=torch.float32) if kl_p is not None else None
-        wenc, wdec = P("encoder_rnn.lstm.weight_ih_l0"), P("decoder_rnn.lstm.weight_ih_l0")
-        pending_hs = None
-        fused_pair = (not v.simple_order and not encode_only and self.lstm_pair
-                      and bool(L.query("rbvae_lstm_pair_fwd_ok", T, Ld, nl)))
-        if fused_pair:
-            # encoder stack -> binarise (+ KL sums) -> decoder stack as one wavefront launch
-            hs = sv.hs_enc[nl]
-            sv.z = sv.hs_dec[0].view(N, Ld)
-            parts = None
-            if kl_p is not None:
-                parts = self._E(S, dtype=torch.float32)
-                kl = (parts, S, 1.0 / N) if defer_losses else kl
-            sv.ds_pad = self._E(N, self.Lp)
-            L.call("rbvae_lstm_pair_fwd", wenc, self.wT_enc, wdec, self.wT_dec, sv.hs_enc, sv.hp_enc, sv.acts_enc,
-                   sv.cs_enc, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec, e_parts, self.fc_split, N * Ld, U, sv.y,
-                   parts, float(tau), tau_dev, float(r), v.eps, int(hard), float(kl_p if kl_p is not None else 0.5), 1e-8, 1,
-                   int(seed) * 8 + 5, self.seed_dev, sv.ds_pad, self.dt, self.Lp, S, T, Ld, nl)
-            if kl_p is not None and not defer_losses:
-                kl = (parts.sum() * (1.0 / N)).reshape(1)
-            if after_hs is not None:
-                self._fork()
-                pending_hs = hs                 # issued behind the main stream's continuation (end of forward())
-        elif not v.simple_order:
-            if e_parts is not None:
-                L.call("rbvae_lstm_fwd_ex", wenc, self.wT_enc, sv.hs_enc, sv.hp_enc, sv.acts_enc, sv.cs_enc, S, T, Ld,
-                       nl, e_parts, self.fc_split, N * Ld, None, 0, 0)
-            else:
-                L.call("rbvae_lstm_fwd", wenc, self.wT_enc, sv.hs_enc, sv.hp_enc, sv.acts_enc, sv.cs_enc, S, T, Ld, nl)
-            hs = sv.hs_enc[nl]
-            if after_hs is not None:
-                self._fork()
-                pending_hs = hs
-            sv.z = sv.hs_dec[0].view(N, Ld)
-            if defer_losses and kl_p is not None:
-                nkl = L.query("rbvae_binarize_kl_nparts", N, Ld)
-                parts = self._E(nkl, dtype=torch.float32)
-                L.call("rbvae_binarize_kl_fwd_parts", hs, U, sv.y, sv.z, parts, N, Ld, float(tau), tau_dev, float(r), v.eps,
-                       int(hard), float(kl_p), 1e-8, 1, int(seed) * 8 + 5, self.seed_dev)
-                kl = (parts, nkl, 1.0 / N)
-            else:
-                L.call("rbvae_binarize_kl_fwd", hs, U, sv.y, sv.z, kl, N, Ld, float(tau), float(r), v.eps, int(hard),
-                       float(kl_p if kl_p is not None else 0.5), 1e-8, 1, int(seed) * 8 + 5, self.seed_dev)
-            if encode_only:
-                return {"z": sv.z.view(S, T, Ld), "hs": hs, "saved": sv}
-            if fwd_wave:
-                sv.ds_pad = self._E(N, self.Lp)
-                L.call("rbvae_lstm_fwd_ex", wdec, self.wT_dec, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec, S, T, Ld, nl,
-                       None, 1, 0, sv.ds_pad, self.dt, self.Lp)
-            else:
-                L.call("rbvae_lstm_fwd", wdec, self.wT_dec, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec, S, T, Ld, nl)
+        self._lstm_fwd(p, p.enc, parts=p.e_parts)
+        hs = sv.hs_enc[nl]
+        fork()
+        sv.z = sv.hs_dec[0].view(N, Ld)
+        if p.defer_losses and kl_p is not None:
+            nkl = L.query("rbvae_binarize_kl_nparts", N, Ld)
+            parts = self._E(nkl, dtype=torch.float32)
+            L.call("rbvae_binarize_kl_fwd_parts", hs, U, sv.y, sv.z, parts, N, Ld, float(sv.tau), sv.tau_dev, float(p.r),
+                   *p.bin(kl_p, 1e-8, 1))
+            kl = (parts, nkl, 1.0 / N)
         else:
-            sv.z = sv.hs_enc[0].view(N, Ld)
-            L.call("rbvae_binarize_kl_fwd", sv.e, U, sv.y, sv.z, None, N, Ld, float(tau), float(r), v.eps, int(hard),
-                   0.5, 1e-10, 0, int(seed) * 8 + 5, self.seed_dev)
-            L.call("rbvae_lstm_fwd", wenc, self.wT_enc, sv.hs_enc, sv.hp_enc, sv.acts_enc, sv.cs_enc, S, T, Ld, nl)
-            hs = sv.hs_enc[nl]
-            sv.hs_dec[0].copy_(hs)
-            L.call("rbvae_lstm_fwd", wdec, self.wT_dec, sv.hs_dec, sv.hp_dec, sv.acts_dec, sv.cs_dec, S, T, Ld, nl)
-        ds = sv.hs_dec[nl]
-        # decoder CNN
-        if not ((fwd_wave or fused_pair) and not v.simple_order):
-            sv.ds_pad = self._E(N, self.Lp)
-            L.call("rbvae_cast_pad", self.dt, ds, sv.ds_pad, N, Ld, self.Lp)
-        sv.f = self._E(N * h3 * w3, c3)
-        self._gemm(sv.ds_pad, self.Wdfc, sv.f, self.bdfc, None, None, N, 1, 1, 1, 1, 1, 1, 1, 1, self.Lp, self.F3,
-                   self.Lp, self.F3, 1, "one")
-        sv.d1 = self._E(N * h2 * w2, c2)
-        m, mk = dm(2)
-        self._gemm(sv.f, self.V1d, sv.d1, P(f"decoder_cnn.deconv.{i0}.bias"), None, mk, N, h3, w3, h3, w3, 1, h2, w2,
-                   2, c3, c2, c3, c2, kk, "dgrad", relu=1, drop_mode=m, drop_p=drop, scale=dscale, seed=seed * 8 + 3)
-        sv.d2 = self._E(N * h1 * w1, c1)
-        m, mk = dm(3)
-        self._gemm(sv.d1, self.V2d, sv.d2, P(f"decoder_cnn.deconv.{i1}.bias"), None, mk, N, h2, w2, h2, w2, 1, h1, w1,
-                   2, c2, c1, c2, c1, kk, "dgrad", relu=1, drop_mode=m, drop_p=drop, scale=dscale, seed=seed * 8 + 4)
-        sv.xr = self._E(S, T, self.out_ch, H, W, dtype=torch.float32)
-        mse = None
-        sse = None
-        sv.dpre3 = None
-        sv.b3_parts = None
-        fparts = L.query("rbvae_deconv_last_fused_parts", self.dt, N, h1, w1, c1, self.out_ch) if (
-            self.deconv_fused and k == 3 and (target is None or defer_losses)) else 0
-        nb2 = (L.query("rbvae_deconv_last_dgrad_blocks", self.dt, self.out_ch, H, W, c1, N)
-               if (fparts and self.deconv_last_bwd_fused and bwd_from_dpre and target is not None and need_grad
-                   and defer_losses and self.conv_first_fused and self.K3 == 64
-                   and L.query("rbvae_deconv_last_fwd_bwd_ok", self.dt, N, h1, w1, c1, self.out_ch)) else 0)
+            L.call("rbvae_binarize_kl_fwd", hs, U, sv.y, sv.z, kl, N, Ld, float(sv.tau), float(p.r),
+                   *p.bin(kl_p if kl_p is not None else 0.5, 1e-8, 1))
+        if decode:
+            self._lstm_fwd(p, p.dec, cast=sv.ds_pad if p.fwd_wave else None)
+        return hs, kl
+
+    def _fwd_latent_simple(self, p: _Pass):
+        """The simple variant's order: binarise the logits, then both stacks (plain kernels, no KL term)."""
+        sv, N, Ld, nl = p.sv, p.N, self.latent, self.v.lstm_layers
+        sv.z = sv.hs_enc[0].view(N, Ld)
+        L.call("rbvae_binarize_kl_fwd", sv.e, p.U, sv.y, sv.z, None, N, Ld, float(sv.tau), float(p.r), *p.bin(0.5, 1e-10, 0))
+        self._lstm_fwd(p, p.enc)
+        hs = sv.hs_enc[nl]
+        sv.hs_dec[0].copy_(hs)
+        self._lstm_fwd(p, p.dec)
+        return hs
+
+    def _fwd_decoder(self, p: _Pass):
+        """ds_pad -> fc -> f -> d1 -> d2."""
+        sv, N = p.sv, p.N
+        c1, c2, c3 = self.v.channels
+        sv.f = self._E(p.P3, c3)
+        self._one(sv.ds_pad, self.Wdfc, sv.f, self.bdfc, None, None, N, self.Lp, self.F3)
+        sv.d1 = self._E(p.P2, c2)
+        mk, kw = self._site(p, 3)
+        self._up(self.deconv0, N, sv.f, sv.d1, p.P(self.deconv0.bias), None, mk, relu=1, **kw)
+        sv.d2 = self._E(p.P1, c1)
+        mk, kw = self._site(p, 4)
+        self._up(self.deconv1, N, sv.d1, sv.d2, p.P(self.deconv1.bias), None, mk, relu=1, **kw)
+
+    def _fwd_last(self, p: _Pass, target, recon_gscale, need_grad, bwd_from_dpre):
+        """d2 -> x_recon, with a target the squared-error sums and (need_grad) dpre3 = d(loss)/d(pre-sigmoid); returns
+        (mse, sse).  The fused kernel where it exists (3x3, eval or deferred losses), else product matrix + col2im."""
+        sv, N, S, T, H, W, k, oc = p.sv, p.N, p.S, p.T, p.H, p.W, self.k, self.out_ch
+        c1, (h1, w1) = self.v.channels[0], self.g1
+        sv.xr = self._E(S, T, oc, H, W, dtype=torch.float32)
+        mse = sse = ws = sv.dpre3 = sv.b3_parts = None
+        b3 = p.P(self.deconv2.bias)
+        fparts = L.query("rbvae_deconv_last_fused_parts", self.dt, N, h1, w1, c1, oc) if (
+            k == 3 and (target is None or p.defer_losses)) else 0
+        if target is not None:
+            # persistent (one fused forward is in flight at a time): the backward pass's job table points into it
+            ws = self._buf((N, "col2im_ws"), max(L.query("rbvae_col2im_ws_floats"), 5 * fparts))
+            nparts = fparts or L.query("rbvae_col2im_nparts", sv.xr.numel())
+            if p.defer_losses:    # per-block partial sums stay in ws; rbvae_combine_losses finishes the mean
+                sse = (ws, nparts, 1.0 / sv.xr.numel())
+            else:
+                mse = self._E(1, dtype=torch.float32)
+            if need_grad:
+                sv.dpre3 = self._E(N, H, W, oc, dtype=torch.float32)
+                if fparts or L.query("rbvae_col2im_has_dcol", N, h1, w1, self.NY, H, W, oc):
+                    # the kernel leaves dpre3's per-block column sums (the last deconv's bias gradient) behind the
+                    # squared-error sums in ws
+                    sv.b3_parts = (ws, nparts)
         if fparts:
             # last deconv + sigmoid + recon loss as one kernel (products on the matrix cores from an LDS-resident pixel
             # block, kept in f32): no product matrix in HBM, no separate col2im pass
-            ws = None
-            fm = frame_map if frame_map is not None else (0, 0, 0, 0, self.out_ch * H * W)
-            if target is not None:
-                ws = self._buf((N, "col2im_ws"), max(L.query("rbvae_col2im_ws_floats"), 5 * fparts))
-                sse = (ws, fparts, 1.0 / sv.xr.numel())
-                if need_grad:
-                    sv.dpre3 = self._E(N, H, W, self.out_ch, dtype=torch.float32)
-                    sv.b3_parts = (ws, fparts)
+            nb2 = (L.query("rbvae_deconv_last_dgrad_blocks", self.dt, oc, H, W, c1, N)
+                   if (self.deconv_last_bwd_fused and bwd_from_dpre and target is not None and need_grad
+                       and p.defer_losses and self.K3 == 64
+                       and L.query("rbvae_deconv_last_fwd_bwd_ok", self.dt, N, h1, w1, c1, oc)) else 0)
+            fm = p.fm(oc)
             if nb2:
                 # ... and the layer's input gradient from the same resident block: backward()'s buffers, filled here
-                P1 = N * h1 * w1
-                dd2 = self._buf((N, "dd2"), P1 * c1, self.tdt).view(P1, c1)
-                col3 = (None if self._wf_ksplit(N, self.out_ch, H, W, c1)
-                        else self._buf((N, "col3"), P1 * self.K3, self.tdt).view(P1, self.K3))
+                dd2 = p.tmp("dd2", p.P1, c1)
+                col3 = None if self._wf_ksplit(N, oc, H, W, c1) else p.tmp("col3", p.P1, self.K3)
                 ws2 = self._buf((N, "colsum_dd2f"), nb2 * c1)
                 sv.dd2_fused = (dd2, col3, ws2, nb2)
-                L.call("rbvae_deconv_last_fwd_bwd", self.dt, sv.d2, self.V3p, self.NY, self.V3f,
-                       P(f"decoder_cnn.deconv.{i2}.bias"), self.zero, N, h1, w1, c1, self.out_ch, sv.xr, target.contiguous(),
-                       *fm, ws, sv.dpre3, float(recon_gscale), col3, dd2, float(sv.gate_scale), ws2)
+                L.call("rbvae_deconv_last_fwd_bwd", self.dt, sv.d2, self.V3p, self.NY, self.V3f, b3, self.zero, N, h1, w1,
+                       c1, oc, sv.xr, target.contiguous(), *fm, ws, sv.dpre3, float(recon_gscale), col3, dd2,
+                       float(sv.gate_scale), ws2)
             else:
-                L.call("rbvae_deconv_last_fused", self.dt, sv.d2, self.V3p, self.NY, P(f"decoder_cnn.deconv.{i2}.bias"),
-                       self.zero, N, h1, w1, c1, self.out_ch, sv.xr, None if target is None else target.contiguous(), *fm, ws,
-                       sv.dpre3, float(recon_gscale))
-        else:
-            Y = self._E(N * h1 * w1, self.NY)
-            self._gemm(sv.d2, self.V3p, Y, None, None, None, N * h1 * w1, 1, 1, 1, 1, 1, 1, 1, 1, c1, self.NY, c1,
-                       self.NY, 1, "one")
-            if target is not None:
-                # persistent (one fused forward is in flight at a time): the backward pass's job table points into it
-                ws = self._buf((N, "col2im_ws"), L.query("rbvae_col2im_ws_floats"))
-                if defer_losses:    # per-block partial sums stay in ws; rbvae_combine_losses finishes the mean
-                    sse = (ws, L.query("rbvae_col2im_nparts", sv.xr.numel()), 1.0 / sv.xr.numel())
-                else:
-                    mse = self._E(1, dtype=torch.float32)
-                if need_grad:
-                    sv.dpre3 = self._E(N, H, W, self.out_ch, dtype=torch.float32)
-                    if L.query("rbvae_col2im_has_dcol", N, h1, w1, self.NY, H, W, self.out_ch):
-                        # the kernel leaves dpre3's per-block column sums (the last deconv's bias gradient) behind the
-                        # squared-error sums in ws
-                        sv.b3_parts = (ws, L.query("rbvae_col2im_nparts", sv.xr.numel()))
-                if frame_map is None:
-                    L.call("rbvae_col2im_sigmoid", self.dt, Y, self.NY, P(f"decoder_cnn.deconv.{i2}.bias"), N, h1, w1, H, W,
-                           self.out_ch, k, k, 1, sv.xr, target.contiguous(), mse, ws, sv.dpre3, float(recon_gscale), None)
-                else:
-                    L.call("rbvae_col2im_sigmoid_frames", self.dt, Y, self.NY, P(f"decoder_cnn.deconv.{i2}.bias"), N, h1,
-                           w1, H, W, self.out_ch, k, k, 1, sv.xr, target.contiguous(), *frame_map, mse, ws, sv.dpre3,
-                           float(recon_gscale), None)
-            else:
-                L.call("rbvae_col2im_sigmoid", self.dt, Y, self.NY, P(f"decoder_cnn.deconv.{i2}.bias"), N, h1, w1, H, W,
-                       self.out_ch, k, k, 1, sv.xr, None, None, None, None, 0.0, None)
-        if pending_hs is not None:
-            with self._on_side():
-                after_hs(pending_hs)
-        return {"xr": sv.xr, "hs": hs, "z": sv.z.view(S, T, Ld), "e": sv.e, "kl": kl, "mse": mse, "sse": sse, "saved": sv}
+                L.call("rbvae_deconv_last_fused", self.dt, sv.d2, self.V3p, self.NY, b3, self.zero, N, h1, w1, c1, oc,
+                       sv.xr, None if target is None else target.contiguous(), *fm, ws, sv.dpre3, float(recon_gscale))
+            return mse, sse
+        Y = self._E(p.P1, self.NY)
+        self._one(sv.d2, self.V3p, Y, None, None, None, p.P1, c1, self.NY)
+        framed = target is not None and p.frame_map is not None
+        L.call("rbvae_col2im_sigmoid_frames" if framed else "rbvae_col2im_sigmoid", self.dt, Y, self.NY, b3, N, h1, w1, H, W,
+               oc, k, k, 1, sv.xr, None if target is None else target.contiguous(), *(p.frame_map if framed else ()), mse, ws,
+               sv.dpre3, float(recon_gscale) if target is not None else 0.0, None)
+        return mse, sse
 
     # ---- backward --------------------------------------------------------------
     def backward(self, flat: torch.Tensor, gflat: torch.Tensor, sv: Saved, g_xr: Optional[torch.Tensor],
@@ -884,109 +920,21 @@ class Engine:
         gradients of decoder_cnn.* and both LSTM stacks (the contiguous tail of gflat from
         layout.offsets["decoder_cnn.fc.weight"]) are final and only the encoder CNN's remain to be computed: the
         data-parallel trainer ends one graph and starts the next there and all-reduces that tail beside the rest."""
+        # The schedule: which stage (_bwd_*: they know nothing of streams) is issued when, and on which stream
         self._join()                       # side-stream work of forward() (after_hs)
         # the loss bookkeeping rides the side stream's fork for the decoder's weight gradients (no edge of its own)
         book_with_decoder = side_first is not None and self.overlap
         if side_first is not None and not book_with_decoder:
             side_first()
-        v = self.v
-        N, S, T = sv.N, sv.S, sv.T
-        H, W = sv.hw
-        k, kk = self.k, self.k * self.k
-        c1, c2, c3 = v.channels
-        (h1, w1), (h2, w2), (h3, w3) = self.g1, self.g2, self.g3
-        Ld, lay, nl = self.latent, self.layout, v.lstm_layers
-        i0, i1, i2 = lay.conv_idx
-        P = lambda name: lay.view(flat, name)
-        G = lambda name: lay.view(gflat, name)
-        gs = sv.gate_scale
-        P1, P2, P3 = N * h1 * w1, N * h2 * w2, N * h3 * w3
-        g3 = h3 * w3
-        oc = self.out_ch
+        p = _Pass(self, sv, flat, gflat)
         self._jobs = JobList()
-        f32 = torch.float32
-
-        def tmp(tag, *shape, dtype=None):
-            n = math.prod(shape)
-            return self._buf((N, tag), n, dtype or self.tdt).view(*shape)
-
-        # --- decoder CNN, data-gradient chain first (main stream) ...
-        if g_xr is not None:
-            dpre3 = tmp("dpre3", N, H, W, oc, dtype=f32)
-            L.call("rbvae_sigmoid_bwd_nhwc", g_xr.contiguous(), sv.xr, dpre3, N, oc, H, W)
-        else:
-            dpre3 = sv.dpre3
-            if dpre3 is None:
-                raise RuntimeError("backward without g_xr needs forward(target=..., need_grad=True)")
-        dd2 = tmp("dd2", P1, c1)
-        nb = (L.query("rbvae_deconv_last_dgrad_blocks", self.dt, oc, H, W, c1, N)
-              if self.conv_first_fused and k == 3 and self.K3 == 64 else 0)
-        wf3 = self._wf_ksplit(N, oc, H, W, c1) if nb else 0      # the last deconv's weight gradient from dpre3 itself
-        col3 = None if wf3 else tmp("col3", P1, self.K3)
-        if nb:
-            # im2col + GEMM + gate + bias-gradient partial sums in one kernel (csrc/conv_first.hip, MODE 1)
-            ws = self._buf((N, "colsum_dd2f"), nb * c1)
-            if g_xr is None and sv.dd2_fused is not None:
-                # forward() left dd2, col3 and the column sums in these very buffers (rbvae_deconv_last_fwd_bwd)
-                assert sv.dd2_fused[0].data_ptr() == dd2.data_ptr() and sv.dd2_fused[2].data_ptr() == ws.data_ptr()
-                assert (sv.dd2_fused[1] is None) == (col3 is None) and sv.dd2_fused[3] == nb
-            else:
-                L.call("rbvae_deconv_last_dgrad_fused", self.dt, dpre3, self.V3f, self.zero, col3, sv.d2, dd2, N, oc, H, W,
-                       c1, c1, float(gs), ws)
-            self._jobs.add(JOB_ROWS, ws, G(f"decoder_cnn.deconv.{i1}.bias"), (1, 1, c1), (0, 0, 1), nslab=nb, slab=c1)
-        else:
-            L.call("rbvae_im2col", self.dt, dpre3, H * W * oc, 1, W * oc, oc, N, oc, H, W, h1, w1, k, k, 2, 1, self.K3, col3)
-            self._gemm(col3, self.V3f, dd2, None, sv.d2, None, P1, 1, 1, 1, 1, 1, 1, 1, 1, self.K3, c1, self.K3, c1, 1,
-                       "one", scale=gs, bias_grad=G(f"decoder_cnn.deconv.{i1}.bias"), tag=(N, "dd2"))
-        # deconv1 (c2 -> c1): input grad = conv forward of dd2 with the same weights
-        dd1 = tmp("dd1", P2, c2)
-        self._gemm(dd2, self.V2f, dd1, None, sv.d1, None, N, h1, w1, h2, w2, 2, h2, w2, 1, c1, c2, c1, c2, kk, "conv",
-                   scale=gs, bias_grad=G(f"decoder_cnn.deconv.{i0}.bias"), tag=(N, "dd1"))
-        # deconv0 (c3 -> c2)
-        df = tmp("df", P3, c3)
-        self._gemm(dd1, self.V1f, df, None, None, None, N, h2, w2, h3, w3, 2, h3, w3, 1, c2, c3, c2, c3, kk, "conv")
-
-        # ... then its weight / bias gradients, beside the LSTM chain when overlap is on
-        def decoder_wgrads():
-            if self.overlap:
-                self._wg_cus = max(64, 256 - min(S, 128))     # the LSTM backward kernels run beside these: S workgroups
-            try:
-                decoder_wgrads_()
-            finally:
-                self._wg_cus = 256
-        self._job_blocks = 256      # workgroups per job of a batched job launch
-
-        def decoder_wgrads_():
-            if g_xr is None and sv.b3_parts is not None:
-                ws_b3, nb3 = sv.b3_parts
-                self._jobs.add(JOB_ROWS, ws_b3[nb3:], G(f"decoder_cnn.deconv.{i2}.bias"), (1, 1, oc), (0, 0, 1), nslab=nb3,
-                               slab=4)
-            else:
-                self._colsum(F32, dpre3, N * H * W, oc, oc, G(f"decoder_cnn.deconv.{i2}.bias"), tag=(N, "b3"))
-            if wf3:
-                self._wgrad_first(1, dpre3, (0, 0, 0, 0, 0), sv.d2, N, oc, H, W, c1, c1, wf3,
-                                  G(f"decoder_cnn.deconv.{i2}.weight"), (c1, oc, kk), (self.K3, 1, oc), tag=(N, "V3"))
-            else:
-                self._wgrad(sv.d2, col3, None, P1, c1, self.K3, c1, self.K3, 1, G(f"decoder_cnn.deconv.{i2}.weight"),
-                            (c1, oc, kk), (self.K3, 1, oc), tag=(N, "V3"))
-            self._wgrad(sv.d1, dd2, self._conv_idx(N, h1, w1, h2, w2), P2, c2, c1, c2, c1, kk,
-                        G(f"decoder_cnn.deconv.{i1}.weight"), (c2, c1, kk), (kk * c1, 1, c1), tag=(N, "V2"),
-                        geom=(N, h2, w2, h1, w1))
-            self._wgrad(sv.f, dd1, self._conv_idx(N, h2, w2, h3, w3), P3, c3, c2, c3, c2, kk,
-                        G(f"decoder_cnn.deconv.{i0}.weight"), (c3, c2, kk), (kk * c2, 1, c2), tag=(N, "V1"),
-                        geom=(N, h3, w3, h2, w2))
-            # decoder fc: bias = per (position, channel) sum over frames, permuted to the torch (c, hw) order
-            nf = L.query("rbvae_colsum_ws_floats", N, self.F3)
-            wsf = self._buf((N, "bdfc"), nf)
-            L.call("rbvae_colsum_partial", self.dt, df, N, self.F3, self.F3, wsf)
-            self._jobs.add(JOB_PERMUTE, wsf, G("decoder_cnn.fc.bias"), (c3, g3, 1), (1, c3, 0), nslab=nf // self.F3,
-                           slab=self.F3)
-            self._wgrad(df, sv.ds_pad, None, N, self.F3, self.Lp, self.F3, self.Lp, 1, G("decoder_cnn.fc.weight"),
-                        (c3, g3, Ld), (self.Lp, c3 * self.Lp, 1), tag=(N, "Wdfc"))
-
-        # The gather-index tables both streams' weight-gradient GEMMs read: complete before they enter the cache
-        # (_conv_idx), built here on the main stream before the fork
-        self.prepare(N)
+        # decoder CNN, data-gradient chain first (main stream) ...
+        self._bwd_last_dgrad(p, g_xr)
+        self._bwd_decoder_dgrads(p)
+        # ... then its weight / bias gradients, beside the LSTM chain when overlap is on.  The gather-index tables both
+        # streams' weight-gradient GEMMs read are complete before they enter the cache (_conv_idx), built here on the
+        # main stream before the fork
+        self.prepare(p.N)
         self._fork()
         # with a cut the reductions queued so far (decoder bias sums: their producers ran before the fork) go with the
         # decoder's early reduction, so that every decoder gradient is final at the cut
@@ -1001,7 +949,8 @@ class Engine:
             with self._on_side():
                 if book_with_decoder:
                     side_first()
-                decoder_wgrads()
+                # (with overlap the LSTM backward kernels run beside these: S workgroups that hold one CU each)
+                self._bwd_decoder_wgrads(p, g_xr, cus=max(64, 256 - min(p.S, 128)) if self.overlap else 256)
                 if early:
                     # the decoder's slab / partial-sum reductions right behind them, not at the end of the pass
                     self._run_jobs()
@@ -1014,142 +963,32 @@ class Engine:
                 for ev, fn in side_tail:
                     self._side.wait_event(ev)
                     fn()
-                main_jobs = self._jobs
-            self._jobs = main_jobs
 
         # the main stream's continuation is issued BEFORE the side work (see __init__)
         defer_side = self.overlap
         if not defer_side:
             issue_decoder_side()
-        # as in forward(): slab sums, the cast copy, the column sums and the fused binarise backward are the wavefront
-        # kernel's, which long sequences do not fit
-        bwd_wave = self.lstm_cast and bool(L.query("rbvae_lstm_bwd_wave_ok", T, Ld, nl))
-        split = self.fc_split if bwd_wave else 1
-        if split > 1:
-            dds = tmp("dds", self.fc_split, N, Ld, dtype=f32)
-            L.call("rbvae_skinny_linear_parts", self.dt, df, self.WdfcT, None, dds, N, Ld, self.F3, self.F3, self.F3,
-                   Ld, self.fc_split)
-        else:
-            dds = tmp("dds", N, Ld, dtype=f32)
-            L.call("rbvae_skinny_linear", self.dt, df, self.WdfcT, None, dds, N, Ld, self.F3, self.F3, self.F3, Ld)
-        # --- decoder LSTM
-        wenc, wdec = P("encoder_rnn.lstm.weight_ih_l0"), P("decoder_rnn.lstm.weight_ih_l0")
-        dG = tmp("dG_dec", nl, S, T, 4 * Ld, dtype=f32)
-        dGe = tmp("dG_enc", nl, S, T, 4 * Ld, dtype=f32)
-        d_in_dec = tmp("d_in_dec", N, Ld, dtype=f32)
-        de = tmp("de", N, Ld, dtype=f32)
-        pair_bwd = (self.lstm_pair_bwd and not v.simple_order and bwd_wave and self.bin_bwd_fused
-                    and L.query("rbvae_lstm_pair_bwd_ok", T, Ld, nl))
-        if pair_bwd:
-            # decoder stack -> binarise backward (+ fused KL) -> encoder stack: one wavefront launch
-            de_pad = tmp("de_pad", N, self.Lp)
-            de_sums = self._buf((N, "de_sums"), S * Ld)
-            nparts = split
-            L.call("rbvae_lstm_pair_bwd", wenc, wdec, sv.acts_enc, sv.cs_enc, sv.acts_dec, sv.cs_dec, dds, nparts, N * Ld,
-                   None if g_z is None else g_z.reshape(N, Ld).contiguous(), sv.y, sv.z,
-                   None if g_hs is None else g_hs.reshape(N, Ld).contiguous(), float(sv.tau), sv.tau_dev, float(kl_weight),
-                   float(kl_p), 1e-8, 1, dGe, dG, de, d_in_dec if self.keep_dz else None, de_pad, self.dt, self.Lp, de_sums,
-                   S, T, Ld, nl)
-        elif split > 1:
-            L.call("rbvae_lstm_bwd_ex", wdec, sv.acts_dec, sv.cs_dec, dds, self.fc_split, N * Ld, dG, d_in_dec, None, 0, 0,
-                   None, S, T, Ld, nl)
-        else:
-            L.call("rbvae_lstm_bwd", wdec, self.wT_dec, sv.acts_dec, sv.cs_dec, dds, dG, d_in_dec, S, T, Ld, nl)
-        if pair_bwd:
-            pass
-        elif not v.simple_order:
-            # z -> binarise backward (+ fused KL) -> gradient of h_seq
-            gz = d_in_dec
-            if g_z is not None:
-                gz = gz + g_z.reshape(N, Ld)
-            de_pad = None
-            de_sums = None
-            if bwd_wave and self.bin_bwd_fused:
-                # binarise backward (+ fused KL) in the prologue of the encoder stack's BPTT launch
-                de_pad = tmp("de_pad", N, self.Lp)
-                de_sums = self._buf((N, "de_sums"), S * Ld)
-                L.call("rbvae_lstm_bwd_bin", wenc, sv.acts_enc, sv.cs_enc, gz, sv.y, sv.z,
-                       None if g_hs is None else g_hs.reshape(N, Ld).contiguous(), float(sv.tau), sv.tau_dev, float(kl_weight),
-                       float(kl_p), 1e-8, 1, dGe, de, de_pad, self.dt, self.Lp, de_sums, S, T, Ld, nl)
-            else:
-                if g_hs is not None and g_hs_inplace and g_hs.is_contiguous():
-                    dh = g_hs.view(N, Ld)
-                    L.call("rbvae_binarize_kl_bwd", gz, sv.y, sv.z, dh, 1, N, Ld, float(sv.tau), sv.tau_dev, float(kl_weight), None,
-                           float(kl_p), 1e-8, 1)
-                else:
-                    dh = tmp("dh", N, Ld, dtype=f32)
-                    L.call("rbvae_binarize_kl_bwd", gz, sv.y, sv.z, dh, 0, N, Ld, float(sv.tau), sv.tau_dev, float(kl_weight), None,
-                           float(kl_p), 1e-8, 1)
-                    if g_hs is not None:
-                        dh = dh + g_hs.reshape(N, Ld)
-                if bwd_wave:
-                    de_pad = tmp("de_pad", N, self.Lp)
-                    de_sums = self._buf((N, "de_sums"), S * Ld)        # per-sequence column sums of de: fc bias gradient
-                    L.call("rbvae_lstm_bwd_ex", wenc, sv.acts_enc, sv.cs_enc, dh, 1, 0, dGe, de, de_pad, self.dt, self.Lp,
-                           de_sums, S, T, Ld, nl)
-                else:
-                    L.call("rbvae_lstm_bwd", wenc, self.wT_enc, sv.acts_enc, sv.cs_enc, dh, dGe, de, S, T, Ld, nl)
-        else:
-            de_pad = None
-            de_sums = None
-            # decoder stack input = encoder stack output
-            dz = tmp("dz", N, Ld, dtype=f32)
-            L.call("rbvae_lstm_bwd", wenc, self.wT_enc, sv.acts_enc, sv.cs_enc, d_in_dec, dGe, dz, S, T, Ld, nl)
-            L.call("rbvae_binarize_kl_bwd", dz, sv.y, sv.z, de, 0, N, Ld, float(sv.tau), None, 0.0, None, 0.5, 1e-10, 0)
-            if g_e is not None:
-                de = de + g_e.reshape(N, Ld)
+        self._bwd_latent(p, g_z, g_hs, g_e, kl_weight, kl_p, g_hs_inplace)
         # Side-stream tail (behind the decoder's weight gradients, each piece behind an event on its inputs): launches
         # of the main chain's products that nothing on the chain waits for
         tail_ok = defer_side and cut is None
 
-        def lstm_wgrads():
-            L.call("rbvae_lstm_wgrad_pair", dG, sv.hs_dec, sv.hp_dec, G("decoder_rnn.lstm.weight_ih_l0"),
-                   dGe, sv.hs_enc, sv.hp_enc, G("encoder_rnn.lstm.weight_ih_l0"), S, T, Ld, nl, 0)
+        def tail(fn):
+            if not tail_ok:
+                return fn()
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())
+            side_tail.append((ev, fn))
 
-        if tail_ok:
-            ev_bptt = torch.cuda.Event()
-            ev_bptt.record(torch.cuda.current_stream())
-            side_tail.append((ev_bptt, lstm_wgrads))
-        else:
-            lstm_wgrads()
-        if de_sums is not None and g_e is None:
-            self._jobs.add(JOB_ROWS, de_sums, G("encoder_cnn.fc.bias"), (1, 1, Ld), (0, 0, 1), nslab=S, slab=Ld)
-        else:
-            self._colsum(F32, de, N, Ld, Ld, G("encoder_cnn.fc.bias"), tag=(N, "bfc"))
-        # --- encoder fc
-        if de_pad is None:
-            de_pad = tmp("de_pad", N, self.Lp)
-            L.call("rbvae_cast_pad", self.dt, de, de_pad, N, Ld, self.Lp)
-        def wfc_wgrad():
-            self._wgrad(de_pad, sv.a3, None, N, self.Lp, self.F3, self.Lp, self.F3, 1, G("encoder_cnn.fc.weight"),
-                        (Ld, c3, g3), (self.F3, 1, c3), tag=(N, "Wfc"))
-
+        tail(lambda: self._bwd_lstm_wgrads(p))          # behind ev_bptt: dG_dec / dG_enc are written
+        self._bwd_fc_bias(p, g_e)
         # The encoder fc's weight gradient is a 32-workgroup launch nothing on the data-gradient chain waits for: with
-        # the deferred side work it rides the side stream (behind an event on de_pad), so the main chain goes
+        # the deferred side work it rides the side stream (behind ev_de, an event on de_pad), so the main chain goes
         # straight on to the next data-gradient GEMM instead of queueing it behind a full chip (18 us in the step)
-        if tail_ok:
-            ev_de = torch.cuda.Event()
-            ev_de.record(torch.cuda.current_stream())
-            side_tail.append((ev_de, wfc_wgrad))
-        else:
-            wfc_wgrad()
-        da3 = tmp("da3", P3, c3)
-        # the GEMM sees da3 as [N][F3]; its fused column sums [m-tiles][F3] are [m-tiles*g3][c3] rows,
-        # so the conv3 bias gradient is one row-reduce job over them
-        mt = -(-N // 128)
-        ws3 = self._buf((N, "ws3"), mt * self.F3)
-        self._gemm(de_pad, self.WfcT, da3, None, sv.a3 if v.simple_order else None, None, N, 1, 1, 1, 1, 1, 1, 1, 1,
-                   self.Lp, self.F3, self.Lp, self.F3, 1, "one", colsum_ws=ws3)
-        self._jobs.add(JOB_ROWS, ws3, G(f"encoder_cnn.conv.{i2}.bias"), (1, 1, c3), (0, 0, 1), nslab=mt * g3, slab=c3)
-        # --- conv3
-        idx3, idx2 = self._conv_idx(N, h2, w2, h3, w3), self._conv_idx(N, h1, w1, h2, w2)
+        tail(lambda: self._bwd_fc_wgrad(p))
         # (the encoder's full-chip weight gradients stay on the main stream: on the side stream's tail they only contend
         # with the data-gradient GEMMs, 0.458 -> 0.476 / 0.487 ms per step in round 2)
-        self._wgrad(da3, sv.a2, idx3, P3, c3, c2, c3, c2, kk, G(f"encoder_cnn.conv.{i2}.weight"),
-                    (c3, c2, kk), (kk * c2, 1, c2), tag=(N, "W3"), geom=(N, h3, w3, h2, w2))
-        da2 = tmp("da2", P2, c2)
-        self._gemm(da3, self.W3d, da2, None, sv.a2, None, N, h3, w3, h3, w3, 1, h2, w2, 2, c3, c2, c3, c2, kk, "dgrad",
-                   scale=gs, bias_grad=G(f"encoder_cnn.conv.{i1}.bias"), tag=(N, "da2"))
+        self._bwd_fc_conv3(p)
         if cut is not None:
             # here, not right behind the LSTM kernels: the decoder's weight gradients on the side stream take about as
             # long as the main chain needs to get this far, so the join costs no idle time (at the LSTM kernels it cost
@@ -1159,22 +998,181 @@ class Engine:
                 defer_side = False
             self._join()
             cut()
-        # --- conv2
-        self._wgrad(da2, sv.a1, idx2, P2, c2, c1, c2, c1, kk, G(f"encoder_cnn.conv.{i1}.weight"),
-                    (c2, c1, kk), (kk * c1, 1, c1), tag=(N, "W2"), geom=(N, h2, w2, h1, w1))
-        da1 = tmp("da1", P1, c1)
-        self._gemm(da2, self.W2d, da1, None, sv.a1, None, N, h2, w2, h2, w2, 1, h1, w1, 2, c2, c1, c2, c1, kk, "dgrad",
-                   scale=gs, bias_grad=G(f"encoder_cnn.conv.{i0}.bias"), tag=(N, "da1"))
-        # --- conv1 (1-tap GEMM over the saved im2col columns)
-        if sv.col1 is None:
-            wf1 = self._wf_ksplit(N, self.in_ch, H, W, c1)
-            self._wgrad_first(0, sv.x_in, sv.fm_in, da1, N, self.in_ch, H, W, c1, c1, wf1, G(f"encoder_cnn.conv.{i0}.weight"),
-                              (c1, self.in_ch, kk), (self.K1, 1, self.in_ch), tag=(N, "W1"))
-        else:
-            self._wgrad(da1, sv.col1, None, P1, c1, self.K1, c1, self.K1, 1, G(f"encoder_cnn.conv.{i0}.weight"),
-                        (c1, self.in_ch, kk), (self.K1, 1, self.in_ch), tag=(N, "W1"))
+        self._bwd_conv2_conv1(p)
         if defer_side:
             issue_decoder_side()
         # every slab / partial-sum reduction of this pass in one launch, once the side stream has caught up
         self._join()
         self._run_jobs()
+
+    def _bwd_last_dgrad(self, p: _Pass, g_xr):
+        """dpre3 (from g_xr, or forward()'s) -> dd2, the last deconv's input gradient gated by d2, with deconv1's bias
+        gradient; col3 = dpre3's im2col rows unless the weight gradient reads dpre3 itself (wf3 K-slices)."""
+        sv, N, H, W, k, oc, gs = p.sv, p.N, p.H, p.W, self.k, self.out_ch, p.sv.gate_scale
+        c1, (h1, w1) = self.v.channels[0], self.g1
+        if g_xr is not None:
+            p.dpre3 = p.tmp("dpre3", N, H, W, oc, dtype=torch.float32)
+            L.call("rbvae_sigmoid_bwd_nhwc", g_xr.contiguous(), sv.xr, p.dpre3, N, oc, H, W)
+        else:
+            p.dpre3 = sv.dpre3
+            if p.dpre3 is None:
+                raise RuntimeError("backward without g_xr needs forward(target=..., need_grad=True)")
+        p.dd2 = dd2 = p.tmp("dd2", p.P1, c1)
+        nb = L.query("rbvae_deconv_last_dgrad_blocks", self.dt, oc, H, W, c1, N) if k == 3 and self.K3 == 64 else 0
+        p.wf3 = self._wf_ksplit(N, oc, H, W, c1) if nb else 0      # the last deconv's weight gradient from dpre3 itself
+        p.col3 = col3 = None if p.wf3 else p.tmp("col3", p.P1, self.K3)
+        gb = p.G(self.deconv1.bias)
+        if nb:
+            # im2col + GEMM + gate + bias-gradient partial sums in one kernel (csrc/conv_first.hip, MODE 1)
+            ws = self._buf((N, "colsum_dd2f"), nb * c1)
+            if g_xr is None and sv.dd2_fused is not None:
+                # forward() left dd2, col3 and the column sums in these very buffers (rbvae_deconv_last_fwd_bwd)
+                assert sv.dd2_fused[0].data_ptr() == dd2.data_ptr() and sv.dd2_fused[2].data_ptr() == ws.data_ptr()
+                assert (sv.dd2_fused[1] is None) == (col3 is None) and sv.dd2_fused[3] == nb
+            else:
+                L.call("rbvae_deconv_last_dgrad_fused", self.dt, p.dpre3, self.V3f, self.zero, col3, sv.d2, dd2, N, oc, H, W,
+                       c1, c1, float(gs), ws)
+            self._jobs.add(JOB_ROWS, ws, gb, (1, 1, c1), (0, 0, 1), nslab=nb, slab=c1)
+        else:
+            L.call("rbvae_im2col", self.dt, p.dpre3, H * W * oc, 1, W * oc, oc, N, oc, H, W, h1, w1, k, k, 2, 1, self.K3, col3)
+            self._one(col3, self.V3f, dd2, None, sv.d2, None, p.P1, self.K3, c1, scale=gs, bias_grad=gb, tag=(N, "dd2"))
+
+    def _bwd_decoder_dgrads(self, p: _Pass):
+        """dd2 -> dd1 -> df: a deconv's input gradient = the conv forward of its output gradient with the same weights."""
+        sv, N = p.sv, p.N
+        p.dd1 = p.tmp("dd1", p.P2, self.deconv1.cs)
+        self._down(self.deconv1, N, p.dd2, p.dd1, None, sv.d1, None, scale=sv.gate_scale,
+                   bias_grad=p.G(self.deconv0.bias), tag=(N, "dd1"))
+        p.df = p.tmp("df", p.P3, self.deconv0.cs)
+        self._down(self.deconv0, N, p.dd1, p.df, None, None, None)
+
+    def _bwd_decoder_wgrads(self, p: _Pass, g_xr, cus):
+        """Weight / bias gradients of the three deconvs and the decoder fc, on the `cus` CUs their launches can count on."""
+        sv, N, H, W, oc, kk, G = p.sv, p.N, p.H, p.W, self.out_ch, self.kk, p.G
+        c1, c2, c3 = self.v.channels
+        g3 = self.g3[0] * self.g3[1]
+        if g_xr is None and sv.b3_parts is not None:
+            ws_b3, nb3 = sv.b3_parts
+            self._jobs.add(JOB_ROWS, ws_b3[nb3:], G(self.deconv2.bias), (1, 1, oc), (0, 0, 1), nslab=nb3, slab=4)
+        else:
+            self._colsum(F32, p.dpre3, N * H * W, oc, oc, G(self.deconv2.bias), tag=(N, "b3"))
+        if p.wf3:
+            self._wgrad_first(1, p.dpre3, (0, 0, 0, 0, 0), sv.d2, N, oc, H, W, c1, c1, p.wf3, G(self.deconv2.weight),
+                              (c1, oc, kk), (self.K3, 1, oc), tag=(N, "V3"))
+        else:
+            self._wgrad(sv.d2, p.col3, None, p.P1, c1, self.K3, c1, self.K3, 1, G(self.deconv2.weight), (c1, oc, kk),
+                        (self.K3, 1, oc), tag=(N, "V3"), cus=cus)
+        self._wgrad_s2(self.deconv1, p, sv.d1, p.dd2, "V2", cus)
+        self._wgrad_s2(self.deconv0, p, sv.f, p.dd1, "V1", cus)
+        # decoder fc: bias = per (position, channel) sum over frames, permuted to the torch (c, hw) order
+        nf = L.query("rbvae_colsum_ws_floats", N, self.F3)
+        wsf = self._buf((N, "bdfc"), nf)
+        L.call("rbvae_colsum_partial", self.dt, p.df, N, self.F3, self.F3, wsf)
+        self._jobs.add(JOB_PERMUTE, wsf, G("decoder_cnn.fc.bias"), (c3, g3, 1), (1, c3, 0), nslab=nf // self.F3, slab=self.F3)
+        self._wgrad(p.df, sv.ds_pad, None, N, self.F3, self.Lp, self.F3, self.Lp, 1, G("decoder_cnn.fc.weight"),
+                    (c3, g3, self.latent), (self.Lp, c3 * self.Lp, 1), tag=(N, "Wdfc"), cus=cus)
+
+    def _bwd_latent(self, p: _Pass, g_z, g_hs, g_e, kl_weight, kl_p, g_hs_inplace):
+        """df -> decoder fc -> decoder stack -> binarise backward (+ fused KL) -> encoder stack (the simple variant: both
+        stacks, then the binarisation) -> de, the logits' gradient.  Leaves dG / dGe for the LSTM weight gradients and,
+        from the wavefront kernels, de's padded copy and its per-sequence column sums (the fc bias gradient)."""
+        v, sv, N, S, T, Ld, nl, f32 = self.v, p.sv, p.N, p.S, p.T, self.latent, self.v.lstm_layers, torch.float32
+        # as in forward(): slab sums, the cast copy, the column sums and the fused binarise backward are the wavefront
+        # kernel's, which long sequences do not fit
+        bwd_wave = self.wave_ok and bool(L.query("rbvae_lstm_bwd_wave_ok", T, Ld, nl))
+        split = self.fc_split if bwd_wave else 1
+        parts = (split,) if split > 1 else ()        # the decoder fc's input gradient: K-slabs the BPTT launch sums, or whole
+        dds = p.tmp("dds", *parts, N, Ld, dtype=f32)
+        L.call("rbvae_skinny_linear_parts" if parts else "rbvae_skinny_linear", self.dt, p.df, self.WdfcT, None, dds, N, Ld,
+               self.F3, self.F3, self.F3, Ld, *parts)
+        wenc, wdec = p.P("encoder_rnn.lstm.weight_ih_l0"), p.P("decoder_rnn.lstm.weight_ih_l0")
+        p.dG = dG = p.tmp("dG_dec", nl, S, T, 4 * Ld, dtype=f32)
+        p.dGe = dGe = p.tmp("dG_enc", nl, S, T, 4 * Ld, dtype=f32)
+        d_in_dec = p.tmp("d_in_dec", N, Ld, dtype=f32)
+        p.de = de = p.tmp("de", N, Ld, dtype=f32)
+        p.de_pad = de_pad = p.tmp("de_pad", N, self.Lp) if bwd_wave else None
+        p.de_sums = de_sums = self._buf((N, "de_sums"), S * Ld) if bwd_wave else None
+        rows = lambda g: None if g is None else g.reshape(N, Ld).contiguous()
+        bin_args = (float(sv.tau), sv.tau_dev, float(kl_weight), float(kl_p), 1e-8, 1)
+        if bwd_wave and L.query("rbvae_lstm_pair_bwd_ok", T, Ld, nl):
+            # decoder stack -> binarise backward (+ fused KL) -> encoder stack: one wavefront launch (the codes'
+            # gradient is not stored: None)
+            L.call("rbvae_lstm_pair_bwd", wenc, wdec, sv.acts_enc, sv.cs_enc, sv.acts_dec, sv.cs_dec, dds, split, N * Ld,
+                   rows(g_z), sv.y, sv.z, rows(g_hs), *bin_args, dGe, dG, de, None, de_pad, self.dt, self.Lp, de_sums,
+                   S, T, Ld, nl)
+            return
+        self._lstm_bwd(p, wdec, self.wT_dec, sv.acts_dec, sv.cs_dec, dds, dG, d_in_dec, nparts=split)
+        if v.simple_order:
+            # decoder stack input = encoder stack output
+            dz = p.tmp("dz", N, Ld, dtype=f32)
+            self._lstm_bwd(p, wenc, self.wT_enc, sv.acts_enc, sv.cs_enc, d_in_dec, dGe, dz)
+            L.call("rbvae_binarize_kl_bwd", dz, sv.y, sv.z, de, 0, N, Ld, float(sv.tau), None, 0.0, None, 0.5, 1e-10, 0)
+            if g_e is not None:
+                p.de = de + g_e.reshape(N, Ld)
+            return
+        # z -> binarise backward (+ fused KL) -> gradient of h_seq
+        gz = d_in_dec if g_z is None else d_in_dec + g_z.reshape(N, Ld)
+        if bwd_wave:
+            # ... in the prologue of the encoder stack's BPTT launch
+            L.call("rbvae_lstm_bwd_bin", wenc, sv.acts_enc, sv.cs_enc, gz, sv.y, sv.z, rows(g_hs), *bin_args, dGe, de,
+                   de_pad, self.dt, self.Lp, de_sums, S, T, Ld, nl)
+            return
+        inplace = g_hs is not None and g_hs_inplace and g_hs.is_contiguous()
+        dh = g_hs.view(N, Ld) if inplace else p.tmp("dh", N, Ld, dtype=f32)
+        L.call("rbvae_binarize_kl_bwd", gz, sv.y, sv.z, dh, int(inplace), N, Ld, float(sv.tau), sv.tau_dev,
+               float(kl_weight), None, float(kl_p), 1e-8, 1)
+        if g_hs is not None and not inplace:
+            dh = dh + g_hs.reshape(N, Ld)
+        self._lstm_bwd(p, wenc, self.wT_enc, sv.acts_enc, sv.cs_enc, dh, dGe, de)
+
+    def _bwd_lstm_wgrads(self, p: _Pass):
+        sv = p.sv
+        L.call("rbvae_lstm_wgrad_pair", p.dG, sv.hs_dec, sv.hp_dec, p.G("decoder_rnn.lstm.weight_ih_l0"),
+               p.dGe, sv.hs_enc, sv.hp_enc, p.G("encoder_rnn.lstm.weight_ih_l0"), p.S, p.T, self.latent, self.v.lstm_layers, 0)
+
+    def _bwd_fc_bias(self, p: _Pass, g_e):
+        """The encoder fc's bias gradient (column sums of de) and de's padded copy, where the LSTM launch left neither."""
+        N, Ld = p.N, self.latent
+        if p.de_sums is not None and g_e is None:
+            self._jobs.add(JOB_ROWS, p.de_sums, p.G("encoder_cnn.fc.bias"), (1, 1, Ld), (0, 0, 1), nslab=p.S, slab=Ld)
+        else:
+            self._colsum(F32, p.de, N, Ld, Ld, p.G("encoder_cnn.fc.bias"), tag=(N, "bfc"))
+        if p.de_pad is None:
+            p.de_pad = p.tmp("de_pad", N, self.Lp)
+            L.call("rbvae_cast_pad", self.dt, p.de, p.de_pad, N, Ld, self.Lp)
+
+    def _bwd_fc_wgrad(self, p: _Pass):
+        c3, g3 = self.v.channels[2], self.g3[0] * self.g3[1]
+        self._wgrad(p.de_pad, p.sv.a3, None, p.N, self.Lp, self.F3, self.Lp, self.F3, 1, p.G("encoder_cnn.fc.weight"),
+                    (self.latent, c3, g3), (self.F3, 1, c3), tag=(p.N, "Wfc"))
+
+    def _bwd_fc_conv3(self, p: _Pass):
+        """de_pad -> da3 (gated by a3 in the simple variant) -> da2, with conv3's / conv2's bias and conv3's weight gradient."""
+        N, c3, g3 = p.N, self.v.channels[2], self.g3[0] * self.g3[1]
+        p.da3 = p.tmp("da3", p.P3, c3)
+        # the GEMM sees da3 as [N][F3]; its fused column sums [m-tiles][F3] are [m-tiles*g3][c3] rows,
+        # so the conv3 bias gradient is one row-reduce job over them
+        mt = -(-N // 128)
+        ws3 = self._buf((N, "ws3"), mt * self.F3)
+        self._one(p.de_pad, self.WfcT, p.da3, None, p.sv.a3 if self.v.simple_order else None, None, N, self.Lp, self.F3,
+                  colsum_ws=ws3)
+        self._jobs.add(JOB_ROWS, ws3, p.G(self.conv3.bias), (1, 1, c3), (0, 0, 1), nslab=mt * g3, slab=c3)
+        self._wgrad_s2(self.conv3, p, p.da3, p.sv.a2, "W3")
+        p.da2 = p.tmp("da2", p.P2, self.conv3.cb)
+        self._up(self.conv3, N, p.da3, p.da2, None, p.sv.a2, None, scale=p.sv.gate_scale, bias_grad=p.G(self.conv2.bias),
+                 tag=(N, "da2"))
+
+    def _bwd_conv2_conv1(self, p: _Pass):
+        """conv2's weight gradient; da2 -> da1 with conv1's bias gradient; conv1's weight gradient (frames or im2col rows)."""
+        sv, N, H, W, C, kk = p.sv, p.N, p.H, p.W, self.in_ch, self.kk
+        c1 = self.v.channels[0]
+        self._wgrad_s2(self.conv2, p, p.da2, sv.a1, "W2")
+        da1 = p.tmp("da1", p.P1, c1)
+        self._up(self.conv2, N, p.da2, da1, None, sv.a1, None, scale=sv.gate_scale, bias_grad=p.G(self.conv1.bias),
+                 tag=(N, "da1"))
+        out, dims, strides = p.G(self.conv1.weight), (c1, C, kk), (self.K1, 1, C)
+        if sv.col1 is None:
+            wf1 = self._wf_ksplit(N, C, H, W, c1)
+            self._wgrad_first(0, sv.x_in, sv.fm_in, da1, N, C, H, W, c1, c1, wf1, out, dims, strides, tag=(N, "W1"))
+        else:
+            self._wgrad(da1, sv.col1, None, p.P1, c1, self.K1, c1, self.K1, 1, out, dims, strides, tag=(N, "W1"))

@@ -20,5 +20,5 @@ for Ld in (int(a) for a in (sys.argv[1:] or ["25", "32", "50", "64", "75", "100"
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / n
     eng = tr.eng
-    print(f"L={Ld:4d}: {dt * 1e3:.4f} ms/step  {256 / dt:9.0f} frames/s  pair_fwd={bool(eng.lstm_pair and sfv._lib.query('rbvae_lstm_pair_fwd_ok', 8, Ld, 4))} "
-          f"fc_split={eng.fc_split} lstm_cast={eng.lstm_cast} loss={tr.losses[0].item():.3f}", flush=True)
+    print(f"L={Ld:4d}: {dt * 1e3:.4f} ms/step  {256 / dt:9.0f} frames/s  pair_fwd={bool(eng.wave_ok and sfv._lib.query('rbvae_lstm_pair_fwd_ok', 8, Ld, 4))} "
+          f"fc_split={eng.fc_split} wave_ok={eng.wave_ok} loss={tr.losses[0].item():.3f}", flush=True)
