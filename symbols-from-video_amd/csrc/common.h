@@ -24,6 +24,19 @@ int fail(int code, const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The Bernoulli prior p of the KL term as the kernels take it: log p and log(1 - p).  `on`: whether the launch evaluates
+// the KL term at all; off, p is not looked at and both logs are 0 (no kernel reads them).  False: p outside (0, 1); the
+// wrapper refuses in its own words:  RBVAE_CHECK_ARG(kl_prior(on, kl_p, &kp), "<who>: ... %g ...", kl_p).
+struct KlPrior { float lp, l1p; };
+static inline bool kl_prior(bool on, float p, KlPrior* kp) {
+    kp->lp = kp->l1p = 0.f;
+    if (!on) return true;
+    if (!(p > 0.f && p < 1.f)) return false;
+    kp->lp = logf(p);
+    kp->l1p = logf(1.0f - p);
+    return true;
+}
+
 // dynamic LDS of a kernel instance: once per instance, allow `bytes` ...
 template <auto KERNEL> static inline void lds_attr_once(int bytes) {
     static bool attr_set = false;
@@ -107,6 +120,17 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// binary_concrete_logits (percep_RBVAE_model.py:17-44) from the logit h and its logistic noise: y is saved for the
+// backward, z (hard or soft) is the code.  One definition for the stand-alone binarise kernels (losses.hip) and the seam
+// of the LSTM pair forward kernels (lstm.hip).  How h + noise is rounded is the caller's: see bc_noise in losses.hip.
+struct BinCode { float y, z; };
+__device__ __forceinline__ BinCode bin_code(float h, float noise, float tau, int hard) {
+    BinCode r;
+    r.y = sigmoidf_((h + noise) / tau);
+    r.z = hard ? (r.y > 0.5f ? 1.0f : 0.0f) : r.y;
+    return r;
+}
 
 // torch.optim.Adam on one element (percep_RBVAE_train.py:753,553): g is scaled by gscale, m / v are updated in place,
 // the new weight is returned.  step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t).  Explicit fma placement: every

@@ -604,7 +604,9 @@ __global__ __launch_bounds__(1024) void lstm_pair_fwd_k(const PairArgs p) {
     }
     // ---- encoder input (plain or K-split slabs) and the noise term, staged by all threads.  The slab loads of an
     // element are issued together (summed in slab order all the same) and the step counter is read once: as a loop of
-    // dependent loads this prologue cost five memory round trips before the first time step.
+    // dependent loads this prologue cost five memory round trips before the first time step.  Its last two lines mirror
+    // bc_uniform and bc_noise of losses.hip (typed out: the uniform comes from a load issued above, and the noise is
+    // rounded to f32 here and added on a later diagonal, where the binarise kernels contract it into one fma).
     for (int i = threadIdx.x; i < T * L; i += blockDim.x) {
         const long o = ((long)s * T) * L + i;
         // unconditional loads on always-valid addresses (absent operands alias the input element / a weight): nothing
@@ -683,7 +685,7 @@ __global__ __launch_bounds__(1024) void lstm_pair_fwd_k(const PairArgs p) {
             if (q == layers - 1) {
                 // binary_concrete_logits on the encoder's output (percep_RBVAE_model.py:17-44): z feeds the decoder stack
                 const long e = ((long)s * T + t) * L + j;
-                const LstmCode code = lstm_binarise(h, nbuf[t * LS + j], inv_tau_src, p.hard);
+                const BinCode code = bin_code(h, nbuf[t * LS + j], inv_tau_src, p.hard);
                 p.y_soft[e] = code.y;
                 p.hs_d[e] = code.z;
                 hbuf[(layers + 1) * T * LS + t * LS + j] = code.z;        // decoder stack, slot 0
@@ -757,7 +759,8 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
         for (int k = 0; k < L; ++k) { wih[g][k] = pi[k * kstride]; whh[g][k] = ph[k * kstride]; }
     }
     // the input staging of lstm_pair_fwd_k, typed out again with LS == L (as a helper one scalar branch of each
-    // listing changes, and the timing check cannot tell that from a rebuild); keep the two alike
+    // listing changes, and the timing check cannot tell that from a rebuild); keep the two alike (uniform and noise:
+    // bc_uniform / bc_noise of losses.hip, as there)
     for (int i = threadIdx.x; i < T * L; i += blockDim.x) {
         const long o = ((long)s * T) * L + i;
         const bool parts = p.in_parts != nullptr;
@@ -843,7 +846,7 @@ __global__ __launch_bounds__(512) void lstm_pair_fwd_unit_k(const PairArgs p) {
                 hs_all[(((long)(l + 1) * S + s) * T + t) * L + j] = h;
                 if (q == layers - 1) {
                     const long e = ((long)s * T + t) * L + j;
-                    const LstmCode code = lstm_binarise(h, nbuf[t * LS + j], inv_tau_src, p.hard);
+                    const BinCode code = bin_code(h, nbuf[t * LS + j], inv_tau_src, p.hard);
                     p.y_soft[e] = code.y;
                     p.hs_d[e] = code.z;
                     hbuf[(layers + 1) * T * LS + t * LS + j] = code.z;        // decoder stack, slot 0
@@ -1496,8 +1499,8 @@ static size_t pair_bwd_lds(int T, int L, int layers) {
 #define LSTM_CHECK_CAST(who) \
     RBVAE_CHECK_ARG(!cast_out || ((cast_dtype == RBVAE_F32 || cast_dtype == RBVAE_BF16) && cast_ld >= L), \
                     who ": cast output dtype %d ld %d", cast_dtype, cast_ld)
-#define LSTM_CHECK_KL_P(who) \
-    RBVAE_CHECK_ARG(kl_weight == 0.f || (kl_p > 0.f && kl_p < 1.f), who ": kl_p=%g outside (0,1)", kl_p)
+#define LSTM_CHECK_KL_P(who) /* fills the wrapper's KlPrior kp (common.h); the KL term is off at weight 0 */ \
+    RBVAE_CHECK_ARG(kl_prior(kl_weight != 0.f, kl_p, &kp), who ": kl_p=%g outside (0,1)", kl_p)
 
 // lstm_fwd_big_k / lstm_bwd_big_k are instantiated for these dot-product lengths (16-byte chunks): LAUNCH(N) with the
 // smallest N >= nch
@@ -1510,11 +1513,11 @@ static size_t pair_bwd_lds(int T, int L, int layers) {
 
 // the binarise backward's arguments as the kernels take them (gz: null where the gradient of the codes never leaves the chip)
 static BinBwd bin_bwd_args(const float* gz, const float* y_soft, const float* z, const float* g_hs, float tau,
-                           const float* tau_dev, float kl_weight, float kl_p, float kl_eps, int kl_clamp, int S, int T) {
+                           const float* tau_dev, float kl_weight, KlPrior kp, float kl_eps, int kl_clamp, int S, int T) {
     BinBwd bb;
     bb.gz = gz; bb.y = y_soft; bb.z = z; bb.g_hs = g_hs; bb.tau = tau; bb.tau_dev = tau_dev;
     bb.klw = kl_weight / (float)((long)S * T);
-    bb.lp = kl_weight != 0.f ? logf(kl_p) : 0.f; bb.l1p = kl_weight != 0.f ? logf(1.0f - kl_p) : 0.f;
+    bb.lp = kp.lp; bb.l1p = kp.l1p;
     bb.keps = kl_eps; bb.clamp = kl_clamp; bb.on = 1;
     return bb;
 }
@@ -1614,7 +1617,8 @@ int rbvae_lstm_pair_fwd(const float* wblk_enc, const float* wT_enc, const float*
     RBVAE_CHECK_ARG((acts_enc == nullptr) == (cs_enc == nullptr) && (acts_enc == nullptr) == (hprev_enc == nullptr) &&
                     (acts_dec == nullptr) == (acts_enc == nullptr) && (cs_dec == nullptr) == (acts_enc == nullptr) &&
                     (hprev_dec == nullptr) == (acts_enc == nullptr), "lstm_pair_fwd: saved-state buffers must be given together");
-    RBVAE_CHECK_ARG((tau_dev || tau > 0.f) && (!kl_parts || (kl_p > 0.f && kl_p < 1.f)), "lstm_pair_fwd: tau=%g kl_p=%g", tau, kl_p);
+    KlPrior kp;
+    RBVAE_CHECK_ARG((tau_dev || tau > 0.f) && kl_prior(kl_parts != nullptr, kl_p, &kp), "lstm_pair_fwd: tau=%g kl_p=%g", tau, kl_p);
     RBVAE_CHECK_ARG(!in_parts || (nparts >= 1 && part_stride >= (long)S * T * L), "lstm_pair_fwd: bad slabs");
     LSTM_CHECK_CAST("lstm_pair_fwd");
     PairArgs a;
@@ -1623,8 +1627,8 @@ int rbvae_lstm_pair_fwd(const float* wblk_enc, const float* wT_enc, const float*
     a.hs_d = hs_dec; a.hp_d = hprev_dec; a.acts_d = acts_dec; a.cs_d = cs_dec;
     a.in_parts = in_parts; a.nparts = nparts; a.part_stride = part_stride;
     a.U = U; a.y_soft = y_soft; a.kl_parts = kl_parts;
-    a.tau = tau; a.tau_dev = tau_dev; a.ratio = noise_ratio; a.neps = noise_eps; a.lp = kl_parts ? logf(kl_p) : 0.f;
-    a.l1p = kl_parts ? logf(1.0f - kl_p) : 0.f; a.keps = kl_eps; a.hard = hard; a.clamp = kl_clamp;
+    a.tau = tau; a.tau_dev = tau_dev; a.ratio = noise_ratio; a.neps = noise_eps; a.lp = kp.lp;
+    a.l1p = kp.l1p; a.keps = kl_eps; a.hard = hard; a.clamp = kl_clamp;
     a.seed = seed; a.seed_dev = seed_dev;
     a.cast_out = cast_out; a.cast_bf16 = cast_dtype == RBVAE_BF16; a.cast_ld = cast_ld;
     const int threads = lstm_group_threads(L);
@@ -1705,8 +1709,9 @@ int rbvae_lstm_bwd_bin(const float* wblk, const float* acts, const float* cs, co
                        float kl_eps, int kl_clamp, float* dG, float* dx, void* cast_out, int cast_dtype, int cast_ld, float* dx_colsum,
                        int S, int T, int L, int layers, void* stream) {
     RBVAE_CHECK_ARG(g_z && y_soft && z && (tau_dev || tau > 0.f), "lstm_bwd_bin: bad arguments");
+    KlPrior kp;
     LSTM_CHECK_KL_P("lstm_bwd_bin");
-    const BinBwd bb = bin_bwd_args(g_z, y_soft, z, g_hs, tau, tau_dev, kl_weight, kl_p, kl_eps, kl_clamp, S, T);
+    const BinBwd bb = bin_bwd_args(g_z, y_soft, z, g_hs, tau, tau_dev, kl_weight, kp, kl_eps, kl_clamp, S, T);
     return lstm_bwd_impl(wblk, nullptr, acts, cs, g_z, dG, dx, S, T, L, layers, 1, 0, cast_out, cast_dtype, cast_ld, dx_colsum, bb,
                          stream);
 }
@@ -1727,6 +1732,7 @@ int rbvae_lstm_pair_bwd(const float* wblk_enc, const float* wblk_dec, const floa
                     "range (rbvae_lstm_pair_bwd_ok)", T, L, layers);
     RBVAE_CHECK_ARG(nparts >= 1 && (nparts == 1 || part_stride >= (long)S * T * L), "lstm_pair_bwd: bad slabs");
     RBVAE_CHECK_ARG(tau_dev || tau > 0.f, "lstm_pair_bwd: tau=%g", tau);
+    KlPrior kp;
     LSTM_CHECK_KL_P("lstm_pair_bwd");
     LSTM_CHECK_CAST("lstm_pair_bwd");
     PairBwdArgs a;
@@ -1734,7 +1740,7 @@ int rbvae_lstm_pair_bwd(const float* wblk_enc, const float* wblk_dec, const floa
     a.g_top = g_top_parts; a.nparts = nparts; a.part_stride = part_stride;
     a.dG_e = dG_enc; a.dG_d = dG_dec; a.dx = dx; a.dz = dz; a.gz_extra = gz_extra;
     a.cast_out = cast_out; a.cast_bf16 = cast_dtype == RBVAE_BF16; a.cast_ld = cast_ld; a.dx_colsum = dx_colsum;
-    a.bb = bin_bwd_args(nullptr, y_soft, z, g_hs, tau, tau_dev, kl_weight, kl_p, kl_eps, kl_clamp, S, T);
+    a.bb = bin_bwd_args(nullptr, y_soft, z, g_hs, tau, tau_dev, kl_weight, kp, kl_eps, kl_clamp, S, T);
     const int threads = lstm_group_threads(L);
     a.S = S; a.T = T; a.L = L; a.layers = layers; a.G = threads;
     const size_t lds = pair_bwd_lds(T, L, layers);

@@ -49,15 +49,8 @@ __device__ __forceinline__ LstmCell lstm_cell(float ig, float fg, float gg, floa
     return r;
 }
 
-// The seam, forward: binary_concrete_logits on the encoder's output (percep_RBVAE_model.py:17-44); y is saved, z (hard or
-// soft) feeds the decoder stack
-struct LstmCode { float y, z; };
-__device__ __forceinline__ LstmCode lstm_binarise(float h, float noise, float tau, int hard) {
-    LstmCode r;
-    r.y = sigmoidf_((h + noise) / tau);
-    r.z = hard ? (r.y > 0.5f ? 1.0f : 0.0f) : r.y;
-    return r;
-}
+// The seam, forward: bin_code (common.h, shared with the binarise kernels of losses.hip) on the encoder's output; z feeds
+// the decoder stack
 
 // ---- backward --------------------------------------------------------------------------------------------------------
 // The seam, backward: the gradient of the codes gz (extra gradient and klw * dKL/dz already added, in that order) through

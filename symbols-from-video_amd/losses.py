@@ -21,6 +21,16 @@ def _rows(t):
     return t.detach().reshape(-1, t.shape[-1]).float().contiguous()
 
 
+def _scalar_out(t):
+    """The one-float output of a forward kernel, on t's device (returned to autograd as out.reshape(()))."""
+    return torch.empty(1, device=t.device)
+
+
+def _upstream(g):
+    """The upstream gradient as the backward kernels take it: one f32 on the device (their gscale_dev)."""
+    return g.reshape(1).float().contiguous()
+
+
 class _Mse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -28,7 +38,7 @@ class _Mse(torch.autograd.Function):
         if a.shape != b.shape:
             raise RuntimeError(f"recon_loss: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
         af, bf = a.detach().float().contiguous(), b.detach().float().contiguous()
-        out = torch.empty(1, device=a.device)
+        out = _scalar_out(a)
         ws = torch.empty(L.query("rbvae_mse_ws_floats", af.numel()), device=a.device)
         L.call("rbvae_mse_fwd", af, bf, af.numel(), out, ws)
         ctx.save_for_backward(af, bf)
@@ -38,7 +48,7 @@ class _Mse(torch.autograd.Function):
     def backward(ctx, g):
         af, bf = ctx.saved_tensors
         da = torch.empty_like(af)
-        L.call("rbvae_mse_bwd", af, bf, af.numel(), 1.0, g.reshape(1).float().contiguous(), da)
+        L.call("rbvae_mse_bwd", af, bf, af.numel(), 1.0, _upstream(g), da)
         return da, -da
 
 
@@ -53,7 +63,7 @@ class _Kl(torch.autograd.Function):
         if not 0.0 < p < 1.0:
             raise ValueError(f"kl_binary_concrete: p={p} must lie in (0, 1)")
         qf = _rows(q)
-        out = torch.empty(1, device=q.device)
+        out = _scalar_out(q)
         L.call("rbvae_kl_fwd", qf, out, qf.shape[0], qf.shape[1], float(p), float(eps), int(clamp))
         ctx.save_for_backward(qf)
         ctx.cfg = (float(p), float(eps), int(clamp), q.shape)
@@ -64,7 +74,7 @@ class _Kl(torch.autograd.Function):
         (qf,) = ctx.saved_tensors
         p, eps, clamp, shape = ctx.cfg
         dq = torch.empty_like(qf)
-        L.call("rbvae_kl_bwd", qf, dq, qf.shape[0], qf.shape[1], p, eps, clamp, 1.0, g.reshape(1).float().contiguous())
+        L.call("rbvae_kl_bwd", qf, dq, qf.shape[0], qf.shape[1], p, eps, clamp, 1.0, _upstream(g))
         return dq.reshape(shape), None, None, None
 
 
@@ -83,7 +93,7 @@ class _PairDist(torch.autograd.Function):
         if x1.shape != x2.shape:
             raise RuntimeError(f"contrast_loss: shapes {tuple(x1.shape)} and {tuple(x2.shape)} differ")
         a, b = _rows(x1), _rows(x2)
-        out = torch.empty(1, device=x1.device)
+        out = _scalar_out(x1)
         Ld = a.shape[1]
         L.call("rbvae_pairdist_fwd", a, b, Ld, Ld, a.shape[0], Ld, int(label), float(margin), 1e-6, out)
         ctx.save_for_backward(a, b)
@@ -97,7 +107,7 @@ class _PairDist(torch.autograd.Function):
         da, db = torch.empty_like(a), torch.empty_like(b)
         Ld = a.shape[1]
         L.call("rbvae_pairdist_bwd", a, b, Ld, Ld, a.shape[0], Ld, label, margin, 1e-6, 1.0,
-               g.reshape(1).float().contiguous(), da, db, Ld, Ld, 0)
+               _upstream(g), da, db, Ld, Ld, 0)
         return da.reshape(shape), db.reshape(shape), None, None
 
 
@@ -113,7 +123,7 @@ class _PairCos(torch.autograd.Function):
         b = x2.detach().float().movedim(1, -1).contiguous()
         Ld = a.shape[-1]
         a2, b2 = a.reshape(-1, Ld), b.reshape(-1, Ld)
-        out = torch.empty(1, device=x1.device)
+        out = _scalar_out(x1)
         L.call("rbvae_paircos_fwd", a2, b2, Ld, Ld, a2.shape[0], Ld, int(label), float(margin), 1e-8, out)
         ctx.save_for_backward(a2, b2)
         ctx.cfg = (int(label), float(margin), a.shape)
@@ -126,7 +136,7 @@ class _PairCos(torch.autograd.Function):
         da, db = torch.empty_like(a2), torch.empty_like(b2)
         Ld = a2.shape[1]
         L.call("rbvae_paircos_bwd", a2, b2, Ld, Ld, a2.shape[0], Ld, label, margin, 1e-8, 1.0,
-               g.reshape(1).float().contiguous(), da, db, Ld, Ld)
+               _upstream(g), da, db, Ld, Ld)
         return da.reshape(shape).movedim(-1, 1), db.reshape(shape).movedim(-1, 1), None, None
 
 
@@ -146,7 +156,7 @@ class _Triplet(torch.autograd.Function):
     def forward(ctx, a, p, n, margin, eps, swap):
         _need_cuda(a, "triplet_loss")
         af, pf, nf = _rows(a), _rows(p), _rows(n)
-        out = torch.empty(1, device=a.device)
+        out = _scalar_out(a)
         Ld = af.shape[1]
         L.call("rbvae_triplet_fwd", af, pf, nf, Ld, Ld, Ld, af.shape[0], Ld, float(margin), float(eps), int(swap), out)
         ctx.save_for_backward(af, pf, nf)
@@ -160,7 +170,7 @@ class _Triplet(torch.autograd.Function):
         da, dp, dn = (torch.empty_like(af) for _ in range(3))
         Ld = af.shape[1]
         L.call("rbvae_triplet_bwd", af, pf, nf, Ld, Ld, Ld, af.shape[0], Ld, margin, eps, swap, 1.0,
-               g.reshape(1).float().contiguous(), da, dp, dn, Ld, Ld, Ld, 0)
+               _upstream(g), da, dp, dn, Ld, Ld, Ld, 0)
         return da.reshape(shape), dp.reshape(shape), dn.reshape(shape), None, None, None
 
 
@@ -187,7 +197,7 @@ class _ContrastTerm(torch.autograd.Function):
         if T < 2:
             raise ZeroDivisionError("float division by zero")   # what the reference raises for one state (:541)
         a, b = h0.detach().float().contiguous(), h1.detach().float().contiguous()
-        out = torch.empty(1, device=h0.device)
+        out = _scalar_out(h0)
         L.call("rbvae_contrast_term_fwd", a, b, B, T, Ld, out)
         ctx.save_for_backward(a, b)
         return out.reshape(())
@@ -197,7 +207,7 @@ class _ContrastTerm(torch.autograd.Function):
         a, b = ctx.saved_tensors
         B, T, Ld = a.shape
         d0, d1 = torch.empty_like(a), torch.empty_like(b)
-        L.call("rbvae_contrast_term_bwd", a, b, B, T, Ld, 1.0, g.reshape(1).float().contiguous(), d0, d1)
+        L.call("rbvae_contrast_term_bwd", a, b, B, T, Ld, 1.0, _upstream(g), d0, d1)
         return d0, d1
 
 
@@ -213,7 +223,7 @@ class _TripletTerm(torch.autograd.Function):
         if T < 2:
             raise ZeroDivisionError("float division by zero")
         a, b = h0.detach().float().contiguous(), h1.detach().float().contiguous()
-        out = torch.empty(1, device=h0.device)
+        out = _scalar_out(h0)
         L.call("rbvae_triplet_term_fwd", a, b, B, T, Ld, float(margin), out)
         ctx.save_for_backward(a, b)
         ctx.margin = float(margin)
@@ -224,7 +234,7 @@ class _TripletTerm(torch.autograd.Function):
         a, b = ctx.saved_tensors
         B, T, Ld = a.shape
         d0, d1 = torch.empty_like(a), torch.empty_like(b)
-        L.call("rbvae_triplet_term_bwd", a, b, B, T, Ld, ctx.margin, 1.0, g.reshape(1).float().contiguous(), d0, d1)
+        L.call("rbvae_triplet_term_bwd", a, b, B, T, Ld, ctx.margin, 1.0, _upstream(g), d0, d1)
         return d0, d1, None
 
 
